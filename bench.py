@@ -29,6 +29,8 @@ One JSON line is printed by rank 0.  Extra objects:
 as the reference spawns its own self-play workers (train_RL.py:215-227); under a launcher WORLD_SIZE must equal --gpus.
   cpu_baseline  the oracle (reference algorithm restated on the CPU: one leaf per step, per-game pointer tree,
                 batch-1 fp32 forward on the host cores) on BASELINE.json configs[0], timed on rank 0 over a bounded sample
+`--dump-outputs DIR` writes, after the timed steps, what the last timed ply returned (ply record + network outputs, float32 .npy, <= 64 MB) for
+output-for-output comparison of two builds; weights, start positions and sampling draws are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -290,6 +292,37 @@ def train_step_sample(dev, batch=128, steps=40):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_POLICY_ROWS = 256
+
+
+def dump_outputs(out_dir, last, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays the last timed ply handed to its caller, as float32 .npy files in out_dir — the ply record of every board
+    (sz_fetch_ply: packed planes, root actions and visit counts, sampled move, game end) and the network's outputs of the ply's last search
+    iteration (value of every board, the policy of a fixed sample of DUMP_POLICY_ROWS boards).  Above `limit` bytes the per-board arrays keep a
+    fixed, seeded subset of boards (board_index says which); the same arguments give the same boards, so two builds compare file for file."""
+    rec = last["rec"]
+    per_board = {k: np.asarray(v, dtype=np.float32) for k, v in rec.items()}
+    per_board["value"] = last["value"].float().reshape(-1).cpu().numpy()
+    B = len(per_board["value"])
+    policy = last["policy"].float().reshape(B, -1)
+    n_pol = min(B, DUMP_POLICY_ROWS)
+    row_bytes = sum(v[0].nbytes for v in per_board.values()) + 4
+    budget = limit - 4096                   # room for the .npy headers
+    n = min(B, max(1, (budget - n_pol * policy.shape[1] * 4 - n_pol * 4) // row_bytes))
+    n_pol = min(n_pol, n)
+    idx = np.arange(B) if n == B else np.sort(np.random.RandomState(0).choice(B, n, replace=False))
+    pol_idx = idx if n_pol == n else np.sort(np.random.RandomState(1).choice(idx, n_pol, replace=False))
+    arrays = {k: v[idx] for k, v in per_board.items()}
+    arrays["board_index"] = idx.astype(np.float32)
+    arrays["policy"] = policy[torch.as_tensor(pol_idx, device=policy.device)].cpu().numpy()
+    arrays["policy_board_index"] = pol_idx.astype(np.float32)
+    assert sum(v.nbytes for v in arrays.values()) <= limit
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` outside a launcher: start N ranks (one per GPU) before anything in this process has touched the GPU, relay their output
     (rank 0 prints the JSON line) and return their exit code.  The reference spawns its own workers the same way (train_RL.py:215-227)."""
@@ -326,10 +359,14 @@ def main():
     ap.add_argument("--no-train-step", action="store_true", help="skip the optimiser-step side sample (`train_step`)")
     ap.add_argument("--split-plies", type=int, default=3, help="timed plies of the `roofline_split` run (after one warm-up ply)")
     ap.add_argument("--no-kernel-events", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed ply returned (ply record, network outputs) as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
 
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.dump_outputs and a.steps < 1:
+        raise SystemExit("--dump-outputs needs --steps >= 1: it writes what the last timed step computed")
     if "RANK" not in os.environ and a.gpus > 1:
         sys.exit(self_launch(a.gpus, sys.argv[1:]))        # nothing above this line has touched the GPU
     rank = int(os.environ.get("RANK", "0"))
@@ -373,6 +410,7 @@ def main():
 
     ev_nn, ev_tree, conv_events = [], [], []
     use_events = not a.no_kernel_events
+    last = {}                               # what the latest ply handed back: its record and the network's last outputs
 
     def evaluate(planes):
         if fast:
@@ -402,6 +440,7 @@ def main():
                 eng.step(policy, value)
         eng.play(rng.random_sample(B))
         rec = eng.fetch_ply()               # the training record of this ply goes to the host like in sim.py:71-73
+        last.update(rec=rec, policy=policy, value=value)
         # finished games restart so that every board keeps working (steady-state self-play)
         over = rec["game_over"].astype(bool) & rec["active"].astype(bool)
         if over.any():
@@ -422,6 +461,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     st1 = eng.check_errors()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
 
     sims = st1["simulations"] - st0["simulations"]
     exps = st1["expansions"] - st0["expansions"]
