@@ -37,6 +37,15 @@ def _pack(w, cin_padded, ksize, device, w16=False, f16=False):
     return torch.from_numpy(out.view(np.int16)).to(device)
 
 
+def _check_f16_range(named, scale, what):
+    """f16 operands: refuse (ValueError) a network whose weights times `scale` do not fit f16 (|v| rounds to inf beyond 65504) instead of computing with inf"""
+    for name, w in named:
+        amax = float(w.detach().abs().max())
+        if not np.isfinite(amax) or amax * scale >= 65520.0:                  # f32 -> f16 rounds to inf from 65504 + half a quantum on
+            raise ValueError("%s: %s has a weight of magnitude %.4g; f16 operands%s hold at most 65504%s — use operands=\"bf16\""
+                             % (what, name, amax, " (weights packed times %g)" % scale if scale != 1 else "", " / %g" % scale if scale != 1 else ""))
+
+
 class FastPolicyNet:
     """operands: "bf16" (default) or "fp16" — the element type of the MFMA operands (weights and stored activations; accumulation, bias,
     residual add and the value MLP are f32 either way).  fp16 keeps 11 bits of mantissa instead of 8 at the same speed; it needs the
@@ -65,11 +74,17 @@ class FastPolicyNet:
         w, b = _fold_bn(model.conv1.weight, model.norm_layer)
         self.stem = (_pack_w(w, 128, 3, dev), b.to(dev).contiguous())
         self.blocks = []
-        for blk in model.resnet_blocks:
+        folded = [("conv1 (folded)", w)]
+        for k, blk in enumerate(model.resnet_blocks):
             w1, b1 = _fold_bn(blk.conv1.weight, blk.bn1)
             w2, b2 = _fold_bn(blk.conv2.weight, blk.bn2)
+            folded += [("resnet_blocks.%d.conv1 (folded)" % k, w1), ("resnet_blocks.%d.conv2 (folded)" % k, w2)]
+            if self.f16:
+                _check_f16_range(folded[-2:], 1, "FastPolicyNet")
             self.blocks.append((_pack_w(w1, 256, 3, dev), b1.to(dev).contiguous(), _pack_w(w2, 256, 3, dev), b2.to(dev).contiguous()))
         wp, bp = _fold_bn(model.conv_p1.weight, model.p_norm1)
+        if self.f16:
+            _check_f16_range(folded[:1] + [("conv_p1 (folded)", wp), ("conv_p2", model.conv_p2.weight)], 1, "FastPolicyNet")
         self.p1 = (_pack_w(wp, 256, 1, dev), bp.to(dev).contiguous())
         # heads (tiny): policy 1x1 256->73 (+bias), value 1x1 256->1 + BN + ReLU + MLP
         self.wp2 = model.conv_p2.weight.detach().view(73, 256).t().contiguous().to(dev).to(torch.bfloat16)      # [256,73]
@@ -272,6 +287,9 @@ class SplitPolicyNet:
         L = N.lib()
         stream = np.zeros(int(L.sz_nn_split_stream_elems(self.n_blocks)), dtype=np.uint16)
         wp1, bp1 = _fold_bn(model.conv_p1.weight, model.p_norm1)
+        if self.f16:                                     # the weights are packed times 2^10 (SP_WSCALE_LOG2) as hi + lo f16: |w| * 2^10 must stay finite in f16
+            _check_f16_range([("tower convolution %d (folded)" % k, w) for k, (w, _) in enumerate(convs)] + [("conv_p1 (folded)", wp1), ("conv_p2", model.conv_p2.weight)],
+                             1024.0, "SplitPolicyNet")
         for k, (w, b) in enumerate(convs + [(wp1, bp1)]):                  # conv_p1 (1x1) rides behind the tower in the stream: the heads are fused onto the tile
             wk = w.contiguous().cpu().float().numpy()
             assert wk.shape[0] == 256 and wk.shape[2] == wk.shape[3] == (1 if k == len(convs) else 3)

@@ -17,8 +17,10 @@ MIOpen's fp32 kernels take 90-105 us (forward), 216 us (backward) per convolutio
 
 `train_rl.train` switches it on by default for an fp32 model on a GPU (`split_convs=False` / `--train-convs torch`: MIOpen).  Measured at batch 128
 (tools/trainconv_probe.py, profiles/r03zze_trainconv_probe.txt, r03zzr_train_loop_same_box_ab_counters.txt): optimiser step 12.9 -> 6.8-7.3 ms; forward / input gradient / weight gradient of one convolution
-5.0e-7 / 5.1e-7 / 2.7e-7 relative L2 from fp64 (torch fp32: 4.9e-7 / 5.1e-7 / 2.5e-7), also on inputs scaled by 1e3 or 1e-6; whole-network gradient 3.8e-3 from an fp64
-step (3.45e-3 with torch's BatchNorm launches; MIOpen's fp32 step: 3.37e-3; the 39 train-mode BatchNorms amplify every rounding).  OPERANDS_F16 = False selects hi + lo bf16 operands for forward / backward-data
+5.0e-7 / 5.1e-7 / 2.7e-7 relative L2 from fp64 (torch fp32: 4.9e-7 / 5.1e-7 / 2.5e-7), also on inputs scaled by 1e3 or 1e-6.  Whole-network gradient against an fp64
+step: dominated by ReLU branch flips (an input within rounding of zero takes the other branch; the 39 train-mode BatchNorms carry that everywhere), so it
+ranges over 1e-6 .. 5e-3 for ANY fp32 implementation (MIOpen's step included) depending on which inputs flip; with the device's ReLU masks given to both
+steps, MIOpen's is ~1.3e-6 and this one ~2x that (tests/test_gpu_train_fp64.py).  OPERANDS_F16 = False selects hi + lo bf16 operands for forward / backward-data
 (16 bits: 4.5e-6 per convolution, gradient 1.1e-2) with torch's weight gradient; WGRAD_KERNEL = False keeps torch's weight gradient.
 """
 import contextlib
@@ -214,8 +216,22 @@ def _eligible(m):
             and m.stride == (1, 1) and m.dilation == (1, 1) and m.groups == 1 and m.bias is None)
 
 
+def check_weight_range(model):
+    """f16 operands pack the weights times 2^10 (SP_WSCALE_LOG2): a weight of magnitude >= 65520 / 2^10 (~64) would become inf.  Raises ValueError naming the
+    convolution.  Checked when the convolutions are switched on (one host read per convolution, once): a check inside every call would stall the step on a sync."""
+    if not OPERANDS_F16:
+        return
+    for name, m in model.named_modules():
+        if _eligible(m):
+            amax = float(m.weight.detach().abs().max())
+            if not amax * 1024.0 < 65520.0:
+                raise ValueError("split_convs: %s has a weight of magnitude %.4g; the f16 operands hold |w| * 2^10 <= 65504 — use split_convs=False (MIOpen)" % (name, amax))
+
+
 def enable_split_convs(model):
-    """every 3x3 256->256 convolution of `model` runs SplitConv3x3 on fp32 cuda inputs of 8x8 boards (anything else falls through to torch)"""
+    """every 3x3 256->256 convolution of `model` runs SplitConv3x3 on fp32 cuda inputs of 8x8 boards (anything else falls through to torch); ValueError when a
+    weight is outside what the f16 operands hold (check_weight_range)"""
+    check_weight_range(model)
     n = 0
     for m in model.modules():
         if _eligible(m) and not hasattr(m, "_sz_orig_forward"):

@@ -64,7 +64,8 @@ def test_split_precision_training_convolution_forward_and_backward():
     g = torch.Generator(device="cuda").manual_seed(5)
     w = (torch.randn(256, 256, 3, 3, device="cuda", generator=g) * 0.03).requires_grad_()
     rel = lambda a, b: float((a.double() - b.double()).norm() / b.double().norm())
-    for B in (1, 37, 300):
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    for B in sorted({1, 37, n_cu // 2, n_cu // 2 + 1, n_cu, 128, 300}):          # n/2: the last batch of the two-workgroups-per-board form; 128: train_rl's batch
         x = (torch.randn(B, 256, 8, 8, device="cuda", generator=g) * (torch.rand(B, 256, 8, 8, device="cuda", generator=g) < 0.5)).requires_grad_()
         gy = torch.randn(B, 256, 8, 8, device="cuda", generator=g)
         y64 = F.conv2d(x.double(), w.double(), padding=1)
@@ -98,8 +99,10 @@ def test_split_precision_training_convolution_forward_and_backward():
 
 def test_train_step_with_split_convolutions_matches_reference_loss_and_the_cpu_gradient(golden_dir):
     """the default train step on the device (train_rl.train enables trainconv's convolutions: hi + lo f16 operands, fp32's accuracy class): loss within 1e-4 of the
-    reference's golden values; the gradient of this 8-sample batch as close to the CPU's as MIOpen's fp32 path is (both ~2.7e-3: 39 train-mode BatchNorms over 8
-    samples amplify every rounding)"""
+    reference's golden values; the gradient of this 8-sample batch against the CPU's fp32 step — two fp32 evaluations, neither of them the reference: r_mi (MIOpen
+    vs CPU) < 5e-3 and r_sp (split + fused vs CPU) < 1.2e-2 bound the disagreement between fp32 implementations, not the error of either: both are dominated by
+    ReLU branch flips.  The distance from fp64 with the flips taken out is asserted in test_gpu_train_fp64.py::test_whole_train_step_against_an_fp64_step
+    (golden batch, masked: split + fused 2.75e-6, MIOpen 1.2e-6)."""
     from sigma_zero_amd.trainconv import split_convs
     from sigma_zero_amd import train_rl as T
     z = np.load(os.path.join(golden_dir, "train_loss_golden.npz"))
@@ -133,8 +136,9 @@ def test_train_step_with_split_convolutions_matches_reference_loss_and_the_cpu_g
         assert not any(hasattr(m, "_sz_orig_forward") for m in net.modules())
     assert len(hist[None]) == 3 and np.allclose(np.array(hist[None]), np.array(hist[False]), rtol=2e-3, atol=2e-3), (hist[None], hist[False])
     # two fp32 evaluations of this 8-sample step differ by a few 1e-3 whatever produces them (MIOpen vs the CPU: 2.6e-3; the matrix-core convolutions with torch's
-    # BatchNorm: 2.7e-3; with the fused BatchNorm + ReLU launches, each as close to fp64 as torch's own: 5.9e-3): against an fp64 step at batch 128 the three are at
-    # 3.4e-3 / 3.5e-3 / 3.8e-3 (tools/trainconv_probe.py)
+    # BatchNorm: 2.7e-3; with the fused BatchNorm + ReLU launches: 5.9e-3): these bounds measure fp32-vs-fp32 disagreement (39 train-mode BatchNorms over 8 samples
+    # amplify every branch flip).  Unmasked against an fp64 step: batch 8 split 5.2e-3, MIOpen 1.3e-6 .. 1.5e-3 between processes; batch 128 split 5.1e-3, MIOpen
+    # 4.2e-3 (test_gpu_train_fp64.py)
     assert r_sp < 1.2e-2 and r_mi < 5e-3
 
 

@@ -218,3 +218,20 @@ def test_optimiser_state_resume(tmp_path):
     train_rl.train(net2, dl, opt2, total_steps=0)
     for a, b in zip(net.parameters(), net2.parameters()):
         assert torch.equal(a, b)
+
+
+def test_split_convs_refuse_weights_beyond_the_f16_range():
+    """the train convolutions pack w * 2^10 into f16: a weight of 64 or more would become inf, so switching them on refuses such a model (ValueError) and leaves
+    its forwards untouched; weights just below the limit are accepted"""
+    from sigma_zero_amd.trainconv import enable_split_convs, disable_split_convs
+    torch.manual_seed(0)
+    net = sz.policyNN({})
+    with torch.no_grad():
+        net.resnet_blocks[3].conv2.weight[5, 7, 1, 1] = 63.9
+    assert enable_split_convs(net) == 38
+    disable_split_convs(net)
+    with torch.no_grad():
+        net.resnet_blocks[3].conv2.weight[5, 7, 1, 1] = -64.0
+    with pytest.raises(ValueError, match="resnet_blocks.3.conv2"):
+        enable_split_convs(net)
+    assert not any(hasattr(m, "_sz_orig_forward") for m in net.modules())

@@ -1,0 +1,115 @@
+"""tests/nnref.py — the fp64 emulation of FastPolicyNet's rounding points — held against policyNN, torch's conversions and the native weight packers (CPU only)."""
+import numpy as np
+import pytest
+import torch
+
+import sigma_zero_amd as sz
+from sigma_zero_amd.fastnet import _fold_bn, _pack
+
+from nnref import Emulated, folded_convs, round_to, trained_regime, truncated
+
+
+def _net(seed=0, regime=False):
+    torch.manual_seed(seed)
+    net = sz.policyNN({}).eval()
+    if regime:
+        trained_regime(net, seed, verbose=False)
+    else:
+        with torch.no_grad():
+            for m in net.modules():
+                if isinstance(m, torch.nn.BatchNorm2d):
+                    m.running_mean.normal_(0, 0.05); m.running_var.uniform_(0.5, 1.5); m.weight.uniform_(0.7, 1.3); m.bias.normal_(0, 0.05)
+    return net
+
+
+@pytest.mark.parametrize("regime", [False, True], ids=["benign", "trained"])
+def test_emulation_without_rounding_is_policynn_in_double(regime):
+    net = _net(1, regime)
+    g = torch.Generator().manual_seed(2)
+    x = (torch.rand(3, 119, 8, 8, generator=g) < 0.15).double()
+    x[2] = 0                                                                  # an all-zero board
+    net64 = truncated(net, 19).double()
+    with torch.no_grad():
+        p64, v64 = net64(x, inference=False)
+        y64 = net64.resnet_blocks(torch.relu(net64.norm_layer(net64.conv1(x))))
+        em = Emulated(net, None)
+        y = em.tower(x)
+        p, v = em.heads(y)
+        pi, _ = em(x, inference=True)
+    rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
+    assert rel(y, y64) < 1e-12 and rel(p, p64) < 1e-12 and float((v - v64).abs().max()) < 1e-12, (rel(y, y64), rel(p, p64))
+    assert float((pi - torch.softmax(p64, 1)).abs().max()) < 1e-12
+    # truncation: n_blocks = k is the network with resnet_blocks[:k]
+    t2 = truncated(net, 2).double()
+    with torch.no_grad():
+        assert rel(Emulated(net, None, n_blocks=2).tower(x), t2.resnet_blocks(torch.relu(t2.norm_layer(t2.conv1(x))))) < 1e-12
+
+
+@pytest.mark.parametrize("operands,dtype", [("bf16", torch.bfloat16), ("fp16", torch.float16)])
+def test_rounding_is_torch_conversion_bit_for_bit(operands, dtype):
+    """every f32 exponent, random mantissas, exact ties, subnormals of the target, the overflow boundary"""
+    rng = np.random.RandomState(0)
+    bits = rng.randint(0, 2 ** 31, size=400000).astype(np.uint32) | (rng.randint(0, 2, size=400000).astype(np.uint32) << 31)
+    x = torch.from_numpy(bits.view(np.float32).copy())
+    x = x[torch.isfinite(x)]
+    keep = 8 if operands == "bf16" else 11
+    ties = torch.from_numpy(((bits & ~np.uint32((1 << (24 - keep)) - 1)) | np.uint32(1 << (23 - keep))).view(np.float32).copy())          # exactly half a quantum above a value
+    ties = ties[torch.isfinite(ties)]
+    sub = torch.ldexp(torch.arange(-3000, 3000, dtype=torch.float32), torch.tensor(-26 if operands == "fp16" else -135))                     # around the target's subnormal range
+    fmax = torch.finfo(dtype).max
+    edge = torch.tensor([fmax, -fmax, np.nextafter(np.float32(fmax), np.float32(np.inf)), fmax * (1 + 2.0 ** -keep), fmax * (1 + 2.0 ** -keep) * (1 - 2.0 ** -23),
+                         fmax * (1 + 2.0 ** -keep) * (1 + 2.0 ** -23), 0.0, -0.0, 1.0, -1.0, 3e38, -3e38], dtype=torch.float32)
+    for v in (x, ties, sub, edge, x.double() * (1 + 2.0 ** -30)):          # the last: double inputs take the double -> f32 -> 16 bit path
+        got, ref = round_to(v, operands), v.float().to(dtype).double()
+        assert torch.equal(torch.isinf(got), torch.isinf(ref))
+        fin = torch.isfinite(ref)
+        assert torch.equal(got[fin], ref[fin]) and torch.equal(torch.signbit(got), torch.signbit(ref))
+
+
+def _unpack16(packed, cin_padded, ksize, cin):
+    """inverse of pack_weights16_impl (sz_nn.hip): out[t][ks][tile][l][j] with co = tile*16 + (l & 15), ci = ks*32 + 8*(l >> 4) + j -> [256, cin, k, k] uint16 bits"""
+    taps, ksteps = ksize * ksize, cin_padded // 32
+    a = packed.reshape(taps, ksteps, 16, 4, 16, 8)                           # t, ks, tile, l >> 4, l & 15, j
+    w = a.transpose(2, 4, 1, 3, 5, 0).reshape(256, cin_padded, taps)         # co = (tile, l & 15), ci = (ks, l >> 4, j)
+    return w[:, :cin].reshape(256, cin, ksize, ksize)
+
+
+def _bits(t, operands):
+    return t.float().to(torch.bfloat16 if operands == "bf16" else torch.float16).view(torch.int16).numpy().view(np.uint16)
+
+
+@pytest.mark.parametrize("operands", ["bf16", "fp16"])
+@pytest.mark.parametrize("regime", [False, True], ids=["benign", "trained"])
+def test_folded_weights_are_what_the_packers_store(operands, regime):
+    """all 39 tower convolutions and conv_p1, as FastPolicyNet packs them (fastnet._fold_bn + _pack -> sz_nn_pack_weights16[_f16]), unpacked from the MFMA
+    fragment order: the emulation's rounded weights bit for bit; the folded f32 biases equal too"""
+    net = _net(3, regime)
+    f16 = operands == "fp16"
+    em = Emulated(net, operands)
+    mods = [(net.conv1.weight, net.norm_layer)] + [p for blk in net.resnet_blocks for p in ((blk.conv1.weight, blk.bn1), (blk.conv2.weight, blk.bn2))]
+    mods.append((net.conv_p1.weight, net.p_norm1))
+    mine = folded_convs(net, operands) + [em.p1]
+    assert len(mods) == 40
+    for k, ((cw, bn), (w_em, b_em)) in enumerate(zip(mods, mine)):
+        w, b = _fold_bn(cw, bn)
+        ksize, cin = cw.shape[2], cw.shape[1]
+        cin_padded = 128 if cin == 119 else 256
+        packed = _pack(w, cin_padded, ksize, "cpu", w16=True, f16=f16).numpy().view(np.uint16)
+        assert np.array_equal(_unpack16(packed, cin_padded, ksize, cin), _bits(w_em, operands)), k
+        assert not _unpack16(packed, cin_padded, ksize, cin_padded)[:, cin:].any()            # the stem's padding channels 119..127 are zero
+        assert torch.equal(b.double(), b_em), k
+    if regime:
+        assert float(mine[0][0].abs().max()) > 50                           # the stem channels on the rare planes really are O(100)
+
+
+def test_trained_regime_is_what_it_says():
+    net = _net(4, regime=True)
+    bns = [m for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d) and m.num_features == 256]
+    gamma = torch.cat([m.weight.detach() for m in bns])
+    var = torch.cat([m.running_var.detach() for m in bns])
+    beta = torch.cat([m.bias.detach() for m in bns])
+    assert float((gamma == 0).float().mean()) > 0.02 and float((gamma < 0).float().mean()) > 0.05 and float(gamma.abs().max()) > 2
+    assert float(var.min()) < 2e-3 and float(var.max()) > 5 and float(beta.min()) < -4
+    from nnref import report
+    xmax = report(net)
+    assert 30 < xmax < 3000, xmax                                             # the residual stream is O(100) after block 19
