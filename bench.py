@@ -11,13 +11,16 @@ Workload at N=1 (BASELINE.json configs[2], the configuration the metric is quote
 classical-chess boards per GPU, num_searches=800, bf16 policy/value network with seeded random-init weights.
 Boards are independent, so with N ranks each rank owns 4096 boards (weak scaling, no data-path collective).
 
-One JSON line is printed by rank 0.  Extra objects:
+One JSON line is printed by rank 0.  A plain run does only what that line's headline needs: set-up, warm-up plies, timed plies,
+--dump-outputs, the line.  Extra objects, read off HIP events recorded in the timed plies themselves:
   roofline      the dominant kernel of the job (97.7 % of GPU time): k_tower16_bf16, the whole policy/value tower in one persistent
                 MFMA launch — algorithmic FLOP per launch / mean launch duration measured with HIP events on the launch stream over
                 the timed region, against the 2.5 PFLOP/s dense bf16 peak; `traffic` = HBM bytes per launch from the committed
                 rocprofv3 --pmc passes (profiles/pmc_tower_latest.json)
   roofline_tree the hand-written tree kernel (k_search_step), HBM roofline: algorithmic bytes per launch / mean launch duration
   roofline_nn   the whole network forward (tower + heads): 2.915 GFLOP x boards / mean forward duration
+`--full` adds, after the timed plies, the side measurements that take runs of their own (N=1; `--no-split`, `--no-parity-config`, `--no-train-step`,
+`--no-cpu-baseline` leave single ones out):
   roofline_split the same workload with the network at the REFERENCE's precision class on the matrix cores (SplitPolicyNet / k_tower_split: hi + lo
                 bf16 operands, 3 MFMAs per product — the configuration that meets north_star's 1e-4 on visit policies): 1 warm-up + 3 timed plies,
                 simulations/s, launch duration of k_tower_split by HIP events, algorithmic AND issued MFMA fraction of the 2.5 PFLOP/s peak (N=1 only)
@@ -25,10 +28,10 @@ One JSON line is printed by rank 0.  Extra objects:
   parity_config simulations/s of the same boards-per-GPU with the fp32 network the reference uses (bounded sample, N=1 only)
   train_step    the optimiser step of the same loop (train_RL.py:103-122, batch 128, synthetic batches): ms per step with the matrix-core convolutions + fused
                 BatchNorm (train_rl.train's default) and with torch / MIOpen fp32 beside it (a few seconds, N=1 only)
-`--gpus N` with N > 1 outside a launcher (no RANK in the environment) starts N ranks itself (torch.distributed.run on 127.0.0.1) before any GPU call,
-as the reference spawns its own self-play workers (train_RL.py:215-227); under a launcher WORLD_SIZE must equal --gpus.
   cpu_baseline  the oracle (reference algorithm restated on the CPU: one leaf per step, per-game pointer tree,
                 batch-1 fp32 forward on the host cores) on BASELINE.json configs[0], timed on rank 0 over a bounded sample
+`--gpus N` with N > 1 outside a launcher (no RANK in the environment) starts N ranks itself (torch.distributed.run on 127.0.0.1) before any GPU call,
+as the reference spawns its own self-play workers (train_RL.py:215-227); under a launcher WORLD_SIZE must equal --gpus.
 `--dump-outputs DIR` writes, after the timed steps, what the last timed ply returned (ply record + network outputs, float32 .npy, <= 64 MB) for
 output-for-output comparison of two builds; weights, start positions and sampling draws are seeded, so the same arguments give the same inputs.
 """
@@ -336,7 +339,7 @@ def self_launch(n, argv):
     return subprocess.run(cmd).returncode
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -353,15 +356,22 @@ def main():
     ap.add_argument("--planes", default="bits128", choices=["bits128", "nhwc128"],
                     help="network-input image written by the tree kernel on the fast path: bit-packed (1 KiB/board) or bf16 NHWC (16 KiB/board)")
     ap.add_argument("--edges-per-board", type=int, default=0, help="child slots per board (0 = engine default: worst case when it fits in half of the free HBM)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-config", action="store_true", help="skip the fp32-network sample (`parity_config`)")
-    ap.add_argument("--no-split", action="store_true", help="skip the reference-precision run on the matrix cores (`roofline_split`)")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the optimiser-step side sample (`train_step`)")
-    ap.add_argument("--split-plies", type=int, default=3, help="timed plies of the `roofline_split` run (after one warm-up ply)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements that take runs of their own (N=1): `roofline_split`, `fp16_config`, "
+                         "`parity_config`, `train_step`, `cpu_baseline`; a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle's CPU sample (`cpu_baseline`)")
+    ap.add_argument("--no-parity-config", action="store_true", help="with --full: skip the fp32-network sample (`parity_config`)")
+    ap.add_argument("--no-split", action="store_true", help="with --full: skip the reference-precision run on the matrix cores (`roofline_split`) and the f16 ply (`fp16_config`)")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the optimiser-step side sample (`train_step`)")
+    ap.add_argument("--split-plies", type=int, default=3, help="with --full: timed plies of the `roofline_split` run (after one warm-up ply)")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed ply returned (ply record, network outputs) as DIR/<name>.npy (rank 0)")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    a = parse_args()
 
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -555,34 +565,35 @@ def main():
             else:
                 out["roofline"] = tree_roof
                 out["roofline_nn"] = nn_roof
-        # the two side measurements must never cost the headline line: a failure is reported in their place
         if world == 1 and fast:
             eng.close()
-        if not a.no_split and world == 1 and fast and not split:
-            try:
-                out["roofline_split"] = split_sample(dev, B, S, a.chess960, plies=a.split_plies)
-            except Exception as ex:                     # noqa: BLE001
-                out["roofline_split"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
-        if not a.no_split and world == 1 and fast and not split and a.operands == "bf16":
-            try:
-                out["fp16_config"] = fp16_sample(dev, B, S, a.chess960)
-            except Exception as ex:                     # noqa: BLE001
-                out["fp16_config"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
-        if not a.no_parity_config and world == 1 and fast:
-            try:
-                out["parity_config"] = parity_config_sample(dev, B, a.chess960)
-            except Exception as ex:                     # noqa: BLE001
-                out["parity_config"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
-        if not a.no_train_step and world == 1 and fast:
-            try:
-                out["train_step"] = train_step_sample(dev)
-            except Exception as ex:                     # noqa: BLE001
-                out["train_step"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
-        if not a.no_cpu_baseline and world == 1:      # rank 0 at N=1 only (bounded ~15 s sample)
-            try:
-                out["cpu_baseline"] = cpu_baseline()
-            except Exception as ex:                     # noqa: BLE001
-                out["cpu_baseline"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
+        if a.full:
+            # --full: the side measurements must never cost the headline line: a failure is reported in their place
+            if not a.no_split and world == 1 and fast and not split:
+                try:
+                    out["roofline_split"] = split_sample(dev, B, S, a.chess960, plies=a.split_plies)
+                except Exception as ex:                     # noqa: BLE001
+                    out["roofline_split"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
+            if not a.no_split and world == 1 and fast and not split and a.operands == "bf16":
+                try:
+                    out["fp16_config"] = fp16_sample(dev, B, S, a.chess960)
+                except Exception as ex:                     # noqa: BLE001
+                    out["fp16_config"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
+            if not a.no_parity_config and world == 1 and fast:
+                try:
+                    out["parity_config"] = parity_config_sample(dev, B, a.chess960)
+                except Exception as ex:                     # noqa: BLE001
+                    out["parity_config"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
+            if not a.no_train_step and world == 1 and fast:
+                try:
+                    out["train_step"] = train_step_sample(dev)
+                except Exception as ex:                     # noqa: BLE001
+                    out["train_step"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
+            if not a.no_cpu_baseline and world == 1:      # rank 0 at N=1 only (bounded ~15 s sample)
+                try:
+                    out["cpu_baseline"] = cpu_baseline()
+                except Exception as ex:                     # noqa: BLE001
+                    out["cpu_baseline"] = {"value": None, "error": "%s: %s" % (type(ex).__name__, ex)}
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -70,3 +70,11 @@ def test_dump_outputs_writes_float32_within_the_budget(tmp_path):
     pol = z["policy_board_index"].astype(np.int64)
     assert set(pol.tolist()) <= set(idx.tolist()) and np.array_equal(z["policy"], big["policy"].numpy()[pol])
     assert all(np.array_equal(z[k], z2[k]) for k in z)
+
+
+def test_side_measurements_wait_for_full():
+    """a plain run measures the headline only; the side measurements that take runs of their own are asked for with --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "2", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full"]).full is True

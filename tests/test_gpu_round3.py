@@ -1,5 +1,5 @@
 """Round-3 GPU tests: the RL train step on the device against the reference's golden loss and the CPU step,
-BASELINE configs[1] (512 boards x 100 searches, bf16 MFMA network), and bench.py's own multi-rank launch."""
+BASELINE configs[1] (512 boards x 100 searches, bf16 MFMA network), bench.py's own multi-rank launch and what its plain and --full runs print."""
 import json
 import os
 import random
@@ -344,3 +344,22 @@ def test_bench_gpus_2_launches_two_ranks_itself():
     assert line["n_gpus"] == 2 and line["sim_count_ok"] is True
     assert line["config"]["boards_per_gpu"] == 256 and line["value"] > 0
     assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 2 * 256 * 20) < 1.0               # whole-job aggregate: both ranks' simulations over the slowest rank's time
+
+
+def test_bench_plain_run_is_the_headline_and_full_adds_the_side_measurements():
+    """A plain `python bench.py --gpus 1` prints the headline (with the rooflines read off its own timed plies) and runs nothing else;
+    `--full` adds the side measurements that take runs of their own, each with a value"""
+    side = ("roofline_split", "fp16_config", "parity_config", "train_step", "cpu_baseline")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    # 32 searches: the tower's launch events are sampled at search iteration 25
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--boards", "256", "--searches", "32", "--steps", "1", "--warmup", "1"]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    plain = _bench_line(r.stdout)
+    assert plain["sim_count_ok"] is True and plain["value"] > 0 and plain["roofline"]["launch_ms"] > 0
+    assert not [k for k in side if k in plain]
+    r = subprocess.run(cmd + ["--full", "--split-plies", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    full = _bench_line(r.stdout)
+    assert full["sim_count_ok"] is True and full["value"] > 0
+    assert all(full[k]["value"] is not None for k in side), {k: full.get(k) for k in side}
