@@ -146,6 +146,25 @@ int sz_fetch_ply(sz_engine* e, uint8_t* packed_planes, int32_t* action, int32_t*
  * with reuse_subtree: a reused root is never expanded again, the noise would silently reach the first ply of a game only. */
 int sz_set_root_noise(sz_engine* e, const float* gamma_dev);
 
+/* NON-REFERENCE option (default L = 1, lambda ignored): gather up to `leaves_per_step` leaves per board per
+ * sz_search_step with virtual loss `virtual_loss`; network rows become n_rows * leaves_per_step, board b's
+ * leaf i at row slot(b)*leaves_per_step + i.  Only between searches (SZ_ERR_STATE otherwise).
+ * Per board and step: every leaf pending from the previous step is expanded and backed up in gather order; then descents
+ * are made one after another until L leaves are pending or simulations done + pending == num_searches.  Every edge carries
+ * an in-flight count k (kept apart from W / N); selection scores a child with visit count N + k and value sum W + lambda*k
+ * (f64) under the parent term sqrt(N_parent + k_parent), otherwise exactly Node.get_ucb / Node.select.  A terminal leaf is
+ * backed up on the spot; a new non-terminal leaf becomes pending (k + 1 along its path, network input at its row); a descent
+ * that ends on a leaf already pending in this step (a collision) ends the gather.  A search takes at most num_searches steps
+ * and counts the same simulations as at L = 1.  L = 1 is the reference's search, bit for bit (the same kernel).  L > 1 is NOT
+ * the reference's search and is not held to its visit counts; its effect on playing strength is unmeasured.
+ * SZ_ERR_INVALID: L < 1, L > SZ_MAX_LEAVES_PER_STEP, lambda negative or not finite, or L > 1 on an engine with reuse_subtree.
+ * The buffers (in-flight counts, L paths and legal masks per board) are allocated by the first call with L > 1. */
+#define SZ_MAX_LEAVES_PER_STEP 256
+int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream);
+/* number of boards still waiting for a network evaluation (synchronises the stream).  With leaf batching a search takes a
+ * data-dependent number of steps (collisions end a gather early): step until this is 0. */
+int sz_pending_boards(sz_engine* e, int32_t* n_out, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

@@ -13,6 +13,7 @@ SZ_NN_IN_BITS = 0x1000000
 SZ_NN_SPLIT_WGB1, SZ_NN_SPLIT_WGB2 = 0x2000000, 0x4000000
 SZ_NN_F16 = 0x8000000
 SZ_NN_TOWER_WGB1, SZ_NN_TOWER_WGB2 = 0x10000000, 0x20000000
+SZ_MAX_LEAVES_PER_STEP = 256
 
 
 class sz_config(C.Structure):
@@ -44,6 +45,8 @@ EXPORTS = {
     "sz_compact": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_search_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "sz_search_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sz_set_leaf_batching": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
+    "sz_pending_boards": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_get_stats": (C.c_int, [C.c_void_p, C.POINTER(sz_stats), C.c_void_p]),
     "sz_root_children": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]),
     "sz_play": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -19,15 +19,16 @@ def play_match(model_a, model_b, args, n_games, chess960=False, scharnagl=None, 
     eng.new_games(scharnagl if chess960 else [-1] * n_games)
     a_is_white = (np.arange(n_games) % 2 == 0)
     results = np.full(n_games, 2, dtype=np.int8)            # +1 white won, -1 black won, 0 draw, 2 unfinished
-    idx_dev = torch.arange(n_games, device=eng.device)
+    L = eng.L                                               # args["leaves_per_step"]: board b's leaves are network rows b*L .. b*L+L-1
+    idx_dev = torch.arange(n_games * L, device=eng.device)
     for ply in range(max_plies):
         white_to_move = (ply % 2 == 0)                      # all games start together: one side to move per ply
-        a_moves = torch.as_tensor(a_is_white == white_to_move, device=eng.device)
+        a_moves = torch.as_tensor(np.repeat(a_is_white == white_to_move, L), device=eng.device)
         ia, ib = idx_dev[a_moves], idx_dev[~a_moves]
 
         def evaluator(planes):
-            policy = torch.empty(n_games, 4672, dtype=torch.float32, device=eng.device)
-            value = torch.empty(n_games, dtype=torch.float32, device=eng.device)
+            policy = torch.empty(n_games * L, 4672, dtype=torch.float32, device=eng.device)
+            value = torch.empty(n_games * L, dtype=torch.float32, device=eng.device)
             for model, ii in ((model_a, ia), (model_b, ib)):
                 if ii.numel():
                     p, v = model(planes[ii].contiguous(), inference=True)

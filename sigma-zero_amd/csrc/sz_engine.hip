@@ -28,6 +28,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <cmath>
 #include <vector>
 #include "sz_chess.h"
 #include "../../include/sigmazero.h"
@@ -44,8 +45,8 @@ struct alignas(16) Ctl {
     int status, n_nodes, n_edges, sims_done;
     int pend_node, pend_depth, game_ply, err;
     unsigned long long n_expand, n_term, sum_depth, sum_k;
-    int max_edges, game_result, reuse_ready, pad1;      // reuse_ready: the store holds the subtree of the move just played (sz_config.reuse_subtree)
-};
+    int max_edges, game_result, reuse_ready, n_pend;    // reuse_ready: the store holds the subtree of the move just played (sz_config.reuse_subtree)
+};                                                      // n_pend: leaves waiting for the network (sz_set_leaf_batching only)
 
 struct View {
     int B, S, n_cap, e_cap, p_cap, learning, chess960, planes_dtype;
@@ -62,6 +63,16 @@ struct View {
 };
 
 #define PMASK_STRIDE 80     // u64 words per board (73 used)
+
+// NON-REFERENCE option (sz_set_leaf_batching): up to L leaves per board per step, steered apart by a virtual loss `lam` per descent in
+// flight.  The in-flight count k of an edge is kept apart from W / N (W + lam - lam is not exact in f64).  Allocated on first use only.
+struct Batch {
+    int L; float lam;
+    int* vk;        // [B][e_cap] descents in flight through each edge; zeroed as edges are created (the root edge at search begin)
+    int* path;      // [B][L][p_cap] descent path of pending leaf i (path[0] = root edge)
+    u64* mask;      // [B][L][PMASK_STRIDE] its legal-move mask
+    int* depth;     // [B][L] its depth
+};
 #define LDS_HIST_WORDS 64   // 8 history slots x 8 words
 #define LDS_MASK_WORDS 80
 
@@ -116,6 +127,25 @@ __device__ __forceinline__ int wave_select_child(const EdgeStat* ch, int n, int 
         EdgeStat s = ch[c];
         float u = ucb_value(s.N, s.W, s.P, sq, c_puct);
         if (ucb_out) ucb_out[c] = u;
+        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+    }
+    return uni(bi);
+}
+
+// the same with virtual loss (sz_set_leaf_batching): child c scores as if its k[c] descents in flight had each returned a loss for the
+// parent, vc = N + k, wsum = W + lam*k (f64); parentVC = N + k of the parent.  k == 0 everywhere gives wave_select_child exactly.
+__device__ __forceinline__ int wave_select_child_vl(const EdgeStat* ch, const int* k, int n, int parentVC, float c_puct, float lam) {
+    const int lane = lane_id();
+    const float sq = (float)sqrt((double)parentVC);
+    float best = 0.f; int bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) {
+        EdgeStat s = ch[c];
+        const int kc = k[c];
+        float u = ucb_value(s.N + kc, s.W + (double)lam * (double)kc, s.P, sq, c_puct);
         if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
     }
     for (int off = 32; off >= 1; off >>= 1) {
@@ -392,7 +422,9 @@ __global__ void k_after_upload(View v, int b, int ply) {
 // ------------------------------------------------------------------------------------------------
 // kernel: search begin — create roots (mcts.py:43-46), root movegen + terminal test, encode root planes
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_search_begin(View v, void* planes) {
+// VL: leaf batching on (sz_set_leaf_batching): the root is pending leaf 0, its network input goes to row slot(b)*L
+template <bool VL>
+__global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb) {
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -445,31 +477,44 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes) {
             bp.es[0].W = tv * (double)S; bp.es[0].N = 1 + S;
             Ctl* c = bp.ctl; c->status = st | ST_DONE; c->n_nodes = 1; c->n_edges = 1; c->sims_done = S;
             c->n_term += (unsigned long long)S; c->pend_node = -1; c->pend_depth = 0;
+            if constexpr (VL) c->n_pend = 0;
         }
         return;
     }
     int n_legal, ep_legal; u64 checkers;
     wave_movegen(X, v.chess960, mask, n_legal, ep_legal, checkers);
     __syncthreads();
-    for (int i = lane; i < SZ_MASK_WORDS; i += 64) bp.pmask[i] = mask[i];
+    u64* pm = VL ? vb.mask + (size_t)b * vb.L * PMASK_STRIDE : bp.pmask;
+    for (int i = lane; i < SZ_MASK_WORDS; i += 64) pm[i] = mask[i];
     wave_load_history(bp, path, 0, root_ply, X, hist);
     __syncthreads();
     const int row = v.slot ? uni(v.slot[b]) : b;              // network batch row of this board (compacted batches: live boards first)
-    wave_encode(hist, X, (planes && row >= 0) ? (char*)planes + (size_t)row * planes_board_bytes(v.planes_dtype) : nullptr, v.planes_dtype,
+    const size_t row0 = (size_t)row * (VL ? vb.L : 1);       // batched: its leaf i sits at row slot(b)*L + i
+    wave_encode(hist, X, (planes && row >= 0) ? (char*)planes + row0 * planes_board_bytes(v.planes_dtype) : nullptr, v.planes_dtype,
                 v.rec_planes ? v.rec_planes + (size_t)b * SZ_NUM_PLANES * 8 : nullptr);
     if (lane == 0) {
         Ctl* c = bp.ctl;
         c->status = st | ST_PENDING; c->n_nodes = 1; c->n_edges = 1; c->sims_done = 0; c->pend_node = 0; c->pend_depth = 0;
         if (v.rec_colour) v.rec_colour[b] = (uint8_t)szm_turn(X.meta);
+        if constexpr (VL) {
+            const size_t li = (size_t)b * vb.L;
+            c->n_pend = 1; vb.depth[li] = 0; vb.path[li * v.p_cap] = 0;
+            vb.vk[(size_t)b * v.e_cap] = 1;                     // the root's own evaluation is in flight
+        }
     }
 }
+
 
 // ------------------------------------------------------------------------------------------------
 // kernel: one lock-step iteration (expand + backprop of the evaluated leaf, then select / move /
 // terminal test / encode of the next one)
 // ------------------------------------------------------------------------------------------------
 #define STEP_STAMP(k) do { if (v.dbg) { unsigned long long _t = __builtin_amdgcn_s_memtime(); if (lane_id() == 0) v.dbg[(size_t)blockIdx.x * 8 + (k)] = _t; } } while (0)
-__global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes) {
+// VL = false: the reference's search, one leaf per board per step.  VL = true (sz_set_leaf_batching): every pending leaf is expanded and
+// backed up in gather order (its k taken back along its path), then descents with virtual loss gather up to L new leaves; a terminal leaf
+// is backed up on the spot, a descent that ends on a leaf already pending in this step (a collision) ends the gather.
+template <bool VL>
+__global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb) {
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -486,119 +531,137 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     STEP_STAMP(0);
 
     if (status & ST_PENDING) {
-        // ---- mcts.py:77-109 for the leaf evaluated by the network -------------------------------
-        const int d = uni(bp.ctl->pend_depth), node = uni(bp.ctl->pend_node);
-        for (int j = lane; j <= d; j += 64) path[j] = bp.gpath[j];
-        for (int i = lane; i < SZ_MASK_WORDS; i += 64) mask[i] = bp.pmask[i];
+      const int n_leaves = VL ? uni(bp.ctl->n_pend) : 1;
+      for (int li = 0;;) {                                              // VL = false: one pass, no loop
+        // ---- mcts.py:77-109 for the leaf evaluated by the network (batched: every pending leaf, in gather order) -------------------
+        const int d = VL ? uni(vb.depth[(size_t)b * vb.L + li]) : uni(bp.ctl->pend_depth), node = VL ? 0 : uni(bp.ctl->pend_node);
+        const int* gpath = VL ? vb.path + ((size_t)b * vb.L + li) * v.p_cap : bp.gpath;
+        const u64* gmask = VL ? vb.mask + ((size_t)b * vb.L + li) * PMASK_STRIDE : bp.pmask;
+        const int prow = VL ? row * vb.L + li : row;                        // network batch row of this leaf
+        for (int j = lane; j <= d; j += 64) path[j] = gpath[j];
+        for (int i = lane; i < SZ_MASK_WORDS; i += 64) mask[i] = gmask[i];
         __syncthreads();
-        const float* pol = policy + (size_t)row * SZ_NUM_ACTIONS;
-        // masked sum in the fixed order: per-lane partial over planes ascending, then xor butterfly.
-        // Only planes that hold a legal move are fetched (~20 of 73), and in groups of 16 INDEPENDENT loads: a load-wait-add chain per
-        // plane cost one full memory latency each, and fetching all 73 planes made the kernel bandwidth-bound at 4096 boards.  The
-        // value and action of every legal move are stashed in LDS in ascending action order, so the second half works on the K <= 218
-        // children directly (lane = child: coalesced child records) instead of walking the planes again.
-        const int path_alloc = v.p_cap > 256 ? v.p_cap : 256;
-        float* sval = (float*)(path + path_alloc);                          // [<= 218] policy value of legal move c
-        unsigned short* sact = (unsigned short*)(sval + 220);               // [<= 218] its action index
-        u64 ne0 = __ballot(mask[lane] != 0);                                // planes 0..63 with at least one legal move
-        u64 ne1 = __ballot(lane < SZ_MASK_WORDS - 64 && mask[64 + (lane < SZ_MASK_WORDS - 64 ? lane : 0)] != 0);   // planes 64..72
-        constexpr int PCH = 16;
-        float acc = 0.0f;
-        int n_moves = 0;
-        while (ne0 | ne1) {
-            int pls[PCH];
-#pragma unroll
-            for (int k = 0; k < PCH; k++) {                                  // next PCH non-empty planes, ascending (uniform)
-                int pl = -1;
-                if (ne0) { pl = __builtin_ctzll(ne0); ne0 &= ne0 - 1; }
-                else if (ne1) { pl = 64 + __builtin_ctzll(ne1); ne1 &= ne1 - 1; }
-                pls[k] = pl;
-            }
-            float pv[PCH];
-#pragma unroll
-            for (int k = 0; k < PCH; k++) pv[k] = pol[(pls[k] >= 0 ? pls[k] : 0) * 64 + lane];     // issued back to back; plane 0 stands in for "none"
-#pragma unroll
-            for (int k = 0; k < PCH; k++) {
-                const int pl = pls[k];
-                if (pl >= 0) {                                               // uniform
-                    const bool mine = (mask[pl] >> lane) & 1;
-                    if (mine) acc = acc + pv[k];
-                    const u64 mm = __ballot(mine);
-                    if (mine) {
-                        const int r = n_moves + __popcll(mm & ((1ULL << lane) - 1));
-                        sval[r] = pv[k];
-                        sact[r] = (unsigned short)(pl * 64 + lane);
+        const float* pol = policy + (size_t)prow * SZ_NUM_ACTIONS;
+            // masked sum in the fixed order: per-lane partial over planes ascending, then xor butterfly.
+            // Only planes that hold a legal move are fetched (~20 of 73), and in groups of 16 INDEPENDENT loads: a load-wait-add chain per
+            // plane cost one full memory latency each, and fetching all 73 planes made the kernel bandwidth-bound at 4096 boards.  The
+            // value and action of every legal move are stashed in LDS in ascending action order, so the second half works on the K <= 218
+            // children directly (lane = child: coalesced child records) instead of walking the planes again.
+            const int path_alloc = v.p_cap > 256 ? v.p_cap : 256;
+            float* sval = (float*)(path + path_alloc);                          // [<= 218] policy value of legal move c
+            unsigned short* sact = (unsigned short*)(sval + 220);               // [<= 218] its action index
+            u64 ne0 = __ballot(mask[lane] != 0);                                // planes 0..63 with at least one legal move
+            u64 ne1 = __ballot(lane < SZ_MASK_WORDS - 64 && mask[64 + (lane < SZ_MASK_WORDS - 64 ? lane : 0)] != 0);   // planes 64..72
+            constexpr int PCH = 16;
+            float acc = 0.0f;
+            int n_moves = 0;
+            while (ne0 | ne1) {
+                int pls[PCH];
+    #pragma unroll
+                for (int k = 0; k < PCH; k++) {                                  // next PCH non-empty planes, ascending (uniform)
+                    int pl = -1;
+                    if (ne0) { pl = __builtin_ctzll(ne0); ne0 &= ne0 - 1; }
+                    else if (ne1) { pl = 64 + __builtin_ctzll(ne1); ne1 &= ne1 - 1; }
+                    pls[k] = pl;
+                }
+                float pv[PCH];
+    #pragma unroll
+                for (int k = 0; k < PCH; k++) pv[k] = pol[(pls[k] >= 0 ? pls[k] : 0) * 64 + lane];     // issued back to back; plane 0 stands in for "none"
+    #pragma unroll
+                for (int k = 0; k < PCH; k++) {
+                    const int pl = pls[k];
+                    if (pl >= 0) {                                               // uniform
+                        const bool mine = (mask[pl] >> lane) & 1;
+                        if (mine) acc = acc + pv[k];
+                        const u64 mm = __ballot(mine);
+                        if (mine) {
+                            const int r = n_moves + __popcll(mm & ((1ULL << lane) - 1));
+                            sval[r] = pv[k];
+                            sact[r] = (unsigned short)(pl * 64 + lane);
+                        }
+                        n_moves += __popcll(mm);
                     }
-                    n_moves += __popcll(mm);
                 }
             }
-        }
-        const float total = wave_sum_butterfly(acc);
-        __syncthreads();                                                     // one wave per workgroup: makes the LDS stash visible
-        const int first = n_edges;
-        int kept = 0;
-        const int leaf_edge = path[d];
-        for (int base = 0; base < n_moves; base += 64) {
-            const int c = base + lane;
-            const bool mine = c < n_moves;
-            float p = 0.0f;
-            if (mine) p = sval[c] / total;                                  // policy /= torch.sum(policy)
-            const bool keep = mine && !(p == 0.0f);                         // policy.nonzero() (NaN stays)
-            const u64 km = __ballot(keep);
-            if (keep) {
-                if (v.learning && !v.root_gamma) p = (0.75f * p) + (0.25f * v.noise);   // (1-eps)*probs + eps*noise
-                const int slot = first + kept + __popcll(km & ((1ULL << lane) - 1));
-                if (slot < v.e_cap) {
-                    EdgeStat s; s.W = 0.0; s.N = 0; s.P = p;
-                    bp.es[slot] = s;
-                    EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = sact[c]; m.term = 0; m.tval = 0; m.pad = 0;
-                    bp.em[slot] = m;
+            const float total = wave_sum_butterfly(acc);
+            __syncthreads();                                                     // one wave per workgroup: makes the LDS stash visible
+            const int first = n_edges;
+            int kept = 0;
+            const int leaf_edge = path[d];
+            for (int base = 0; base < n_moves; base += 64) {
+                const int c = base + lane;
+                const bool mine = c < n_moves;
+                float p = 0.0f;
+                if (mine) p = sval[c] / total;                                  // policy /= torch.sum(policy)
+                const bool keep = mine && !(p == 0.0f);                         // policy.nonzero() (NaN stays)
+                const u64 km = __ballot(keep);
+                if (keep) {
+                    if (v.learning && !v.root_gamma) p = (0.75f * p) + (0.25f * v.noise);   // (1-eps)*probs + eps*noise
+                    const int slot = first + kept + __popcll(km & ((1ULL << lane) - 1));
+                    if (slot < v.e_cap) {
+                        EdgeStat s; s.W = 0.0; s.N = 0; s.P = p;
+                        bp.es[slot] = s;
+                        if constexpr (VL) vb.vk[(size_t)b * v.e_cap + slot] = 0;
+                        EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = sact[c]; m.term = 0; m.tval = 0; m.pad = 0;
+                        bp.em[slot] = m;
+                    }
                 }
+                kept += __popcll(km);
             }
-            kept += __popcll(km);
+            if (first + kept > v.e_cap) { err = SZ_ERR_CAPACITY; kept = 0; }
+            if (v.learning && v.root_gamma && d == 0 && kept > 0) {
+                // non-reference option (sz_set_root_noise): AlphaZero's root-only noise.  The K Gamma(alpha,1) draws of this board,
+                // normalised over its K children, are one Dirichlet(alpha) sample of dimension K; inner nodes keep their priors.
+                const float* g = v.root_gamma + (size_t)b * SZ_MAX_MOVES;
+                __threadfence_block();                                      // the children were written by other lanes of this wave
+                float gs = 0.f;
+                for (int c = lane; c < kept; c += 64) gs = gs + g[c];
+                gs = wave_sum_butterfly(gs);
+                for (int c = lane; c < kept; c += 64) bp.es[first + c].P = (0.75f * bp.es[first + c].P) + (0.25f * (g[c] / gs));
+            }
+            if (lane == 0) { bp.em[leaf_edge].first = first; bp.em[leaf_edge].n = (unsigned short)kept; }
+            n_edges += kept;
+            (void)node;
+        const double val = (double)value[prow];                         // node.value = value.item()
+        if constexpr (VL) {                                             // its descent is no longer in flight
+            for (int j = lane; j <= d; j += 64) vb.vk[(size_t)b * v.e_cap + path[j]] -= 1;
         }
-        if (first + kept > v.e_cap) { err = SZ_ERR_CAPACITY; kept = 0; }
-        if (v.learning && v.root_gamma && d == 0 && kept > 0) {
-            // non-reference option (sz_set_root_noise): AlphaZero's root-only noise.  The K Gamma(alpha,1) draws of this board,
-            // normalised over its K children, are one Dirichlet(alpha) sample of dimension K; inner nodes keep their priors.
-            const float* g = v.root_gamma + (size_t)b * SZ_MAX_MOVES;
-            __threadfence_block();                                      // the children were written by other lanes of this wave
-            float gs = 0.f;
-            for (int c = lane; c < kept; c += 64) gs = gs + g[c];
-            gs = wave_sum_butterfly(gs);
-            for (int c = lane; c < kept; c += 64) bp.es[first + c].P = (0.75f * bp.es[first + c].P) + (0.25f * (g[c] / gs));
-        }
-        if (lane == 0) { bp.em[leaf_edge].first = first; bp.em[leaf_edge].n = (unsigned short)kept; }
-        n_edges += kept;
-        (void)node;
-        const double val = (double)value[row];                          // node.value = value.item()
         wave_backprop(bp.es, path, d, val);
         sims++; n_expand++; sum_depth += d; sum_k += kept;
+        if constexpr (!VL) break;
+        __syncthreads();                                                // path, mask and stash in LDS are reused by the next leaf
+        if (++li >= n_leaves) break;
+      }
         status &= ~ST_PENDING;
     }
     STEP_STAMP(1);
 
     // ---- next simulation(s): mcts.py:49-64 ------------------------------------------------------
-    while (sims < v.S && !err) {
+    int n_pend = 0;                                                     // batched: leaves gathered in this step
+    int* vk = VL ? vb.vk + (size_t)b * v.e_cap : nullptr;
+    while (sims + n_pend < v.S && (!VL || n_pend < vb.L) && !err) {
         int d = 0, cur = 0;
         path[0] = 0;
         EdgeMeta m = bp.em[0];
         int parentN = bp.es[0].N;
+        if constexpr (VL) parentN += vk[0];
         m.first = uni(m.first); int mn = uni((int)m.n); parentN = uni(parentN);
         while (mn > 0) {                                                // Node.select
-            int bi = wave_select_child(bp.es + m.first, mn, parentN, v.c_puct, nullptr);
+            int bi = VL ? wave_select_child_vl(bp.es + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam)
+                        : wave_select_child(bp.es + m.first, mn, parentN, v.c_puct, nullptr);
             cur = m.first + bi;
             d++;
             if (d >= v.p_cap) { err = SZ_ERR_CAPACITY; break; }
             path[d] = cur;
             m = bp.em[cur];
-            parentN = uni(bp.es[cur].N);
+            parentN = uni(bp.es[cur].N + (VL ? vk[cur] : 0));
             m.first = uni(m.first); mn = uni((int)m.n);
         }
         if (err) break;
         STEP_STAMP(2);
         int node = uni(m.node);
         if (node >= 0) {
+            if (VL && !uni((int)m.term) && m.first < 0) break;          // batched: a collision with a leaf pending in this step ends the gather
             // visited leaf without children: a terminal position (mcts.py:104-109)
             double tv = (double)(int)m.tval;
             wave_backprop(bp.es, path, d, tv);
@@ -627,6 +690,21 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         }
         // non-terminal leaf: hand it to the network
         __syncthreads();
+        if constexpr (VL) {
+            // batched: pending leaf n_pend at row slot(b)*L + n_pend; its descent goes in flight (k + 1 along its path) and the gather goes on
+            const size_t li = (size_t)b * vb.L + n_pend;
+            for (int i = lane; i < SZ_MASK_WORDS; i += 64) vb.mask[li * PMASK_STRIDE + i] = mask[i];
+            for (int j = lane; j <= d; j += 64) { vb.path[li * v.p_cap + j] = path[j]; vk[path[j]] += 1; }
+            if (lane == 0) vb.depth[li] = d;
+            wave_load_history(bp, path, d, root_ply, X, hist);
+            __syncthreads();
+            wave_encode(hist, X, (char*)planes + ((size_t)row * vb.L + n_pend) * planes_board_bytes(v.planes_dtype), v.planes_dtype, nullptr);
+            __threadfence_block();
+            __syncthreads();
+            n_pend++;
+            status |= ST_PENDING;
+            continue;
+        }
         for (int i = lane; i < SZ_MASK_WORDS; i += 64) bp.pmask[i] = mask[i];
         for (int j = lane; j <= d; j += 64) bp.gpath[j] = path[j];
         wave_load_history(bp, path, d, root_ply, X, hist);
@@ -645,7 +723,20 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         c->n_expand += n_expand; c->n_term += n_term; c->sum_depth += sum_depth; c->sum_k += sum_k;
         if (n_edges > c->max_edges) c->max_edges = n_edges;
         if (err && !c->err) c->err = err;
+        if constexpr (VL) c->n_pend = n_pend;
     }
+}
+
+// boards still waiting for the network (sz_pending_boards): one workgroup
+__global__ __launch_bounds__(1024) void k_count_pending(View v, int* out) {
+    __shared__ int tot;
+    if (threadIdx.x == 0) tot = 0;
+    __syncthreads();
+    int c = 0;
+    for (int b = threadIdx.x; b < v.B; b += 1024) c += (v.ctl[b].status & ST_PENDING) ? 1 : 0;
+    if (c) atomicAdd(&tot, c);
+    __syncthreads();
+    if (threadIdx.x == 0) *out = tot;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -805,6 +896,9 @@ struct sz_engine {
     std::vector<void*> allocs;
     int* d_scharnagl; uint8_t* d_active;
     int* d_slot; int* d_nlive;
+    Batch vb;                       // sz_set_leaf_batching; vb.L == 1: the reference's search, nothing allocated
+    int vb_cap;                     // L the batching buffers were allocated for
+    std::vector<void*> vb_allocs;
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
@@ -878,6 +972,7 @@ int sz_create(const sz_config* cfg, sz_engine** out) {
     v.p_cap = v.n_cap;
     v.learning = cfg->learning; v.chess960 = cfg->chess960; v.planes_dtype = cfg->planes_dtype;
     v.c_puct = cfg->c_puct; v.noise = cfg->noise_value; v.root_gamma = nullptr; v.dbg = nullptr;
+    e->vb.L = 1; e->vb.lam = 1.0f;
     e->lds_bytes = (LDS_HIST_WORDS + LDS_MASK_WORDS) * 8 + (size_t)(v.p_cap > 256 ? v.p_cap : 256) * 4 + 220 * 4 + 220 * 2;   // + expand stash
     if (e->lds_bytes > 64 * 1024) { delete e; return SZ_ERR_INVALID; }
     const size_t B = v.B;
@@ -905,6 +1000,7 @@ int sz_destroy(sz_engine* e) {
     if (!e) return SZ_OK;
     ENGINE_GUARD(e);
     for (void* p : e->allocs) (void)hipFree(p);
+    for (void* p : e->vb_allocs) (void)hipFree(p);
     delete e;
     return SZ_OK;
 }
@@ -981,12 +1077,14 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    hipLaunchKernelGGL(k_search_begin, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev);
+    if (e->vb.L > 1) hipLaunchKernelGGL(k_search_begin<true>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
+    else hipLaunchKernelGGL(k_search_begin<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
     HIPCHK(hipGetLastError());
     if (e->v.reuse && planes_dev) {
         // boards that continue on a kept subtree have no root to evaluate: one descent-only launch selects their first leaf (boards whose fresh
         // root waits for the network sit it out), so that every board enters the first network call with a real position
-        hipLaunchKernelGGL(k_search_step, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, (const float*)nullptr, (const float*)nullptr, planes_dev);
+        hipLaunchKernelGGL(k_search_step<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, (const float*)nullptr, (const float*)nullptr, planes_dev,
+                           Batch{});
         HIPCHK(hipGetLastError());
     }
     return SZ_OK;
@@ -995,8 +1093,58 @@ int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
 int sz_search_step(sz_engine* e, const float* policy_dev, const float* value_dev, void* planes_dev, void* stream) {
     if (!e || !policy_dev || !value_dev || !planes_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    hipLaunchKernelGGL(k_search_step, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev);
+    if (e->vb.L > 1)
+        hipLaunchKernelGGL(k_search_step<true>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, e->vb);
+    else
+        hipLaunchKernelGGL(k_search_step<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, Batch{});
     HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream) {
+    if (!e || leaves_per_step < 1 || leaves_per_step > SZ_MAX_LEAVES_PER_STEP || !(virtual_loss >= 0.0f) || !std::isfinite(virtual_loss)) return SZ_ERR_INVALID;
+    if (leaves_per_step > 1 && e->v.reuse) return SZ_ERR_INVALID;          // combining the two non-reference options is not supported
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Ctl> h(e->v.B);
+    HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (const Ctl& c : h)
+        if ((c.status & ST_SEARCHING) && !(c.status & (ST_DONE | ST_ERROR))) return SZ_ERR_STATE;       // only between searches
+    if (leaves_per_step > 1 && leaves_per_step > e->vb_cap) {
+        for (void* p : e->vb_allocs) (void)hipFree(p);
+        e->vb_allocs.clear(); e->vb_cap = 0;
+        const size_t B = e->v.B, L = leaves_per_step;
+        void* q[4] = {nullptr, nullptr, nullptr, nullptr};
+        const size_t bytes[4] = {B * e->v.e_cap * sizeof(int), B * L * e->v.p_cap * sizeof(int), B * L * PMASK_STRIDE * sizeof(u64), B * L * sizeof(int)};
+        for (int k = 0; k < 4; k++) {
+            hipError_t err = hipMalloc(&q[k], bytes[k]);
+            if (err != hipSuccess) {
+                fprintf(stderr, "[sigmazero] hipMalloc(%zu bytes) failed: %s\n", bytes[k], hipGetErrorString(err));
+                for (void* p : e->vb_allocs) (void)hipFree(p);
+                e->vb_allocs.clear(); e->vb.L = 1;
+                return SZ_ERR_HIP;
+            }
+            e->vb_allocs.push_back(q[k]);
+        }
+        e->vb.vk = (int*)q[0]; e->vb.path = (int*)q[1]; e->vb.mask = (u64*)q[2]; e->vb.depth = (int*)q[3];
+        e->vb_cap = leaves_per_step;
+    }
+    e->vb.L = leaves_per_step;
+    e->vb.lam = virtual_loss;
+    return SZ_OK;
+}
+
+int sz_pending_boards(sz_engine* e, int32_t* n_out, void* stream) {
+    if (!e || !n_out) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_count_pending, dim3(1), dim3(1024), 0, s, e->v, e->d_nlive);
+    HIPCHK(hipGetLastError());
+    int n = 0;
+    HIPCHK(hipMemcpyAsync(&n, e->d_nlive, sizeof n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n_out = n;
     return SZ_OK;
 }
 

@@ -26,9 +26,12 @@ class MCTS0:
     def _engine(self, learning):
         key = (bool(learning), bool(self.game.chess960))
         if key not in self._engines:
-            dtype = next(self.model.parameters()).dtype if hasattr(self.model, "parameters") else torch.float32
-            if dtype not in (torch.float32, torch.bfloat16):
-                dtype = torch.float32
+            if hasattr(self.model, "tower"):               # FastPolicyNet / SplitPolicyNet read the engine's NHWC image (as sim.play_games)
+                dtype = "bits128" if getattr(self.model, "w16", False) else "nhwc128"
+            else:
+                dtype = next(self.model.parameters()).dtype if hasattr(self.model, "parameters") else torch.float32
+                if dtype not in (torch.float32, torch.bfloat16):
+                    dtype = torch.float32
             self._engines[key] = SelfPlayEngine(self.model, self.args, 1, chess960=key[1], learning=key[0], planes_dtype=dtype,
                                                 noise_value=self.args.get("noise_value", NOISE_REFERENCE), device=self.device)
         return self._engines[key]

@@ -1,6 +1,7 @@
 """Batched self-play driver: B boards stepped in lock-step through the HIP engine with one batched
 network call per simulation.  This is the GPU counterpart of sim.py:31-99 + mcts.py:39-122."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -45,6 +46,17 @@ class SelfPlayEngine:
         self.S = int(args["num_searches"])
         self.chess960 = bool(chess960)
         self.planes_dtype = planes_dtype
+        # NON-REFERENCE option (default off): args["leaves_per_step"] = L > 1 gathers up to L leaves per board per network call, steered
+        # apart by a virtual loss args["virtual_loss"] per descent in flight (sz_set_leaf_batching); board b's leaf i is network row slot(b)*L + i
+        L, lam = self.args.get("leaves_per_step", 1), self.args.get("virtual_loss", 1.0)
+        if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= L <= N.SZ_MAX_LEAVES_PER_STEP:
+            raise ValueError("args['leaves_per_step'] must be an integer in 1..%d, got %r" % (N.SZ_MAX_LEAVES_PER_STEP, L))
+        if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not (math.isfinite(lam) and lam >= 0):
+            raise ValueError("args['virtual_loss'] must be a finite number >= 0, got %r" % (lam,))
+        if L > 1 and self.args.get("reuse_subtree", False):
+            raise ValueError("args['leaves_per_step'] > 1 and args['reuse_subtree'] exclude each other")
+        self.L, self.virtual_loss = int(L), float(lam)
+        self.last_steps = 0           # network calls made by the last search()
         # planes_dtype: torch.float32 / torch.bfloat16 -> [B,119,8,8] NCHW (reference layout);
         #               "nhwc128" -> [B,64,128] bf16 position-major for FastPolicyNet (csrc/sz_nn.hip)
         #               "bits128" -> the same image bit-packed, [B,1024] uint8 (1 KiB per board), expanded by the stem kernel
@@ -56,12 +68,15 @@ class SelfPlayEngine:
         self._e = C.c_void_p()
         N.check(N.lib().sz_create(C.byref(cfg), C.byref(self._e)), "sz_create")
         dev = self.device
+        rows = self.B * self.L        # network rows
         if self.bits:
-            self.planes = torch.zeros(self.B, 1024, dtype=torch.uint8, device=dev)
+            self.planes = torch.zeros(rows, 1024, dtype=torch.uint8, device=dev)
         elif self.nhwc:
-            self.planes = torch.zeros(self.B, 64, 128, dtype=torch.bfloat16, device=dev)
+            self.planes = torch.zeros(rows, 64, 128, dtype=torch.bfloat16, device=dev)
         else:
-            self.planes = torch.zeros(self.B, N.SZ_PLANES, 8, 8, dtype=planes_dtype, device=dev)
+            self.planes = torch.zeros(rows, N.SZ_PLANES, 8, 8, dtype=planes_dtype, device=dev)
+        if self.L > 1:
+            N.check(N.lib().sz_set_leaf_batching(self._e, self.L, self.virtual_loss, self._stream()), "sz_set_leaf_batching")
         self.uniforms = torch.zeros(self.B, dtype=torch.float64, device=dev)
         self.root_action = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
         self.root_visits = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
@@ -134,17 +149,37 @@ class SelfPlayEngine:
     def step(self, policy, value):
         N.check(N.lib().sz_search_step(self._e, _ptr(policy), _ptr(value), _ptr(self.planes), self._stream()), "sz_search_step")
 
+    def pending_boards(self):
+        """boards still waiting for a network evaluation (sz_pending_boards; synchronises the stream)"""
+        n = C.c_int32()
+        N.check(N.lib().sz_pending_boards(self._e, C.byref(n), self._stream()), "sz_pending_boards")
+        return int(n.value)
+
     @torch.no_grad()
     def search(self, evaluator=None):
-        """All num_searches simulations for every active board (mcts.py:49-109)."""
+        """All num_searches simulations for every active board (mcts.py:49-109).  The network sees n_rows * leaves_per_step rows."""
         ev = evaluator or self.evaluate
         self.begin()
+        self.last_steps = 0
         if self.n_rows <= 0:
             return
-        planes = self.planes if self.n_rows == self.B else self.planes[:self.n_rows]
-        for _ in range(self.S):
-            policy, value = ev(planes)
-            self.step(policy, value)
+        rows = self.n_rows * self.L
+        planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
+        if self.L == 1:
+            for _ in range(self.S):
+                policy, value = ev(planes)
+                self.step(policy, value)
+            self.last_steps = self.S
+            return
+        # leaf batching: a collision ends a board's gather early, so the number of steps depends on the trees (at most S): ceil(S/L) steps
+        # without a host sync, then one step at a time until no board waits for the network
+        n = -(-self.S // self.L)
+        while n > 0:
+            for _ in range(n):
+                policy, value = ev(planes)
+                self.step(policy, value)
+            self.last_steps += n
+            n = 1 if self.last_steps < self.S and self.pending_boards() else 0
 
     def stats(self):
         st = N.sz_stats()

@@ -162,14 +162,14 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             eng.check_errors()
         t0 = lap("play_fetch", t0)
         pending = (rec, slot_game.copy())
-        work["sims"] += S * len(running); work["nn_rows"] += S * n_rows; work["plies"] += 1
+        work["sims"] += S * len(running); work["nn_rows"] += eng.last_steps * n_rows * eng.L; work["plies"] += 1
         plies[slot_game[running]] += 1
         done = [int(s_) for s_ in running if (rec["game_over"][s_] and rec["active"][s_]) or plies[slot_game[s_]] >= cap[slot_game[s_]]]
         if done:
             refill(done)
         lap("refill", t0)
         if verbose:
-            print("ply %d: %d games running, %d waiting, %d network rows" % (work["plies"], int((slot_game >= 0).sum()), n_games - next_game, n_rows))
+            print("ply %d: %d games running, %d waiting, %d network rows" % (work["plies"], int((slot_game >= 0).sum()), n_games - next_game, n_rows * eng.L))
     if pending is not None:
         absorb(*pending)
     for g in range(n_games):

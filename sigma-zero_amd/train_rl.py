@@ -489,6 +489,9 @@ def main(argv=None):
     ap.add_argument("--inference", default="fp16", choices=["fp16", "bf16", "split", "fp32"],
                     help="self-play network (run_cycle): fp16 = MFMA tower on f16 operands (default: fp32's visit counts on every tested position, 0.95x of bf16), "
                          "bf16 = fastest (single visits move), split = hi+lo bf16 operands (fp32-class by construction, 0.40x), fp32 = torch module")
+    ap.add_argument("--leaves-per-step", type=int, default=1,
+                    help="NON-REFERENCE: leaves gathered per board per network call, with virtual loss (1 = the reference's search)")
+    ap.add_argument("--virtual-loss", type=float, default=1.0, help="virtual loss per descent in flight (with --leaves-per-step > 1)")
     a = ap.parse_args(argv)
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     gpr = [int(x) for x in str(a.games_per_rank).split(",")]
@@ -518,6 +521,8 @@ def main(argv=None):
     sync_module_state(model, average_buffers=False)
     sync = GradSync(model) if world > 1 else None
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
+    if a.leaves_per_step != 1:
+        args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
     import random
     random.seed(1000 + rank)
     np.random.seed(1000 + rank)
