@@ -1,6 +1,8 @@
 """GPU parity against fixtures produced by the REFERENCE's own chess_tensor.py / mcts.py / mctsnode.py / sim.py (run unmodified in the
 build container, tests/golden/gen_reference_chess_fixtures.py and gen_reference_fixtures.py).  Everything goes through the C ABI
-(ctypes) of libsigmazero_hip.so; the oracle is not involved here: HIP engine vs reference output directly."""
+(ctypes) of libsigmazero_hip.so; the oracle is not involved here: HIP engine vs reference output directly.
+The roots uploaded here (sz_upload_game) carry the HOST's `meta` / `key` words (szh_export), which k_search_begin trusts; the device's own
+sz_finish_meta, key and repetition count are covered by tests/test_gpu_device_perft.py (every node created in a tree or by k_play)."""
 import ctypes as C
 import os
 import random
