@@ -165,6 +165,27 @@ int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_lo
  * data-dependent number of steps (collisions end a gather early): step until this is 0. */
 int sz_pending_boards(sz_engine* e, int32_t* n_out, void* stream);
 
+/* NON-REFERENCE option (default: every board runs num_searches simulations, as the reference's one args['num_searches'] does): a search
+ * budget per board.  budgets: HOST array [n_boards], each entry in 0..num_searches; NULL = every board num_searches again.  num_searches
+ * stays the capacity the stores were sized for.  Takes effect at the next sz_search_begin and holds until changed.  A board with budget s
+ * searches exactly like a board of an engine created with num_searches = s, bit for bit — s = 0 and a terminal root (N = 1 + s, W = tv*s),
+ * SZ_ERR_ZERO_VISITS from sz_play at s = 1 and the counters of sz_get_stats included — with leaf batching as well (simulations done +
+ * pending == s ends a gather).  This is playout-cap randomisation's engine half (KataGo: most plies searched cheaply, a random few
+ * fully); the reference has nothing like it.
+ * SZ_ERR_INVALID: an entry outside 0..num_searches, or budgets != NULL on an engine created with reuse_subtree (a kept subtree already
+ * holds simulations; the combination is not supported).  SZ_ERR_STATE: a search is in progress (the rule of sz_set_leaf_batching). */
+int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream);
+/* IN-SEARCH batch compaction, the other half: valid only between sz_search_begin and the end of that search (SZ_ERR_STATE before a
+ * search and once no board searches any more; nothing is changed then).  The boards that still search (not done, no error) are renumbered
+ * 0..n_live-1 in board order, the others get no row, and the pending network inputs of the live boards — leaves_per_step rows each — are
+ * moved to their new rows of planes_dev (the buffer sz_search_begin / sz_search_step wrote; staged through an engine-owned buffer that
+ * is allocated on first use, since a board's new row can be another live board's old row).  When the call returns the next evaluation runs
+ * on rows 0..n_live*leaves_per_step-1 and the next sz_search_step reads policy / value from the new rows.  Works from the identity
+ * mapping and after sz_compact (rows only ever move down); the next sz_compact between searches replaces the mapping as before — call it
+ * (enable 1 or 0) before the next sz_search_begin, a board without a row is flagged SZ_ERR_STATE there.  Results per board do not depend
+ * on the mapping.  Synchronises the stream to return n_live. */
+int sz_compact_searching(sz_engine* e, void* planes_dev, int32_t* n_live_out, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

@@ -47,6 +47,8 @@ EXPORTS = {
     "sz_search_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sz_set_leaf_batching": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "sz_pending_boards": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_get_stats": (C.c_int, [C.c_void_p, C.POINTER(sz_stats), C.c_void_p]),
     "sz_root_children": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]),
     "sz_play": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -56,6 +56,7 @@ struct View {
     int* nmap;                  // reuse only: [B][n_cap] scratch map node id -> new index of the edge that owns it, during k_play's compaction
     const int* slot;            // optional (sz_compact): row of board b in the network batch (planes / policy / value); NULL = identity
     const float* root_gamma;    // optional (non-reference) true Dirichlet root noise: [B][SZ_MAX_MOVES] Gamma(alpha,1) draws; NULL = reference behaviour
+    const int* budget;          // optional (non-reference, sz_set_search_budgets): simulations of board b in 0..S; NULL = S everywhere (S stays the capacity)
     SzPos* npos; SzPos* ring; EdgeStat* es; EdgeMeta* em; int* gpath; u64* pmask; Ctl* ctl;
     // per-ply training record
     uint8_t* rec_planes; int* rec_action; int* rec_visits; int* rec_nchild; uint8_t* rec_colour; int* rec_chosen;
@@ -158,6 +159,8 @@ __device__ __forceinline__ int wave_select_child_vl(const EdgeStat* ch, const in
 struct BoardPtrs {
     SzPos* npos; SzPos* ring; EdgeStat* es; EdgeMeta* em; int* gpath; u64* pmask; Ctl* ctl;
 };
+// simulations this board's search runs: its own budget (sz_set_search_budgets), else num_searches
+__device__ __forceinline__ int board_budget(const View& v, int b) { return v.budget ? uni(v.budget[b]) : v.S; }
 __device__ __forceinline__ BoardPtrs board_ptrs(const View& v, int b) {
     BoardPtrs p;
     p.npos = v.npos + (size_t)b * v.n_cap;
@@ -388,12 +391,18 @@ __global__ void k_set_active(View v, const uint8_t* active) {
     c->status = st;
 }
 
-// network-batch rows for the boards that will search (active, game not over, no error), in board order: one workgroup, chunked scan
+// network-batch rows for the boards that will search (active, game not over, no error), in board order: one workgroup, chunked scan.
+// IN_SEARCH (sz_compact_searching): the boards that still search (searching, not done, no error) instead.
+template <bool IN_SEARCH>
+__device__ __forceinline__ bool compact_live(int st) {
+    return IN_SEARCH ? ((st & ST_SEARCHING) && !(st & (ST_DONE | ST_ERROR))) : ((st & ST_ACTIVE) && !(st & (ST_GAMEOVER | ST_ERROR)));
+}
+template <bool IN_SEARCH>
 __global__ __launch_bounds__(1024) void k_compact(View v, int* slot, int* n_live) {
     __shared__ int cnt[1024];
     const int t = threadIdx.x, per = (v.B + 1023) / 1024, lo = t * per, hi = min(v.B, lo + per);
     int c = 0;
-    for (int b = lo; b < hi; b++) { const int st = v.ctl[b].status; c += ((st & ST_ACTIVE) && !(st & (ST_GAMEOVER | ST_ERROR))) ? 1 : 0; }
+    for (int b = lo; b < hi; b++) c += compact_live<IN_SEARCH>(v.ctl[b].status) ? 1 : 0;
     cnt[t] = c;
     __syncthreads();
     for (int off = 1; off < 1024; off <<= 1) {                     // inclusive Hillis-Steele scan over the 1024 chunk counts
@@ -403,12 +412,25 @@ __global__ __launch_bounds__(1024) void k_compact(View v, int* slot, int* n_live
         __syncthreads();
     }
     int base = cnt[t] - c;
-    for (int b = lo; b < hi; b++) {
-        const int st = v.ctl[b].status;
-        const bool live = (st & ST_ACTIVE) && !(st & (ST_GAMEOVER | ST_ERROR));
-        slot[b] = live ? base++ : -1;
-    }
+    for (int b = lo; b < hi; b++) slot[b] = compact_live<IN_SEARCH>(v.ctl[b].status) ? base++ : -1;
     if (t == 1023) *n_live = cnt[1023];
+}
+
+// sz_compact_searching: move the pending network inputs of the boards that keep a row, `rows` rows of row_u4 uint4 each per board, from
+// rows old_slot(b)*rows.. of `src` to rows new_slot(b)*rows.. of `dst`.  One workgroup per board.  It runs twice, caller's buffer -> the
+// engine's staging buffer (to_stage: src rows by the old mapping) and back (src rows by the new one): a board's new row can be another live
+// board's old row, so a copy in place would race.  Boards whose row does not change are left alone.
+__global__ __launch_bounds__(256) void k_move_rows(const uint4* __restrict__ src, uint4* __restrict__ dst, const int* old_slot, const int* new_slot, int rows,
+                                                   int row_u4, int to_stage) {
+    const int b = blockIdx.x;
+    const int ns = new_slot[b];
+    if (ns < 0) return;
+    const int os = old_slot ? old_slot[b] : b;
+    if (os < 0 || os == ns) return;
+    const size_t n = (size_t)rows * row_u4;
+    const uint4* s = src + (size_t)(to_stage ? os : ns) * n;
+    uint4* d = dst + (size_t)ns * n;
+    for (size_t i = threadIdx.x; i < n; i += 256) d[i] = s[i];
 }
 
 // finish an uploaded game record (status only; the ring was copied by the host)
@@ -469,10 +491,11 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
         bp.gpath[0] = 0;
     }
     int st = (status & ST_ACTIVE) | ST_SEARCHING;
-    if (szm_term(X.meta) || v.S <= 0) {
+    const int budget = board_budget(v, b);
+    if (szm_term(X.meta) || budget <= 0) {
         // a terminal root: every simulation re-visits it (mcts.py:104-109); children stay empty
         if (lane == 0) {
-            int S = v.S > 0 ? v.S : 0;
+            int S = budget > 0 ? budget : 0;
             double tv = szm_loss(X.meta) ? -1.0 : 0.0;
             bp.es[0].W = tv * (double)S; bp.es[0].N = 1 + S;
             Ctl* c = bp.ctl; c->status = st | ST_DONE; c->n_nodes = 1; c->n_edges = 1; c->sims_done = S;
@@ -523,6 +546,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     if (!(status & ST_SEARCHING) || (status & (ST_DONE | ST_ERROR))) return;
     int n_nodes = uni(bp.ctl->n_nodes), n_edges = uni(bp.ctl->n_edges), sims = uni(bp.ctl->sims_done);
     const int root_ply = uni(bp.ctl->game_ply);
+    const int budget = board_budget(v, b);                    // this board's simulations (num_searches unless sz_set_search_budgets)
     const int row = v.slot ? uni(v.slot[b]) : b;              // network batch row of this board
     if (row < 0) return;
     if ((status & ST_PENDING) && !policy) return;             // descent-only launch (sz_search_begin with reuse): boards that already wait for the network sit it out
@@ -639,7 +663,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     // ---- next simulation(s): mcts.py:49-64 ------------------------------------------------------
     int n_pend = 0;                                                     // batched: leaves gathered in this step
     int* vk = VL ? vb.vk + (size_t)b * v.e_cap : nullptr;
-    while (sims + n_pend < v.S && (!VL || n_pend < vb.L) && !err) {
+    while (sims + n_pend < budget && (!VL || n_pend < vb.L) && !err) {
         int d = 0, cur = 0;
         path[0] = 0;
         EdgeMeta m = bp.em[0];
@@ -715,7 +739,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         STEP_STAMP(4);
         break;
     }
-    if (sims >= v.S && !(status & ST_PENDING)) status |= ST_DONE;
+    if (sims >= budget && !(status & ST_PENDING)) status |= ST_DONE;
     if (err) status |= ST_ERROR;
     if (lane == 0) {
         Ctl* c = bp.ctl;
@@ -896,6 +920,9 @@ struct sz_engine {
     std::vector<void*> allocs;
     int* d_scharnagl; uint8_t* d_active;
     int* d_slot; int* d_nlive;
+    int* d_slot_next;               // sz_compact_searching: the mapping being built (swapped with d_slot when the call succeeds)
+    int* d_budget;                  // sz_set_search_budgets: [n_boards], View::budget points here while budgets are set
+    void* stage; size_t stage_bytes;    // sz_compact_searching: staging buffer of the row move, allocated on first use
     Batch vb;                       // sz_set_leaf_batching; vb.L == 1: the reference's search, nothing allocated
     int vb_cap;                     // L the batching buffers were allocated for
     std::vector<void*> vb_allocs;
@@ -984,7 +1011,8 @@ int sz_create(const sz_config* cfg, sz_engine** out) {
         (rc = dalloc(e, &v.rec_nchild, B)) || (rc = dalloc(e, &v.rec_colour, B)) || (rc = dalloc(e, &v.rec_chosen, B)) ||
         (rc = dalloc(e, &v.rec_over, B)) || (rc = dalloc(e, &v.rec_result, B)) || (rc = dalloc(e, &v.rec_active, B)) ||
         (v.reuse && (rc = dalloc(e, &v.nmap, B * v.n_cap))) ||
-        (rc = dalloc(e, &e->d_scharnagl, B)) || (rc = dalloc(e, &e->d_active, B)) || (rc = dalloc(e, &e->d_slot, B)) || (rc = dalloc(e, &e->d_nlive, 1))) {
+        (rc = dalloc(e, &e->d_scharnagl, B)) || (rc = dalloc(e, &e->d_active, B)) || (rc = dalloc(e, &e->d_slot, B)) || (rc = dalloc(e, &e->d_nlive, 1)) ||
+        (rc = dalloc(e, &e->d_slot_next, B)) || (rc = dalloc(e, &e->d_budget, B))) {
         sz_destroy(e);
         return rc;
     }
@@ -1001,6 +1029,7 @@ int sz_destroy(sz_engine* e) {
     ENGINE_GUARD(e);
     for (void* p : e->allocs) (void)hipFree(p);
     for (void* p : e->vb_allocs) (void)hipFree(p);
+    if (e->stage) (void)hipFree(e->stage);
     delete e;
     return SZ_OK;
 }
@@ -1032,11 +1061,77 @@ int sz_compact(sz_engine* e, int32_t enable, int32_t* n_live_out, void* stream) 
     ENGINE_GUARD(e);
     if (!enable) { e->v.slot = nullptr; if (n_live_out) *n_live_out = e->v.B; return SZ_OK; }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, e->v, e->d_slot, e->d_nlive);
+    hipLaunchKernelGGL(k_compact<false>, dim3(1), dim3(1024), 0, s, e->v, e->d_slot, e->d_nlive);
     HIPCHK(hipGetLastError());
     int n = 0;
     HIPCHK(hipMemcpyAsync(&n, e->d_nlive, sizeof n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    e->v.slot = e->d_slot;
+    if (n_live_out) *n_live_out = n;
+    return SZ_OK;
+}
+
+// true while some board is between sz_search_begin and the end of its search (synchronises the stream)
+static int search_in_progress(sz_engine* e, hipStream_t s, bool* out) {
+    std::vector<Ctl> h(e->v.B);
+    HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *out = false;
+    for (const Ctl& c : h)
+        if ((c.status & ST_SEARCHING) && !(c.status & (ST_DONE | ST_ERROR))) *out = true;
+    return SZ_OK;
+}
+
+int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (budgets && e->v.reuse) return SZ_ERR_INVALID;                      // a kept subtree already holds simulations: not combined with budgets
+    if (budgets)
+        for (int b = 0; b < e->v.B; b++)
+            if (budgets[b] < 0 || budgets[b] > e->v.S) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if (budgets) {
+        HIPCHK(hipMemcpyAsync(e->d_budget, budgets, (size_t)e->v.B * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
+    }
+    e->v.budget = budgets ? e->d_budget : nullptr;
+    return SZ_OK;
+}
+
+int sz_compact_searching(sz_engine* e, void* planes_dev, int32_t* n_live_out, void* stream) {
+    if (!e || !planes_dev) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const View& v = e->v;
+    const int rows = e->vb.L;
+    const size_t row_bytes = v.planes_dtype == SZ_PLANES_F32 ? (size_t)SZ_NUM_PLANES * 64 * 4 : (v.planes_dtype == SZ_PLANES_BF16 ? (size_t)SZ_NUM_PLANES * 64 * 2 :
+                             (v.planes_dtype == SZ_PLANES_NHWC128_BITS ? (size_t)1024 : (size_t)64 * 128 * 2));      // = planes_board_bytes, all multiples of 16
+    const size_t need = (size_t)v.B * rows * row_bytes;
+    if (need > e->stage_bytes) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (e->stage) (void)hipFree(e->stage);
+        e->stage = nullptr; e->stage_bytes = 0;
+        hipError_t err = hipMalloc(&e->stage, need);
+        if (err != hipSuccess) { fprintf(stderr, "[sigmazero] hipMalloc(%zu bytes) failed: %s\n", need, hipGetErrorString(err)); e->stage = nullptr; return SZ_ERR_HIP; }
+        e->stage_bytes = need;
+    }
+    // new mapping into d_slot_next, rows out to the staging buffer and back; the mapping in use is replaced only when the call succeeds.
+    // With no board searching (before sz_search_begin, after the search ended) every new row is -1 and the two moves touch nothing.
+    hipLaunchKernelGGL(k_compact<true>, dim3(1), dim3(1024), 0, s, v, e->d_slot_next, e->d_nlive);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_move_rows, dim3(v.B), dim3(256), 0, s, (const uint4*)planes_dev, (uint4*)e->stage, v.slot, e->d_slot_next, rows, (int)(row_bytes / 16), 1);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_move_rows, dim3(v.B), dim3(256), 0, s, (const uint4*)e->stage, (uint4*)planes_dev, v.slot, e->d_slot_next, rows, (int)(row_bytes / 16), 0);
+    HIPCHK(hipGetLastError());
+    int n = 0;
+    HIPCHK(hipMemcpyAsync(&n, e->d_nlive, sizeof n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (n <= 0) return SZ_ERR_STATE;
+    int* t = e->d_slot; e->d_slot = e->d_slot_next; e->d_slot_next = t;
     e->v.slot = e->d_slot;
     if (n_live_out) *n_live_out = n;
     return SZ_OK;

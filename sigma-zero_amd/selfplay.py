@@ -32,6 +32,54 @@ def model_device(model, default=None):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def search_segments(budgets, L=1, max_shrinks=4, num_searches=None):
+    """Step counts of the segments a budgeted search is run in (SelfPlayEngine.search): after every segment but the last the network
+    batch shrinks to the boards that still search (sz_compact_searching, one stream synchronisation each).
+
+    budgets: simulations per board, or None (every board num_searches).  A board with budget s needs ceil(s / L) steps — exactly that many
+    at L = 1, at least that many with leaf batching, where collisions end gathers early — so the candidate segment ends are the distinct
+    values of ceil(s / L), and the last one, ceil(max / L), is the part of the search that runs without asking the device (with L > 1 the
+    caller then steps until no board is pending).  At most max_shrinks interior ends are kept; when there are more candidates, the ones
+    that minimise the network rows evaluated (segment length x boards searching during it), so nearby budget values share an end.
+    Returns a list of positive step counts that sums to ceil(max / L); [] when nothing is to be searched."""
+    L, max_shrinks = int(L), int(max_shrinks)
+    if L < 1 or max_shrinks < 0:
+        raise ValueError("search_segments: L must be >= 1 and max_shrinks >= 0")
+    if budgets is None:
+        total = -(-int(num_searches or 0) // L)
+        return [total] if total > 0 else []
+    b = np.asarray(budgets, dtype=np.int64).reshape(-1)
+    if b.size and b.min() < 0:
+        raise ValueError("search_segments: budgets must be >= 0")
+    need = -(-b[b > 0] // L)                                     # steps each searching board needs
+    if not need.size:
+        return []
+    ends, counts = np.unique(need, return_counts=True)          # candidate ends ascending, boards finishing at each
+    k = len(ends)
+    t = min(max_shrinks, k - 1)
+    if t == k - 1:
+        chosen = list(range(k))
+    elif t == 0:
+        chosen = [k - 1]
+    else:
+        alive = need.size - np.cumsum(counts)                   # boards still searching after candidate j
+        ends_f = ends.astype(np.float64)
+        best = ends_f * need.size                               # no interior end before candidate i
+        back = []
+        for _ in range(t):                                      # one more interior end per round
+            cand = best[None, :] + (ends_f[:, None] - ends_f[None, :]) * alive[None, :]      # [i, j]: j the interior end before i
+            cand[np.triu_indices(k)] = np.inf                   # j < i only
+            back.append(np.argmin(cand, axis=1))
+            best = cand.min(axis=1)
+        chosen, i = [k - 1], k - 1
+        for arg in reversed(back):
+            i = int(arg[i])
+            chosen.append(i)
+        chosen.reverse()
+    cuts = [0] + [int(ends[i]) for i in chosen]
+    return [hi - lo for lo, hi in zip(cuts[:-1], cuts[1:])]
+
+
 class SelfPlayEngine:
     def __init__(self, model, args, n_boards, chess960=False, learning=True, device=None, planes_dtype=torch.float32,
                  noise_value=NOISE_REFERENCE, edges_per_board=0):
@@ -57,6 +105,16 @@ class SelfPlayEngine:
             raise ValueError("args['leaves_per_step'] > 1 and args['reuse_subtree'] exclude each other")
         self.L, self.virtual_loss = int(L), float(lam)
         self.last_steps = 0           # network calls made by the last search()
+        self.last_rows = 0            # network rows evaluated by the last search()
+        # NON-REFERENCE option (default off): per-board search budgets (set_budgets) with in-search batch shrinking; at most
+        # args["max_shrinks"] shrinks per search on top of the one right after the roots were made (each costs a stream synchronisation)
+        ms = self.args.get("max_shrinks", 4)
+        if isinstance(ms, bool) or not isinstance(ms, (int, np.integer)) or ms < 0:
+            raise ValueError("args['max_shrinks'] must be an integer >= 0, got %r" % (ms,))
+        self.max_shrinks = int(ms)
+        self.budgets = None           # host copy of the budgets in force (None: every board num_searches)
+        self._compact_on = False      # the mapping chosen by the last compact() call
+        self._restore = False         # a search shrank the batch: the caller's mapping is put back before the next search begins
         # planes_dtype: torch.float32 / torch.bfloat16 -> [B,119,8,8] NCHW (reference layout);
         #               "nhwc128" -> [B,64,128] bf16 position-major for FastPolicyNet (csrc/sz_nn.hip)
         #               "bits128" -> the same image bit-packed, [B,1024] uint8 (1 KiB per board), expanded by the stem kernel
@@ -128,7 +186,41 @@ class SelfPlayEngine:
         n = C.c_int32()
         N.check(N.lib().sz_compact(self._e, int(bool(enable)), C.byref(n), self._stream()), "sz_compact")
         self.n_rows = int(n.value) if enable else self.B
+        self._compact_on, self._restore = bool(enable), False
         return self.n_rows
+
+    def set_budgets(self, budgets):
+        """Per-board search budgets (sz_set_search_budgets, a NON-REFERENCE option): budgets[b] in 0..num_searches simulations for board b
+        from the next search on, until changed; None = every board num_searches again.  A board searched with budget s has, bit for bit,
+        the tree it has in an engine created with num_searches = s."""
+        if budgets is None:
+            N.check(N.lib().sz_set_search_budgets(self._e, None, self._stream()), "sz_set_search_budgets")
+            self.budgets = None
+            return
+        b = np.ascontiguousarray(budgets, dtype=np.int32).reshape(-1)
+        if b.shape[0] != self.B:
+            raise ValueError("set_budgets: %d budgets for %d boards" % (b.shape[0], self.B))
+        N.check(N.lib().sz_set_search_budgets(self._e, b.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "sz_set_search_budgets")
+        self.budgets = b.copy()
+
+    def _compact_searching(self):
+        """sz_compact_searching; returns n_live, or 0 when no board searches any more (the mapping is left alone then)"""
+        n = C.c_int32()
+        rc = N.lib().sz_compact_searching(self._e, _ptr(self.planes), C.byref(n), self._stream())
+        if rc == N.SZ_ERR_STATE:
+            return 0
+        N.check(rc, "sz_compact_searching")
+        self.n_rows, self._restore = int(n.value), True
+        return self.n_rows
+
+    def compact_searching(self):
+        """In the middle of a search (between begin() and its last step): shrink the network batch to the boards that still search
+        (sz_compact_searching); their pending network inputs move to rows 0..n_live*leaves_per_step-1 of self.planes.  Returns n_live.
+        search() puts the caller's mapping (compact() on or off) back before the next search."""
+        n = self._compact_searching()
+        if n == 0:
+            raise N.NativeError(N.SZ_ERR_STATE, "sz_compact_searching")
+        return n
 
     def evaluate(self, planes):
         """model(x, inference=True) -> (policy probabilities [B,4672] f32, value [B] f32)"""
@@ -141,6 +233,8 @@ class SelfPlayEngine:
         N.check(N.lib().sz_set_root_noise(self._e, _ptr(self._gamma)), "sz_set_root_noise")
 
     def begin(self):
+        if self._restore:               # the last search shrank the batch: back to the mapping the caller chose (synchronises, like compact())
+            self.compact(self._compact_on)
         if self.root_alpha is not None:
             alpha = torch.full((self.B, N.SZ_MAX_MOVES), float(self.root_alpha), device=self.device)
             self.set_root_noise(torch._standard_gamma(alpha))
@@ -160,16 +254,18 @@ class SelfPlayEngine:
         """All num_searches simulations for every active board (mcts.py:49-109).  The network sees n_rows * leaves_per_step rows."""
         ev = evaluator or self.evaluate
         self.begin()
-        self.last_steps = 0
+        self.last_steps = self.last_rows = 0
         if self.n_rows <= 0:
             return
+        if self.budgets is not None:
+            return self._search_budgeted(ev)
         rows = self.n_rows * self.L
         planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
         if self.L == 1:
             for _ in range(self.S):
                 policy, value = ev(planes)
                 self.step(policy, value)
-            self.last_steps = self.S
+            self.last_steps, self.last_rows = self.S, self.S * rows
             return
         # leaf batching: a collision ends a board's gather early, so the number of steps depends on the trees (at most S): ceil(S/L) steps
         # without a host sync, then one step at a time until no board waits for the network
@@ -179,7 +275,34 @@ class SelfPlayEngine:
                 policy, value = ev(planes)
                 self.step(policy, value)
             self.last_steps += n
+            self.last_rows += n * rows
             n = 1 if self.last_steps < self.S and self.pending_boards() else 0
+
+    def _search_budgeted(self, ev):
+        """search() with budgets set: the steps run in segments that end where boards run out of budget (search_segments), and after
+        each segment the batch shrinks to the boards that still search.  With max_shrinks > 0 the batch is also shrunk once right after
+        the roots were made: boards with budget 0 and terminal roots never take a row."""
+        segs = search_segments(self.budgets, self.L, self.max_shrinks, self.S)
+        if self.max_shrinks > 0 and self._compact_searching() == 0:
+            return                                          # nothing to search: every board was done at begin
+        for i, n in enumerate(segs):
+            rows = self.n_rows * self.L
+            planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
+            for _ in range(n):
+                policy, value = ev(planes)
+                self.step(policy, value)
+            self.last_steps += n
+            self.last_rows += n * rows
+            if i + 1 < len(segs) and self._compact_searching() == 0:
+                return
+        if self.L > 1:                                      # collisions: one step at a time until no board waits for the network
+            rows = self.n_rows * self.L
+            planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
+            while self.last_steps < self.S and self.pending_boards():
+                policy, value = ev(planes)
+                self.step(policy, value)
+                self.last_steps += 1
+                self.last_rows += rows
 
     def stats(self):
         st = N.sz_stats()

@@ -52,8 +52,26 @@ def _moves_for_record(action_idx, colour_white, packed_root):
     return moves
 
 
+def playout_cap_of(args):
+    """args["playout_cap"] = {"fast": n_fast, "p_full": p} checked against args["num_searches"]: (n_fast, p), or None when the option is off"""
+    cap = args.get("playout_cap")
+    if cap is None:
+        return None
+    full = int(args["num_searches"])
+    if not isinstance(cap, dict) or set(cap) != {"fast", "p_full"}:
+        raise ValueError("args['playout_cap'] must be {'fast': n_fast, 'p_full': p}, got %r" % (cap,))
+    fast, p = cap["fast"], cap["p_full"]
+    if isinstance(fast, bool) or not isinstance(fast, (int, np.integer)) or not 2 <= fast <= full:
+        raise ValueError("args['playout_cap']['fast'] must be an integer in 2..num_searches (%d), got %r" % (full, fast))
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= p <= 1.0:       # NaN fails both comparisons
+        raise ValueError("args['playout_cap']['p_full'] must be a probability in [0, 1], got %r" % (p,))
+    if args.get("reuse_subtree", False):
+        raise ValueError("args['playout_cap'] and args['reuse_subtree'] exclude each other (sz_set_search_budgets)")
+    return int(fast), float(p)
+
+
 def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, learning=True, planes_dtype=None, max_plies=100000,
-               verbose=False, n_boards=None, compact=True, stats=None):
+               verbose=False, n_boards=None, compact=True, stats=None, full_search=None):
     """Plays n_games games to the end and returns a list of per-game history dicts (sim.py:38-43 layout), game g at index g.
 
     The games run concurrently on `n_boards` board slots of one engine (default: one slot per game).  A slot whose game ends is
@@ -69,9 +87,22 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
       for every running game in game order (n_games == 1 reproduces the reference's stream; for several concurrent games the order of
       the draws necessarily differs from the reference's one-game-after-another order — generate_training_data(rng_order="reference")).
     max_plies: a game still running after that many plies is cut (result None, rewards 0); one number or one per game.
-    stats: optional dict, receives 'sims', 'nn_rows', 'plies' (work done; nn_rows = network rows evaluated) and 'host_seconds' (the host's wall time per phase
-      of the ply loop: enqueue_search returns before the GPU is done, wait_search is the wait for it)."""
+    stats: optional dict, receives 'sims', 'nn_rows', 'plies' (work done; nn_rows = network rows evaluated), 'full_plies' / 'fast_plies' (game plies searched with
+      the full / the fast budget) and 'host_seconds' (the host's wall time per phase of the ply loop: enqueue_search returns before the GPU is done,
+      wait_search is the wait for it).
+
+    NON-REFERENCE option, off by default (the reference searches every ply with args['num_searches'] and records every ply, sim.py:46-76):
+    args["playout_cap"] = {"fast": n_fast, "p_full": p}, playout-cap randomisation (KataGo).  Per ply every running game is searched with the
+    full budget args["num_searches"] with probability p, else with n_fast simulations (2 <= n_fast <= num_searches); every ply is played, but ONLY
+    full-search plies become training samples (states / actions / colours / packed_states); the game dict's 'sample_plies' lists the ply of
+    each sample and 'rewards' takes its sign from that ply.  The batch shrinks to the full-search boards once the fast ones are done
+    (SelfPlayEngine.search).  Noise and temperature are the same on fast and full plies (`learning` is per engine).
+    full_search(game, ply) -> bool: the full / fast decision, like `uniforms`.  Default: a numpy Generator of its own, drawn per ply for every
+      running game in game order — never the global numpy or `random` state, whose draw order the callers above depend on."""
     import random
+    pcap = playout_cap_of(args)                             # validated before anything is created
+    if full_search is not None and pcap is None:
+        raise ValueError("full_search needs args['playout_cap']")
     if not torch.cuda.is_available():
         raise RuntimeError("self-play needs an MI355X (HIP) device: the search has no CPU fallback")
     dev = model_device(model)                               # the model's own GPU (a rank with local_rank > 0 plays on ITS device)
@@ -91,11 +122,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     B = max(1, min(int(n_games), int(n_boards) if n_boards else int(n_games)))
     S = int(args["num_searches"])
     eng = SelfPlayEngine(model, args, B, chess960=c960, learning=learning, planes_dtype=planes_dtype, device=dev)
-    games = [dict(states=[], actions=[], rewards=[], colours=[], result=None, packed_states=[]) for _ in range(n_games)]   # packed_states: the (119,8) uint8 form (train_RL.py:42)
+    games = [dict(states=[], actions=[], rewards=[], colours=[], result=None, packed_states=[], sample_plies=[], chosen_actions=[]) for _ in range(n_games)]   # packed_states: the (119,8) uint8 form (train_RL.py:42)
+    cap_rng = np.random.default_rng() if pcap is not None and full_search is None else None
     slot_game = np.full(B, -1, dtype=np.int64)            # game running on each board slot, -1 = none
     plies = np.zeros(n_games, dtype=np.int64)             # plies played so far per game
     next_game = 0
-    work = dict(sims=0, nn_rows=0, plies=0)
+    work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0)
 
     def refill(slots):
         """start the next waiting games on these slots (ChessTensor.__init__/start_board for each); the rest go dark"""
@@ -112,9 +144,15 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             eng.new_games(sch, act)
         eng.set_active((slot_game >= 0).astype(np.uint8))
 
-    def absorb(rec, game_of_slot):
+    def absorb(rec, game_of_slot, sampled, ply_of_slot):
         """host-side bookkeeping of one ply's records (sim.py:71-73); runs while the GPU searches the next ply"""
         slots = np.nonzero((game_of_slot >= 0) & rec["active"].astype(bool))[0]
+        for s_ in slots.tolist():                          # the move played, sample or not: chosen_actions has one action index per ply of the game
+            games[int(game_of_slot[s_])]["chosen_actions"].append(int(rec["chosen"][s_]))
+        for s_ in slots[~sampled[slots]].tolist():         # playout cap: a fast-search ply leaves no sample, only the game's outcome
+            if rec["game_over"][s_]:
+                games[int(game_of_slot[s_])]["result"] = {1: "1-0", -1: "0-1", 0: "1/2-1/2"}[int(rec["result"][s_])]
+        slots = slots[sampled[slots]]
         if not len(slots):
             return
         states = torch.from_numpy(unpack_planes(rec["packed"][slots]))          # one unpack for the whole ply; a game's state is a view of it
@@ -128,6 +166,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             games[g]["packed_states"].append(rec["packed"][s_])
             games[g]["actions"].append(dict(zip(moves, (vis / int(vis.sum())).tolist())))      # int / int in float64: the reference's v / sum_values
             games[g]["colours"].append(white)
+            games[g]["sample_plies"].append(int(ply_of_slot[s_]))
             if rec["game_over"][s_]:
                 games[g]["result"] = {1: "1-0", -1: "0-1", 0: "1/2-1/2"}[int(rec["result"][s_])]
 
@@ -143,6 +182,13 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         t0 = time.perf_counter()
         n_rows = eng.compact() if compact else B
         t0 = lap("compact", t0)
+        running = np.nonzero(slot_game >= 0)[0]
+        sampled = np.ones(B, dtype=bool)                   # boards whose ply becomes a training sample: all of them unless playout_cap
+        if pcap is not None:
+            for s_ in running[np.argsort(slot_game[running], kind="stable")]:      # decisions in game order
+                g = int(slot_game[s_])
+                sampled[s_] = bool(full_search(g, int(plies[g]))) if full_search is not None else bool(cap_rng.random() < pcap[1])
+            eng.set_budgets(np.where(sampled, S, pcap[0]))
         eng.search()                                       # enqueues num_searches x (network + tree step); returns before the GPU is done
         t0 = lap("enqueue_search", t0)
         if pending is not None:
@@ -152,7 +198,6 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         eng.check_errors()
         t0 = lap("wait_search", t0)
         u = np.zeros(B, dtype=np.float64)
-        running = np.nonzero(slot_game >= 0)[0]
         for s_ in running[np.argsort(slot_game[running], kind="stable")]:      # draws in game order
             g = int(slot_game[s_])
             u[s_] = uniforms(g, int(plies[g])) if uniforms is not None else np.random.random_sample()
@@ -161,8 +206,11 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         if eng.stats()["boards_error"]:
             eng.check_errors()
         t0 = lap("play_fetch", t0)
-        pending = (rec, slot_game.copy())
-        work["sims"] += S * len(running); work["nn_rows"] += eng.last_steps * n_rows * eng.L; work["plies"] += 1
+        ply_of_slot = np.where(slot_game >= 0, plies[np.maximum(slot_game, 0)], -1)
+        pending = (rec, slot_game.copy(), sampled, ply_of_slot)
+        n_full = int(sampled[running].sum())
+        work["sims"] += S * n_full + (pcap[0] if pcap is not None else 0) * (len(running) - n_full); work["nn_rows"] += eng.last_rows; work["plies"] += 1
+        work["full_plies"] += n_full; work["fast_plies"] += len(running) - n_full
         plies[slot_game[running]] += 1
         done = [int(s_) for s_ in running if (rec["game_over"][s_] and rec["active"][s_]) or plies[slot_game[s_]] >= cap[slot_game[s_]]]
         if done:
@@ -174,7 +222,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         absorb(*pending)
     for g in range(n_games):
         reward = {"1-0": 1, "0-1": -1}.get(games[g]["result"], 0)
-        games[g]["rewards"] = [reward if i % 2 == 0 else -reward for i in range(len(games[g]["actions"]))]   # sim.py:94-97
+        games[g]["rewards"] = [reward if ply % 2 == 0 else -reward for ply in games[g]["sample_plies"]]   # sim.py:94-97: the sign alternates with the ply the sample was taken at
     eng.close()
     if stats is not None:
         stats.update(work)

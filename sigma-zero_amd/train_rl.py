@@ -369,7 +369,8 @@ def load_cycle(model, optimiser, cycle, out_dir="saves", device=None):
     return True
 
 
-def run_cycle(model, optimiser, lr_scheduler, args, n_games, chess960=True, sync=None, batch_size=128, total_steps=6, fast_inference=True, train_convs="split", train_graph=False):
+def run_cycle(model, optimiser, lr_scheduler, args, n_games, chess960=True, sync=None, batch_size=128, total_steps=6, fast_inference=True, train_convs="split", train_graph=False,
+              selfplay_stats=None):
     """One epoch of train_RL.main (:205-264) on this rank: self-play n_games on this GPU, then 7 passes of training.
     fast_inference — the self-play network, fastest first (measured on MI355X at 4096 boards x 800 searches; fidelity = the same 64 positions
     searched with the fp32 module, tests/test_gpu_train_and_precision.py):
@@ -394,7 +395,7 @@ def run_cycle(model, optimiser, lr_scheduler, args, n_games, chess960=True, sync
         player = FastPolicyNet(model, device=device, operands="fp16")
     else:
         raise ValueError("fast_inference: %r" % (fast_inference,))
-    games = play_games(player, args, n_games, c960=chess960, max_plies=args.get("max_plies", 100000))
+    games = play_games(player, args, n_games, c960=chess960, max_plies=args.get("max_plies", 100000), stats=selfplay_stats)
     packed, aidx, aprob, rew = records_from_games(games)
     dl = DeviceBatches(packed, aidx, aprob, rew, batch_size=batch_size, device=device, shuffle=True)       # same batches as DataLoader + collate
     return train(model, dl, optimiser, total_steps=total_steps, lr_scheduler=lr_scheduler, sync=sync, device=device,
@@ -492,6 +493,10 @@ def main(argv=None):
     ap.add_argument("--leaves-per-step", type=int, default=1,
                     help="NON-REFERENCE: leaves gathered per board per network call, with virtual loss (1 = the reference's search)")
     ap.add_argument("--virtual-loss", type=float, default=1.0, help="virtual loss per descent in flight (with --leaves-per-step > 1)")
+    ap.add_argument("--playout-cap-fast", type=int, default=0,
+                    help="NON-REFERENCE: playout-cap randomisation, simulations of a fast ply (2..--searches); fast plies are played but not trained on (0 = off: "
+                         "every ply gets --searches and becomes a sample, like the reference)")
+    ap.add_argument("--playout-cap-full-prob", type=float, default=0.25, help="probability that a ply gets the full --searches (with --playout-cap-fast)")
     a = ap.parse_args(argv)
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     gpr = [int(x) for x in str(a.games_per_rank).split(",")]
@@ -523,13 +528,16 @@ def main(argv=None):
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
+    if a.playout_cap_fast:
+        args["playout_cap"] = {"fast": a.playout_cap_fast, "p_full": a.playout_cap_full_prob}
     import random
     random.seed(1000 + rank)
     np.random.seed(1000 + rank)
     for epoch in range(start_epoch, start_epoch + a.epochs):
+        sp_stats = {}
         hist, games = run_cycle(model, optimiser, sched, args, a.games_per_rank, chess960=bool(a.chess960), sync=sync,
                                 batch_size=a.batch_size, total_steps=a.total_steps, fast_inference=a.inference, train_convs=a.train_convs,
-                                train_graph=(a.train_graph == "on"))
+                                train_graph=(a.train_graph == "on"), selfplay_stats=sp_stats)
         sync_module_state(model, average_buffers=True) if world > 1 else None
         n_samples = sum(len(g["actions"]) for g in games)
         # games/RL_960_{epoch}.pt (train_RL.py:229-241 merges every worker's games into one file): rank 0 writes its games under the
@@ -546,6 +554,11 @@ def main(argv=None):
             save_cycle(model, optimiser, epoch, a.save_dir)
             if a.log_dir:
                 write_step_log(os.path.join(a.log_dir, "RL_train.jsonl"), epoch, hist, sched)
+                import json
+                with open(os.path.join(a.log_dir, "RL_cycles.jsonl"), "a") as f:        # one record per cycle: what self-play cost and what it yielded (rank 0's share)
+                    f.write(json.dumps({"epoch": epoch, "games": a.games_per_rank, "samples": n_samples, "full_plies": sp_stats.get("full_plies"),
+                                        "fast_plies": sp_stats.get("fast_plies"), "network_rows": sp_stats.get("nn_rows"), "simulations": sp_stats.get("sims"),
+                                        "playout_cap": args.get("playout_cap")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"
                   % (epoch, world, a.games_per_rank, n_samples, len(hist), last[0], last[1]), flush=True)
