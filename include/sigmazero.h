@@ -61,7 +61,15 @@ typedef struct sz_config {
     int32_t reuse_subtree;       /* NON-REFERENCE option, 0 = off (default, the reference builds a fresh tree per ply: sim.py:53).  != 0: sz_play keeps the
                                   * subtree below the move it plays (compacted in place) and the next sz_search_begin continues on it — the new root starts
                                   * with that child's visit count, value sum and children — whenever the kept part is at most num_searches nodes and half
-                                  * of the child slots; otherwise, and after sz_new_games / sz_upload_game, the search starts fresh.  Doubles the stores. */
+                                  * of the child slots; otherwise, and after sz_new_games / sz_upload_game, the search starts fresh.  Doubles the stores.
+                                  * The search starts from a fresh root (visit count 1, no children) exactly when
+                                  *  (1) the chosen child was never visited, or was visited and has no children (then it is a terminal position);
+                                  *  (2) the kept subtree has more than num_searches visited nodes, the new root included;
+                                  *  (3) twice its edge count, the new root's own edge included, exceeds the child slots per board
+                                  *      (edges_per_board, at least 220).
+                                  * A continued search makes num_searches new simulations: it descends first (nothing waits for the network at
+                                  * sz_search_begin's return but the first new leaf), the root keeps the kept visit count and is not expanded again.
+                                  * Held to a re-rooted host search by tests/test_gpu_subtree_reuse.py (tests/reuseref.py). */
 } sz_config;
 
 typedef struct sz_stats {

@@ -7,7 +7,10 @@ modes
   "dyadic"   policy entries k/1024, k in 1..64 (about 1 in 128 exactly 0): every masked sum is exact in fp32 in ANY order, so the
              reference's torch.sum (mcts.py:79) and the engine's fixed-order sum agree bit for bit -> whole trees compare bitwise;
   "rational" policy entries f32(m)/f32(100003), m in 1..9973: sums round, so the summation order matters in the last ulp -> these
-             cases measure the north-star tolerance (visit fractions within 1e-4, move indices exact).
+             cases measure the north-star tolerance (visit fractions within 1e-4, move indices exact);
+  "peaked"   policy entries 4^-k, k in 0..31, and the value divided by 16 (|v| < 1/16): among the legal moves one or two entries carry
+             almost all of the mass and Q hardly differs between children, so the visits of a search run down one line -> the subtree
+             below the move played holds most of the tree (the subtree-reuse tests need kept subtrees larger than num_searches).
 """
 import numpy as np
 import torch
@@ -55,10 +58,14 @@ def evaluate_packed(packed, mode="dyadic", salt=0):
             pol[((h >> np.uint64(40)) & np.uint64(127)) == 0] = np.float32(0.0)
         elif mode == "rational":
             pol = (((h >> np.uint64(40)) % np.uint64(9973)) + np.uint64(1)).astype(np.float32) / np.float32(100003.0)
+        elif mode == "peaked":
+            pol = np.ldexp(np.float32(1.0), -2 * (h >> np.uint64(59)).astype(np.int32)).astype(np.float32)
         else:
             raise ValueError(mode)
         hv = _splitmix(key ^ np.uint64(0xA5A5A5A5DEADBEEF))
         val = np.float32((int(hv >> np.uint64(40)) - (1 << 23))) / np.float32(1 << 23)
+        if mode == "peaked":
+            val = val / np.float32(16.0)
     return pol.astype(np.float32), np.float32(val)
 
 
