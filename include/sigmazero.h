@@ -165,7 +165,8 @@ int sz_set_root_noise(sz_engine* e, const float* gamma_dev);
  * that ends on a leaf already pending in this step (a collision) ends the gather.  A search takes at most num_searches steps
  * and counts the same simulations as at L = 1.  L = 1 is the reference's search, bit for bit (the same kernel).  L > 1 is NOT
  * the reference's search and is not held to its visit counts; its effect on playing strength is unmeasured.
- * SZ_ERR_INVALID: L < 1, L > SZ_MAX_LEAVES_PER_STEP, lambda negative or not finite, or L > 1 on an engine with reuse_subtree.
+ * SZ_ERR_INVALID: L < 1, L > SZ_MAX_LEAVES_PER_STEP, lambda negative or not finite, or L > 1 on an engine with reuse_subtree or while the
+ * solver is on (sz_set_solver).
  * The buffers (in-flight counts, L paths and legal masks per board) are allocated by the first call with L > 1. */
 #define SZ_MAX_LEAVES_PER_STEP 256
 int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream);
@@ -193,6 +194,46 @@ int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream);
  * (enable 1 or 0) before the next sz_search_begin, a board without a row is flagged SZ_ERR_STATE there.  Results per board do not depend
  * on the mapping.  Synchronises the stream to return n_live. */
 int sz_compact_searching(sz_engine* e, void* planes_dev, int32_t* n_live_out, void* stream);
+
+/* NON-REFERENCE option, off by default: proven-result propagation (MCTS-Solver; lc0's "certainty propagation").  The reference backs a
+ * checkmate leaf up as one more sample of -1; with enable != 0 the search also carries what is PROVEN up the tree.  Off, every kernel that
+ * runs today runs unchanged (the solver is a template instantiation of its own, like leaf batching).
+ * State: every node e has R(e) in {unknown, WIN, DRAW, LOSS}, from the view of the side to move in e's position (the convention of the
+ * terminal value), and one bit complete(e), set at expansion when the number of children created equals the number of legal moves
+ * (expansion drops moves whose renormalised prior is exactly 0; a node that lost a move that way is never proven LOSS or DRAW).  Both live
+ * in 16 spare bits of the edge record: no new memory per edge.  Rules, per board:
+ *   terminal leaf  when a leaf's position is created and found terminal: R = LOSS if the side to move is mated, DRAW otherwise.
+ *   update         after every backup, walk the backed-up path from its last node towards the root.  The parent p of a node whose R has
+ *                  just become proven is recomputed from p's children alone (one wavefront, lanes = children): WIN if any child is LOSS;
+ *                  otherwise, if complete(p) and every child is proven, DRAW if any child is DRAW, else LOSS; otherwise unknown.  The walk
+ *                  stops at the first node whose R does not change.  R never goes back to unknown.
+ *   descent        a descent stops at the first node on its way whose R is proven, the root included.  The simulation ends there: it is
+ *                  backed up along the path to that node with -1 / 0 / +1 for LOSS / DRAW / WIN (the usual sign alternation), and counted
+ *                  as a simulation and as a terminal_hit at that node's depth (sz_stats); selection repeats within the same step, as it
+ *                  does for terminal leaves.  With a proven root all remaining simulations of the board end at the root in one step.
+ *   selection      at an unknown node the arg-max runs over the children with R != WIN (a child whose side to move wins is a refuted
+ *                  move); Node.get_ucb, its operation order and the first-maximum tie-break are unchanged.  If every child is WIN (possible
+ *                  only when complete is 0) it runs over all children.
+ *   sz_play        on a board whose root is WIN the move played and recorded as `chosen` is the first root child in action order with
+ *                  R == LOSS, whatever the uniform; the recorded action / visits stay what the search counted.  A root that is LOSS,
+ *                  DRAW or unknown is played as without the solver.
+ * NO mate distance is kept: a won position is won by the first proving move in action order, which may not be the shortest mate.
+ * Only between searches (SZ_ERR_STATE otherwise, the rule of sz_set_leaf_batching).  SZ_ERR_INVALID when enabling on an engine created
+ * with reuse_subtree or while leaves_per_step > 1; sz_set_leaf_batching with leaves_per_step > 1 is refused (SZ_ERR_INVALID) while the
+ * solver is on.  Both combinations are follow-ups, not supported.  Works with sz_set_search_budgets (a board whose root is proven early
+ * keeps searching until its budget is counted out), sz_compact, sz_compact_searching and sz_set_root_noise.  Held bit for bit to the host
+ * restatement tests/solverref.py by tests/test_gpu_solver.py.  Its effect on playing strength is unmeasured. */
+int sz_set_solver(sz_engine* e, int32_t enable, void* stream);
+/* proven results after (or during) a search, device pointers: root_dev [n_boards] int8, child_dev [n_boards,218] int8 in action order, as
+ * sz_root_children.  Codes: 0 unknown, 1 WIN, 2 DRAW, 3 LOSS, each for the side to move in that node's own position (a root child
+ * with 3 is a move that wins for the root).  All 0 without the solver. */
+int sz_root_proven(sz_engine* e, int8_t* root_dev, int8_t* child_dev, void* stream);
+/* test / inspection: proven code and complete bit of every node of one board's tree, rows in sz_debug_tree's order (host arrays of
+ * max_nodes entries, may be NULL to count) */
+int sz_debug_tree_proven(sz_engine* e, int32_t board, int32_t max_nodes, int8_t* proven, uint8_t* complete, int32_t* n_out, void* stream);
+/* solver counters, all boards, cumulative since the solver was first switched on (synchronises): out[0] simulations that ended on a proven
+ * NON-terminal node, out[1] nodes proven by the update rule (terminal leaves not counted).  sz_stats is unchanged. */
+int sz_solver_stats(sz_engine* e, uint64_t out[2], void* stream);
 
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */

@@ -14,6 +14,7 @@ SZ_NN_SPLIT_WGB1, SZ_NN_SPLIT_WGB2 = 0x2000000, 0x4000000
 SZ_NN_F16 = 0x8000000
 SZ_NN_TOWER_WGB1, SZ_NN_TOWER_WGB2 = 0x10000000, 0x20000000
 SZ_MAX_LEAVES_PER_STEP = 256
+SZ_PROVEN_UNKNOWN, SZ_PROVEN_WIN, SZ_PROVEN_DRAW, SZ_PROVEN_LOSS = 0, 1, 2, 3      # codes of sz_root_proven / sz_debug_tree_proven
 
 
 class sz_config(C.Structure):
@@ -47,6 +48,10 @@ EXPORTS = {
     "sz_search_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sz_set_leaf_batching": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "sz_pending_boards": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_set_solver": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "sz_root_proven": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sz_debug_tree_proven": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_solver_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_get_stats": (C.c_int, [C.c_void_p, C.POINTER(sz_stats), C.c_void_p]),

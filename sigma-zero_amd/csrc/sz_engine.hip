@@ -39,6 +39,10 @@
 struct alignas(16) EdgeStat { double W; int N; float P; };
 struct alignas(16) EdgeMeta { int first; int node; unsigned short n; unsigned short action; signed char term; signed char tval; unsigned short pad; };
 
+// NON-REFERENCE option (sz_set_solver): EdgeMeta.pad holds the proven result R of the edge's node for the side to move there (bits 0-1, the
+// codes of sz_root_proven) and `complete` (bit 2: expansion kept every legal move as a child).  Zero when the option is off.
+enum { PR_UNKNOWN = 0, PR_WIN = 1, PR_DRAW = 2, PR_LOSS = 3, PR_MASK = 3, PR_COMPLETE = 4 };
+
 enum { ST_ACTIVE = 1, ST_PENDING = 2, ST_DONE = 4, ST_GAMEOVER = 8, ST_ERROR = 16, ST_SEARCHING = 32 };
 
 struct alignas(16) Ctl {
@@ -57,6 +61,7 @@ struct View {
     const int* slot;            // optional (sz_compact): row of board b in the network batch (planes / policy / value); NULL = identity
     const float* root_gamma;    // optional (non-reference) true Dirichlet root noise: [B][SZ_MAX_MOVES] Gamma(alpha,1) draws; NULL = reference behaviour
     const int* budget;          // optional (non-reference, sz_set_search_budgets): simulations of board b in 0..S; NULL = S everywhere (S stays the capacity)
+    unsigned long long* sstat;  // solver only (sz_set_solver): [B][2] simulations ended on a proven non-terminal node, nodes proven by the update rule
     SzPos* npos; SzPos* ring; EdgeStat* es; EdgeMeta* em; int* gpath; u64* pmask; Ctl* ctl;
     // per-ply training record
     uint8_t* rec_planes; int* rec_action; int* rec_visits; int* rec_nchild; uint8_t* rec_colour; int* rec_chosen;
@@ -154,6 +159,52 @@ __device__ __forceinline__ int wave_select_child_vl(const EdgeStat* ch, const in
         if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
     }
     return uni(bi);
+}
+
+// the same with proven results (sz_set_solver): the arg-max runs over the children that are not proven WIN (a child whose side to move wins
+// is a refuted move); over all of them when every child is WIN.  ucb_value, its operation order and the tie-break are wave_select_child's.
+__device__ __forceinline__ int wave_select_child_solver(const EdgeStat* ch, const EdgeMeta* cm, int n, int parentN, float c_puct) {
+    const int lane = lane_id();
+    const float sq = (float)sqrt((double)parentN);
+    bool open = false;
+    for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
+    const bool skip_wins = __ballot(open) != 0;
+    float best = 0.f; int bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) {
+        if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue;
+        EdgeStat s = ch[c];
+        float u = ucb_value(s.N, s.W, s.P, sq, c_puct);
+        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+    }
+    return uni(bi);
+}
+
+// solver update after a backup whose last node path[d] has just become proven: walk towards the root; the parent of a newly proven node is
+// recomputed from its children alone (lanes = children): WIN if any child is LOSS, else, when it is complete and every child is proven,
+// DRAW if any child is DRAW, else LOSS.  The walk ends at the first node that stays UNKNOWN.  Returns the number of nodes proven.
+__device__ __forceinline__ int wave_solver_update(EdgeMeta* em, const int* path, int d) {
+    const int lane = lane_id();
+    int proved = 0;
+    for (int j = d; j > 0; j--) {
+        const int p = path[j - 1];
+        const EdgeMeta pm = em[p];
+        const int first = uni(pm.first), n = uni((int)pm.n), ppad = uni((int)pm.pad);
+        bool loss = false, draw = false, open = false;
+        for (int c = lane; c < n; c += 64) {
+            const int r = em[first + c].pad & PR_MASK;
+            loss |= r == PR_LOSS; draw |= r == PR_DRAW; open |= r == PR_UNKNOWN;
+        }
+        const int r = __ballot(loss) ? PR_WIN : (((ppad & PR_COMPLETE) && !__ballot(open)) ? (__ballot(draw) ? PR_DRAW : PR_LOSS) : PR_UNKNOWN);
+        if (r == (ppad & PR_MASK)) break;
+        if (lane == 0) em[p].pad = (unsigned short)((ppad & ~PR_MASK) | r);
+        __threadfence_block();
+        proved++;
+    }
+    return proved;
 }
 
 struct BoardPtrs {
@@ -445,7 +496,8 @@ __global__ void k_after_upload(View v, int b, int ply) {
 // kernel: search begin — create roots (mcts.py:43-46), root movegen + terminal test, encode root planes
 // ------------------------------------------------------------------------------------------------
 // VL: leaf batching on (sz_set_leaf_batching): the root is pending leaf 0, its network input goes to row slot(b)*L
-template <bool VL>
+// SOLVE: proven results on (sz_set_solver): a terminal root is labelled like any terminal position
+template <bool VL, bool SOLVE>
 __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb) {
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
@@ -487,6 +539,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
         bp.es[0] = s;
         EdgeMeta m; m.first = -1; m.node = 0; m.n = 0; m.action = 0; m.term = (signed char)szm_term(X.meta);
         m.tval = (signed char)(szm_loss(X.meta) ? -1 : 0); m.pad = 0;
+        if constexpr (SOLVE) { if (szm_term(X.meta)) m.pad = szm_loss(X.meta) ? PR_LOSS : PR_DRAW; }
         bp.em[0] = m;
         bp.gpath[0] = 0;
     }
@@ -536,7 +589,8 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // VL = false: the reference's search, one leaf per board per step.  VL = true (sz_set_leaf_batching): every pending leaf is expanded and
 // backed up in gather order (its k taken back along its path), then descents with virtual loss gather up to L new leaves; a terminal leaf
 // is backed up on the spot, a descent that ends on a leaf already pending in this step (a collision) ends the gather.
-template <bool VL>
+// SOLVE = true (sz_set_solver, VL = false only): proven results are carried up the tree; a descent ends at the first proven node on its way.
+template <bool VL, bool SOLVE>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb) {
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
@@ -550,7 +604,9 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     const int row = v.slot ? uni(v.slot[b]) : b;              // network batch row of this board
     if (row < 0) return;
     if ((status & ST_PENDING) && !policy) return;             // descent-only launch (sz_search_begin with reuse): boards that already wait for the network sit it out
+    static_assert(!(VL && SOLVE), "the solver is not combined with leaf batching");
     unsigned long long n_expand = 0, n_term = 0, sum_depth = 0, sum_k = 0;
+    unsigned long long n_stop = 0, n_proved = 0;                // solver: simulations ended on a proven non-terminal node, nodes proven by the update
     int err = 0;
     STEP_STAMP(0);
 
@@ -643,7 +699,10 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
                 gs = wave_sum_butterfly(gs);
                 for (int c = lane; c < kept; c += 64) bp.es[first + c].P = (0.75f * bp.es[first + c].P) + (0.25f * (g[c] / gs));
             }
-            if (lane == 0) { bp.em[leaf_edge].first = first; bp.em[leaf_edge].n = (unsigned short)kept; }
+            if (lane == 0) {
+                bp.em[leaf_edge].first = first; bp.em[leaf_edge].n = (unsigned short)kept;
+                if constexpr (SOLVE) { if (!err && kept == n_moves) bp.em[leaf_edge].pad |= PR_COMPLETE; }     // no move was dropped for a zero prior
+            }
             n_edges += kept;
             (void)node;
         const double val = (double)value[prow];                         // node.value = value.item()
@@ -670,8 +729,11 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         int parentN = bp.es[0].N;
         if constexpr (VL) parentN += vk[0];
         m.first = uni(m.first); int mn = uni((int)m.n); parentN = uni(parentN);
-        while (mn > 0) {                                                // Node.select
-            int bi = VL ? wave_select_child_vl(bp.es + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam)
+        int proven = PR_UNKNOWN;                                        // solver: result of the first proven node on the way, the root included
+        if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
+        while (mn > 0 && !proven) {                                     // Node.select
+            int bi = SOLVE ? wave_select_child_solver(bp.es + m.first, bp.em + m.first, mn, parentN, v.c_puct)
+                   : VL ? wave_select_child_vl(bp.es + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam)
                         : wave_select_child(bp.es + m.first, mn, parentN, v.c_puct, nullptr);
             cur = m.first + bi;
             d++;
@@ -680,9 +742,18 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             m = bp.em[cur];
             parentN = uni(bp.es[cur].N + (VL ? vk[cur] : 0));
             m.first = uni(m.first); mn = uni((int)m.n);
+            if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
         }
         if (err) break;
         STEP_STAMP(2);
+        if constexpr (SOLVE) {
+            if (proven) {                                               // the simulation ends here with the proven value (terminal leaves included)
+                wave_backprop(bp.es, path, d, proven == PR_WIN ? 1.0 : (proven == PR_DRAW ? 0.0 : -1.0));
+                sims++; n_term++; sum_depth += d;
+                if (!uni((int)m.term)) n_stop++;
+                continue;
+            }
+        }
         int node = uni(m.node);
         if (node >= 0) {
             if (VL && !uni((int)m.term) && m.first < 0) break;          // batched: a collision with a leaf pending in this step ends the gather
@@ -704,12 +775,14 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             bp.npos[nid] = X;
             EdgeMeta* em = bp.em + cur;
             em->node = nid; em->term = (signed char)is_term; em->tval = (signed char)(szm_loss(X.meta) ? -1 : 0);
+            if constexpr (SOLVE) { if (is_term) em->pad = szm_loss(X.meta) ? PR_LOSS : PR_DRAW; }
         }
         __threadfence_block();
         if (is_term) {                                                  // get_value_and_terminated -> (0|-1, True)
             double tv = szm_loss(X.meta) ? -1.0 : 0.0;
             wave_backprop(bp.es, path, d, tv);
             sims++; n_term++; sum_depth += d;
+            if constexpr (SOLVE) n_proved += wave_solver_update(bp.em, path, d);
             continue;
         }
         // non-terminal leaf: hand it to the network
@@ -748,6 +821,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if (n_edges > c->max_edges) c->max_edges = n_edges;
         if (err && !c->err) c->err = err;
         if constexpr (VL) c->n_pend = n_pend;
+        if constexpr (SOLVE) { v.sstat[(size_t)b * 2] += n_stop; v.sstat[(size_t)b * 2 + 1] += n_proved; }
     }
 }
 
@@ -788,9 +862,22 @@ __global__ __launch_bounds__(64) void k_root_children(View v, int* action, int* 
     }
 }
 
+// proven results of the root and of its children in action order (sz_root_proven); all 0 on a board that has no search or no solver
+__global__ __launch_bounds__(64) void k_root_proven(View v, int8_t* root, int8_t* child) {
+    const int b = blockIdx.x, lane = lane_id();
+    BoardPtrs bp = board_ptrs(v, b);
+    int n = 0, first = 0, r = 0;
+    if (bp.ctl->status & ST_SEARCHING) { EdgeMeta m = bp.em[0]; n = m.n; first = m.first; r = m.pad & PR_MASK; }
+    if (lane == 0) root[b] = (int8_t)r;
+    for (int c = lane; c < SZ_MAX_CHILDREN; c += 64)
+        child[(size_t)b * SZ_MAX_CHILDREN + c] = (int8_t)(c < n ? (bp.em[first + c].pad & PR_MASK) : 0);
+}
+
 // ------------------------------------------------------------------------------------------------
 // kernel: sample + play (sim.py:63-76) and game-over test (sim.py:46, 86-97)
 // ------------------------------------------------------------------------------------------------
+// SOLVE (sz_set_solver): on a root proven WIN the move played is the first child proven LOSS, whatever the uniform
+template <bool SOLVE>
 __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms) {
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
@@ -830,6 +917,10 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms) {
         if (u < 0.0) {                                                  // greedy: max(action_probs, key=...) of eval.py:92-94 — first maximum
             idx = 0;
             for (int c = 1; c < n; c++) if (vis_lds[c] > vis_lds[idx]) idx = c;
+        }
+        if constexpr (SOLVE) {
+            if ((rm.pad & PR_MASK) == PR_WIN)
+                for (int c = 0; c < n; c++) if ((bp.em[first + c].pad & PR_MASK) == PR_LOSS) { idx = c; break; }
         }
         chosen = idx;
     }
@@ -926,6 +1017,8 @@ struct sz_engine {
     Batch vb;                       // sz_set_leaf_batching; vb.L == 1: the reference's search, nothing allocated
     int vb_cap;                     // L the batching buffers were allocated for
     std::vector<void*> vb_allocs;
+    int solver;                     // sz_set_solver: the SOLVE instantiations of begin / step / play run
+    unsigned long long* d_sstat;    // its counters [n_boards][2], allocated by the first enabling call
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
@@ -1172,14 +1265,15 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    if (e->vb.L > 1) hipLaunchKernelGGL(k_search_begin<true>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
-    else hipLaunchKernelGGL(k_search_begin<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
+    if (e->vb.L > 1) hipLaunchKernelGGL((k_search_begin<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
+    else if (e->solver) hipLaunchKernelGGL((k_search_begin<false, true>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
+    else hipLaunchKernelGGL((k_search_begin<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
     HIPCHK(hipGetLastError());
     if (e->v.reuse && planes_dev) {
         // boards that continue on a kept subtree have no root to evaluate: one descent-only launch selects their first leaf (boards whose fresh
         // root waits for the network sit it out), so that every board enters the first network call with a real position
-        hipLaunchKernelGGL(k_search_step<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, (const float*)nullptr, (const float*)nullptr, planes_dev,
-                           Batch{});
+        hipLaunchKernelGGL((k_search_step<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, (const float*)nullptr, (const float*)nullptr,
+                           planes_dev, Batch{});
         HIPCHK(hipGetLastError());
     }
     return SZ_OK;
@@ -1189,9 +1283,11 @@ int sz_search_step(sz_engine* e, const float* policy_dev, const float* value_dev
     if (!e || !policy_dev || !value_dev || !planes_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     if (e->vb.L > 1)
-        hipLaunchKernelGGL(k_search_step<true>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, e->vb);
+        hipLaunchKernelGGL((k_search_step<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, e->vb);
+    else if (e->solver)
+        hipLaunchKernelGGL((k_search_step<false, true>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, Batch{});
     else
-        hipLaunchKernelGGL(k_search_step<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, Batch{});
+        hipLaunchKernelGGL((k_search_step<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, Batch{});
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
@@ -1199,6 +1295,7 @@ int sz_search_step(sz_engine* e, const float* policy_dev, const float* value_dev
 int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream) {
     if (!e || leaves_per_step < 1 || leaves_per_step > SZ_MAX_LEAVES_PER_STEP || !(virtual_loss >= 0.0f) || !std::isfinite(virtual_loss)) return SZ_ERR_INVALID;
     if (leaves_per_step > 1 && e->v.reuse) return SZ_ERR_INVALID;          // combining the two non-reference options is not supported
+    if (leaves_per_step > 1 && e->solver) return SZ_ERR_INVALID;           // nor leaf batching with the solver
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
     std::vector<Ctl> h(e->v.B);
@@ -1227,6 +1324,46 @@ int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_lo
     }
     e->vb.L = leaves_per_step;
     e->vb.lam = virtual_loss;
+    return SZ_OK;
+}
+
+int sz_set_solver(sz_engine* e, int32_t enable, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (enable && (e->v.reuse || e->vb.L > 1)) return SZ_ERR_INVALID;      // not combined with subtree reuse or leaf batching
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if (enable && !e->d_sstat) {
+        if ((rc = dalloc(e, &e->d_sstat, (size_t)e->v.B * 2))) return rc;
+        HIPCHK(hipMemsetAsync(e->d_sstat, 0, (size_t)e->v.B * 2 * sizeof(unsigned long long), s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    e->solver = enable ? 1 : 0;
+    e->v.sstat = enable ? e->d_sstat : nullptr;
+    return SZ_OK;
+}
+
+int sz_root_proven(sz_engine* e, int8_t* root_dev, int8_t* child_dev, void* stream) {
+    if (!e || !root_dev || !child_dev) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipLaunchKernelGGL(k_root_proven, dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, root_dev, child_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_solver_stats(sz_engine* e, uint64_t out[2], void* stream) {
+    if (!e || !out) return SZ_ERR_INVALID;
+    out[0] = out[1] = 0;
+    if (!e->d_sstat) return SZ_OK;                                          // the solver was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<unsigned long long> h((size_t)e->v.B * 2);
+    HIPCHK(hipMemcpyAsync(h.data(), e->d_sstat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < (size_t)e->v.B; b++) { out[0] += h[2 * b]; out[1] += h[2 * b + 1]; }
     return SZ_OK;
 }
 
@@ -1273,7 +1410,8 @@ int sz_root_children(sz_engine* e, int32_t* action_dev, int32_t* visits_dev, int
 int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    hipLaunchKernelGGL(k_play, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
+    if (e->solver) hipLaunchKernelGGL(k_play<true>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
+    else hipLaunchKernelGGL(k_play<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
@@ -1357,6 +1495,32 @@ int sz_debug_tree(sz_engine* e, int32_t board, int32_t max_nodes, int32_t* depth
         if (n < max_nodes && depth) { depth[n] = d; action[n] = em[ed].action; visits[n] = es[ed].N; value_sum[n] = es[ed].W; prior[n] = es[ed].P; }
         n++;
         if (em[ed].first >= 0) for (int k = (int)em[ed].n - 1; k >= 0; k--) stack.push_back({em[ed].first + k, d + 1});
+    }
+    *n_out = n;
+    return SZ_OK;
+}
+
+int sz_debug_tree_proven(sz_engine* e, int32_t board, int32_t max_nodes, int8_t* proven, uint8_t* complete, int32_t* n_out, void* stream) {
+    if (!e || board < 0 || board >= e->v.B || !n_out) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    Ctl c;
+    HIPCHK(hipMemcpyAsync(&c, e->v.ctl + board, sizeof c, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n_out = 0;
+    if (!(c.status & ST_SEARCHING) || c.n_edges <= 0) return SZ_OK;
+    std::vector<EdgeMeta> em(c.n_edges);
+    HIPCHK(hipMemcpyAsync(em.data(), e->v.em + (size_t)board * e->v.e_cap, em.size() * sizeof(EdgeMeta), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<int> stack;                                 // the walk of sz_debug_tree
+    int n = 0;
+    stack.push_back(0);
+    while (!stack.empty()) {
+        const int ed = stack.back(); stack.pop_back();
+        if (n < max_nodes && proven) proven[n] = (int8_t)(em[ed].pad & PR_MASK);
+        if (n < max_nodes && complete) complete[n] = (uint8_t)((em[ed].pad & PR_COMPLETE) ? 1 : 0);
+        n++;
+        if (em[ed].first >= 0) for (int k = (int)em[ed].n - 1; k >= 0; k--) stack.push_back(em[ed].first + k);
     }
     *n_out = n;
     return SZ_OK;

@@ -104,6 +104,16 @@ class SelfPlayEngine:
         if L > 1 and self.args.get("reuse_subtree", False):
             raise ValueError("args['leaves_per_step'] > 1 and args['reuse_subtree'] exclude each other")
         self.L, self.virtual_loss = int(L), float(lam)
+        # NON-REFERENCE option (default off): args["solver"] = True carries proven results (forced wins, draws and losses) up the tree
+        # (sz_set_solver): descents end at proven nodes, refuted moves are not selected, play() takes the proving move of a won root
+        solver = self.args.get("solver", False)
+        if not isinstance(solver, (bool, np.bool_)):
+            raise ValueError("args['solver'] must be True or False, got %r" % (solver,))
+        if solver and self.args.get("reuse_subtree", False):
+            raise ValueError("args['solver'] and args['reuse_subtree'] exclude each other")
+        if solver and L > 1:
+            raise ValueError("args['solver'] and args['leaves_per_step'] > 1 exclude each other")
+        self.solver = bool(solver)
         self.last_steps = 0           # network calls made by the last search()
         self.last_rows = 0            # network rows evaluated by the last search()
         # NON-REFERENCE option (default off): per-board search budgets (set_budgets) with in-search batch shrinking; at most
@@ -135,6 +145,8 @@ class SelfPlayEngine:
             self.planes = torch.zeros(rows, N.SZ_PLANES, 8, 8, dtype=planes_dtype, device=dev)
         if self.L > 1:
             N.check(N.lib().sz_set_leaf_batching(self._e, self.L, self.virtual_loss, self._stream()), "sz_set_leaf_batching")
+        if self.solver:
+            N.check(N.lib().sz_set_solver(self._e, 1, self._stream()), "sz_set_solver")
         self.uniforms = torch.zeros(self.B, dtype=torch.float64, device=dev)
         self.root_action = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
         self.root_visits = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
@@ -322,6 +334,22 @@ class SelfPlayEngine:
         return (self.root_action.cpu().numpy(), self.root_visits.cpu().numpy(), self.root_nchild.cpu().numpy(),
                 self.root_prior.cpu().numpy(), self.root_wsum.cpu().numpy())
 
+    def root_proven(self):
+        """Proven results of the last search (sz_root_proven; all 0 without args["solver"]): (root [B] int8, children [B, SZ_MAX_MOVES] int8
+        in action order as root_children()).  Codes _native.SZ_PROVEN_*: 0 unknown, 1 WIN, 2 DRAW, 3 LOSS, each for the side to move in
+        that node's own position, so a root child with 3 is a winning move for the root."""
+        root = torch.zeros(self.B, dtype=torch.int8, device=self.device)
+        child = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int8, device=self.device)
+        N.check(N.lib().sz_root_proven(self._e, _ptr(root), _ptr(child), self._stream()), "sz_root_proven")
+        torch.cuda.synchronize(self.device)
+        return root.cpu().numpy(), child.cpu().numpy()
+
+    def solver_stats(self):
+        """(simulations that ended on a proven non-terminal node, nodes proven by the update rule), all boards, cumulative (sz_solver_stats)"""
+        out = (C.c_uint64 * 2)()
+        N.check(N.lib().sz_solver_stats(self._e, out, self._stream()), "sz_solver_stats")
+        return int(out[0]), int(out[1])
+
     def play(self, uniforms):
         """sim.py:68-76 for every board: sample with the given uniforms (one per board), play, test game over."""
         self.uniforms.copy_(torch.as_tensor(np.asarray(uniforms, dtype=np.float64)))
@@ -355,6 +383,15 @@ class SelfPlayEngine:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         N.check(N.lib().sz_debug_tree(self._e, int(board), k, p(d), p(a), p(v), p(w), p(pr), C.byref(n), self._stream()), "sz_debug_tree")
         return d, a, v, w, pr
+
+    def debug_tree_proven(self, board):
+        """(proven codes, complete bits) of every node of one board's tree, rows in debug_tree()'s order (sz_debug_tree_proven)"""
+        n = C.c_int32()
+        N.check(N.lib().sz_debug_tree_proven(self._e, int(board), 0, None, None, C.byref(n), self._stream()), "sz_debug_tree_proven")
+        r, c = np.zeros(n.value, np.int8), np.zeros(n.value, np.uint8)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        N.check(N.lib().sz_debug_tree_proven(self._e, int(board), n.value, p(r), p(c), C.byref(n), self._stream()), "sz_debug_tree_proven")
+        return r, c
 
     def debug_position(self, board):
         pos = np.zeros(10, np.uint64)

@@ -493,6 +493,8 @@ def main(argv=None):
     ap.add_argument("--leaves-per-step", type=int, default=1,
                     help="NON-REFERENCE: leaves gathered per board per network call, with virtual loss (1 = the reference's search)")
     ap.add_argument("--virtual-loss", type=float, default=1.0, help="virtual loss per descent in flight (with --leaves-per-step > 1)")
+    ap.add_argument("--solver", action="store_true",
+                    help="NON-REFERENCE: carry proven results (forced wins, draws, losses) up the search tree (sz_set_solver); not with --leaves-per-step > 1")
     ap.add_argument("--playout-cap-fast", type=int, default=0,
                     help="NON-REFERENCE: playout-cap randomisation, simulations of a fast ply (2..--searches); fast plies are played but not trained on (0 = off: "
                          "every ply gets --searches and becomes a sample, like the reference)")
@@ -528,6 +530,8 @@ def main(argv=None):
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
+    if a.solver:
+        args["solver"] = True
     if a.playout_cap_fast:
         args["playout_cap"] = {"fast": a.playout_cap_fast, "p_full": a.playout_cap_full_prob}
     import random
