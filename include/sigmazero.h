@@ -166,7 +166,7 @@ int sz_set_root_noise(sz_engine* e, const float* gamma_dev);
  * and counts the same simulations as at L = 1.  L = 1 is the reference's search, bit for bit (the same kernel).  L > 1 is NOT
  * the reference's search and is not held to its visit counts; its effect on playing strength is unmeasured.
  * SZ_ERR_INVALID: L < 1, L > SZ_MAX_LEAVES_PER_STEP, lambda negative or not finite, or L > 1 on an engine with reuse_subtree or while the
- * solver is on (sz_set_solver).
+ * solver is on (sz_set_solver); those combinations are asked for through sz_set_search_options.
  * The buffers (in-flight counts, L paths and legal masks per board) are allocated by the first call with L > 1. */
 #define SZ_MAX_LEAVES_PER_STEP 256
 int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream);
@@ -220,10 +220,59 @@ int sz_compact_searching(sz_engine* e, void* planes_dev, int32_t* n_live_out, vo
  * NO mate distance is kept: a won position is won by the first proving move in action order, which may not be the shortest mate.
  * Only between searches (SZ_ERR_STATE otherwise, the rule of sz_set_leaf_batching).  SZ_ERR_INVALID when enabling on an engine created
  * with reuse_subtree or while leaves_per_step > 1; sz_set_leaf_batching with leaves_per_step > 1 is refused (SZ_ERR_INVALID) while the
- * solver is on.  Both combinations are follow-ups, not supported.  Works with sz_set_search_budgets (a board whose root is proven early
+ * solver is on.  Both combinations are follow-ups, not supported by this entry point: sz_set_search_options below sets them.  Works with sz_set_search_budgets (a board whose root is proven early
  * keeps searching until its budget is counted out), sz_compact, sz_compact_searching and sz_set_root_noise.  Held bit for bit to the host
  * restatement tests/solverref.py by tests/test_gpu_solver.py.  Its effect on playing strength is unmeasured. */
 int sz_set_solver(sz_engine* e, int32_t enable, void* stream);
+/* NON-REFERENCE option: leaf batching, the solver and subtree reuse in ONE search.  Sets leaves_per_step / virtual_loss (sz_set_leaf_batching)
+ * and the solver (sz_set_solver) in one call and accepts every combination of L >= 1 and solver on or off, on engines with and without
+ * reuse_subtree.  Only between searches (SZ_ERR_STATE otherwise; nothing is changed then).  SZ_ERR_INVALID: opt NULL, L < 1,
+ * L > SZ_MAX_LEAVES_PER_STEP, virtual_loss negative or not finite.  {1, x, 0} leaves the engine exactly as if no setter had been called;
+ * {L, lam, 0} on an engine without reuse_subtree equals sz_set_leaf_batching(L, lam), {1, x, 1} there equals sz_set_solver(1).  After it
+ * sz_set_leaf_batching and sz_set_solver still apply their own refusals against the state now in force.  Still refused, and not part of
+ * this option: sz_set_search_budgets with budgets != NULL on a reuse_subtree engine, sz_set_root_noise on a reuse_subtree engine.
+ * Never called, every kernel that runs today runs unchanged (the combination is a template instantiation of its own).
+ *
+ * Setting changes on a reuse_subtree engine: a call that changes leaves_per_step or the solver flag drops every board's kept subtree; the next
+ * search of every board starts from a fresh root (a tree built without the solver has no `complete` bits, one built before the in-flight
+ * counts existed has none).  A call that changes neither (virtual_loss alone included) keeps the subtrees.
+ *
+ * Solver with L > 1.  Everything sz_set_leaf_batching and sz_set_solver say holds, with these rules where they meet:
+ *   selection      the arg-max runs over the children with R != WIN, over all children if every child is WIN; each child is scored with
+ *                  visit count N + k and value sum W + lambda*k (f64) under sqrt(N_parent + k_parent).  Node.get_ucb's arithmetic and the
+ *                  first-maximum tie-break are unchanged.  With every k == 0 it is the solver's selection exactly.
+ *   proven stop    a descent stops at the first proven node on its way, the root included.  It is backed up on the spot with -1 / 0 / +1,
+ *                  counted as a simulation and a terminal_hit at that depth (and in sz_solver_stats out[0] when the node is not terminal),
+ *                  never becomes pending and adds nothing to any k; the gather goes on, as it does after a terminal leaf.
+ *   terminal leaf  a new terminal leaf is labelled at creation and backed up, then the update walks its path: the only place it runs.
+ *   pending leaf   is non-terminal, hence unknown: a parent with a pending child cannot become LOSS or DRAW.  Leaves already pending in
+ *                  this step whose ancestors become proven during the gather are still expanded and backed up in the next step, in gather
+ *                  order.  R never goes back.  `complete` is set at expansion as without leaf batching.
+ *   proven root    if the root becomes proven in the middle of a gather, the remaining descents of the budget (budget - simulations done -
+ *                  leaves pending) end at the root in that same step; the board is done once its pending leaves have been consumed.
+ *   collision      a descent that ends on a visited non-terminal node without children (a leaf pending in this step) ends the gather.
+ * Budgets (sz_set_search_budgets), sz_compact and sz_compact_searching work as with leaf batching alone (leaves_per_step rows per board).
+ *
+ * reuse_subtree with L > 1.  At the end of a search every in-flight count is 0 (every descent was taken back), and sz_play's compaction
+ * only moves edges to lower indices among the edges in use, so a kept subtree has no descent in flight.  A continued search has no root
+ * evaluation in flight either: sz_search_begin's descent-only launch gathers up to L leaves (rows slot(b)*L + i) before the first network
+ * call.  The three fresh-start conditions of sz_config.reuse_subtree are unchanged, a continued search makes num_searches new simulations,
+ * and its length in steps is data-dependent: step until sz_pending_boards is 0.
+ *
+ * reuse_subtree with the solver.  Labels and `complete` bits travel with their edges through the compaction.  They are relative to the side
+ * to move in the node, and the game history below the new root is the history they were computed under, so they stay true.  A chosen child
+ * that is proven but has children is kept like any other (fresh-start condition (1) is unchanged).  A continued search whose root is
+ * proven counts all num_searches simulations out at the root in the descent-only launch: it never asks for the network and its board is
+ * done when sz_search_begin returns.  sz_play on a WIN root plays the first LOSS child; a fresh start labels nothing but a terminal root.
+ * All three options together follow from the above.
+ * Held bit for bit to the host restatement tests/composeref.py by tests/test_gpu_compose.py.  The effect of any combination on playing
+ * strength is unmeasured. */
+typedef struct sz_search_options {
+    int32_t leaves_per_step;     /* L of sz_set_leaf_batching, 1..SZ_MAX_LEAVES_PER_STEP */
+    float   virtual_loss;        /* lambda of sz_set_leaf_batching (ignored at L = 1) */
+    int32_t solver;              /* != 0: proven-result propagation on (sz_set_solver) */
+} sz_search_options;
+int sz_set_search_options(sz_engine* e, const sz_search_options* opt, void* stream);
 /* proven results after (or during) a search, device pointers: root_dev [n_boards] int8, child_dev [n_boards,218] int8 in action order, as
  * sz_root_children.  Codes: 0 unknown, 1 WIN, 2 DRAW, 3 LOSS, each for the side to move in that node's own position (a root child
  * with 3 is a move that wins for the root).  All 0 without the solver. */

@@ -23,6 +23,10 @@ class sz_config(C.Structure):
                 ("planes_dtype", C.c_int32), ("device", C.c_int32), ("reuse_subtree", C.c_int32)]
 
 
+class sz_search_options(C.Structure):
+    _fields_ = [("leaves_per_step", C.c_int32), ("virtual_loss", C.c_float), ("solver", C.c_int32)]
+
+
 class sz_stats(C.Structure):
     _fields_ = [("simulations", C.c_uint64), ("expansions", C.c_uint64), ("terminal_hits", C.c_uint64), ("sum_depth", C.c_uint64),
                 ("sum_children", C.c_uint64), ("max_edges_used", C.c_uint64), ("boards_pending", C.c_int32),
@@ -49,6 +53,7 @@ EXPORTS = {
     "sz_set_leaf_batching": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "sz_pending_boards": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_set_solver": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "sz_set_search_options": (C.c_int, [C.c_void_p, C.POINTER(sz_search_options), C.c_void_p]),
     "sz_root_proven": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sz_debug_tree_proven": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_solver_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

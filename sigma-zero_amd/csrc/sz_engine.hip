@@ -207,6 +207,29 @@ __device__ __forceinline__ int wave_solver_update(EdgeMeta* em, const int* path,
     return proved;
 }
 
+// both (sz_set_search_options with leaves_per_step > 1 and the solver): wave_select_child_solver's candidate set, wave_select_child_vl's scores.
+// k == 0 everywhere gives wave_select_child_solver exactly.
+__device__ __forceinline__ int wave_select_child_vl_solver(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam) {
+    const int lane = lane_id();
+    const float sq = (float)sqrt((double)parentVC);
+    bool open = false;
+    for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
+    const bool skip_wins = __ballot(open) != 0;
+    float best = 0.f; int bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) {
+        if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue;
+        EdgeStat s = ch[c];
+        const int kc = k[c];
+        float u = ucb_value(s.N + kc, s.W + (double)lam * (double)kc, s.P, sq, c_puct);
+        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+    }
+    return uni(bi);
+}
+
 struct BoardPtrs {
     SzPos* npos; SzPos* ring; EdgeStat* es; EdgeMeta* em; int* gpath; u64* pmask; Ctl* ctl;
 };
@@ -484,6 +507,13 @@ __global__ __launch_bounds__(256) void k_move_rows(const uint4* __restrict__ src
     for (size_t i = threadIdx.x; i < n; i += 256) d[i] = s[i];
 }
 
+// sz_set_search_options changed leaves_per_step or the solver on a reuse_subtree engine: no board continues on its kept subtree (built without
+// `complete` bits, or before the in-flight counts existed); the next search of every board starts from a fresh root
+__global__ void k_drop_subtrees(View v) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < v.B) v.ctl[b].reuse_ready = 0;
+}
+
 // finish an uploaded game record (status only; the ring was copied by the host)
 __global__ void k_after_upload(View v, int b, int ply) {
     Ctl* c = v.ctl + b;
@@ -497,6 +527,7 @@ __global__ void k_after_upload(View v, int b, int ply) {
 // ------------------------------------------------------------------------------------------------
 // VL: leaf batching on (sz_set_leaf_batching): the root is pending leaf 0, its network input goes to row slot(b)*L
 // SOLVE: proven results on (sz_set_solver): a terminal root is labelled like any terminal position
+// Both (sz_set_search_options) and either with reuse_subtree: the same code; a kept subtree carries its labels and has no descent in flight
 template <bool VL, bool SOLVE>
 __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb) {
     extern __shared__ u64 lds64[];
@@ -528,6 +559,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
             bp.npos[0] = X;
             Ctl* c = bp.ctl;
             c->status = (status & ST_ACTIVE) | ST_SEARCHING; c->sims_done = 0; c->pend_node = -1; c->pend_depth = 0; c->reuse_ready = 0;
+            if constexpr (VL) c->n_pend = 0;                    // no root evaluation in flight: every in-flight count of the kept tree is 0, k[0] included
             if (v.rec_colour) v.rec_colour[b] = (uint8_t)szm_turn(X.meta);
         }
         return;
@@ -589,7 +621,8 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // VL = false: the reference's search, one leaf per board per step.  VL = true (sz_set_leaf_batching): every pending leaf is expanded and
 // backed up in gather order (its k taken back along its path), then descents with virtual loss gather up to L new leaves; a terminal leaf
 // is backed up on the spot, a descent that ends on a leaf already pending in this step (a collision) ends the gather.
-// SOLVE = true (sz_set_solver, VL = false only): proven results are carried up the tree; a descent ends at the first proven node on its way.
+// SOLVE = true (sz_set_solver): proven results are carried up the tree; a descent ends at the first proven node on its way.
+// VL && SOLVE (sz_set_search_options): both at once; a proven stop puts nothing in flight and the gather goes on, a pending leaf is unknown.
 template <bool VL, bool SOLVE>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb) {
     extern __shared__ u64 lds64[];
@@ -604,7 +637,6 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     const int row = v.slot ? uni(v.slot[b]) : b;              // network batch row of this board
     if (row < 0) return;
     if ((status & ST_PENDING) && !policy) return;             // descent-only launch (sz_search_begin with reuse): boards that already wait for the network sit it out
-    static_assert(!(VL && SOLVE), "the solver is not combined with leaf batching");
     unsigned long long n_expand = 0, n_term = 0, sum_depth = 0, sum_k = 0;
     unsigned long long n_stop = 0, n_proved = 0;                // solver: simulations ended on a proven non-terminal node, nodes proven by the update
     int err = 0;
@@ -732,9 +764,11 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         int proven = PR_UNKNOWN;                                        // solver: result of the first proven node on the way, the root included
         if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
         while (mn > 0 && !proven) {                                     // Node.select
-            int bi = SOLVE ? wave_select_child_solver(bp.es + m.first, bp.em + m.first, mn, parentN, v.c_puct)
-                   : VL ? wave_select_child_vl(bp.es + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam)
-                        : wave_select_child(bp.es + m.first, mn, parentN, v.c_puct, nullptr);
+            int bi;
+            if constexpr (VL && SOLVE) bi = wave_select_child_vl_solver(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam);
+            else bi = SOLVE ? wave_select_child_solver(bp.es + m.first, bp.em + m.first, mn, parentN, v.c_puct)
+                    : VL ? wave_select_child_vl(bp.es + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam)
+                         : wave_select_child(bp.es + m.first, mn, parentN, v.c_puct, nullptr);
             cur = m.first + bi;
             d++;
             if (d >= v.p_cap) { err = SZ_ERR_CAPACITY; break; }
@@ -1262,18 +1296,31 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
     return SZ_OK;
 }
 
+// the k_search_step instantiation of the options in force; policy == NULL: the descent-only launch of sz_search_begin
+static void launch_step(sz_engine* e, const float* policy, const float* value, void* planes, hipStream_t s) {
+    if (e->vb.L > 1 && e->solver)
+        hipLaunchKernelGGL((k_search_step<true, true>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, e->vb);
+    else if (e->vb.L > 1)
+        hipLaunchKernelGGL((k_search_step<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, e->vb);
+    else if (e->solver)
+        hipLaunchKernelGGL((k_search_step<false, true>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{});
+    else
+        hipLaunchKernelGGL((k_search_step<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{});
+}
+
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    if (e->vb.L > 1) hipLaunchKernelGGL((k_search_begin<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
+    if (e->vb.L > 1 && e->solver) hipLaunchKernelGGL((k_search_begin<true, true>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
+    else if (e->vb.L > 1) hipLaunchKernelGGL((k_search_begin<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
     else if (e->solver) hipLaunchKernelGGL((k_search_begin<false, true>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
     else hipLaunchKernelGGL((k_search_begin<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
     HIPCHK(hipGetLastError());
     if (e->v.reuse && planes_dev) {
         // boards that continue on a kept subtree have no root to evaluate: one descent-only launch selects their first leaf (boards whose fresh
-        // root waits for the network sit it out), so that every board enters the first network call with a real position
-        hipLaunchKernelGGL((k_search_step<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, (const float*)nullptr, (const float*)nullptr,
-                           planes_dev, Batch{});
+        // root waits for the network sit it out), so that every board enters the first network call with a real position.  Batched
+        // (sz_set_search_options): it gathers up to L leaves; with the solver a board whose kept root is proven counts all its simulations out here
+        launch_step(e, nullptr, nullptr, planes_dev, (hipStream_t)stream);
         HIPCHK(hipGetLastError());
     }
     return SZ_OK;
@@ -1282,27 +1329,13 @@ int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
 int sz_search_step(sz_engine* e, const float* policy_dev, const float* value_dev, void* planes_dev, void* stream) {
     if (!e || !policy_dev || !value_dev || !planes_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    if (e->vb.L > 1)
-        hipLaunchKernelGGL((k_search_step<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, e->vb);
-    else if (e->solver)
-        hipLaunchKernelGGL((k_search_step<false, true>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, Batch{});
-    else
-        hipLaunchKernelGGL((k_search_step<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, policy_dev, value_dev, planes_dev, Batch{});
+    launch_step(e, policy_dev, value_dev, planes_dev, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
 
-int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream) {
-    if (!e || leaves_per_step < 1 || leaves_per_step > SZ_MAX_LEAVES_PER_STEP || !(virtual_loss >= 0.0f) || !std::isfinite(virtual_loss)) return SZ_ERR_INVALID;
-    if (leaves_per_step > 1 && e->v.reuse) return SZ_ERR_INVALID;          // combining the two non-reference options is not supported
-    if (leaves_per_step > 1 && e->solver) return SZ_ERR_INVALID;           // nor leaf batching with the solver
-    ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Ctl> h(e->v.B);
-    HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (const Ctl& c : h)
-        if ((c.status & ST_SEARCHING) && !(c.status & (ST_DONE | ST_ERROR))) return SZ_ERR_STATE;       // only between searches
+// the leaf-batching buffers (in-flight counts, L paths and legal masks per board), grown on the first call that needs more than there is
+static int batch_buffers(sz_engine* e, int leaves_per_step) {
     if (leaves_per_step > 1 && leaves_per_step > e->vb_cap) {
         for (void* p : e->vb_allocs) (void)hipFree(p);
         e->vb_allocs.clear(); e->vb_cap = 0;
@@ -1322,6 +1355,32 @@ int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_lo
         e->vb.vk = (int*)q[0]; e->vb.path = (int*)q[1]; e->vb.mask = (u64*)q[2]; e->vb.depth = (int*)q[3];
         e->vb_cap = leaves_per_step;
     }
+    return SZ_OK;
+}
+
+// the solver's counters, allocated by the first enabling call
+static int solver_counters(sz_engine* e, hipStream_t s) {
+    if (e->d_sstat) return SZ_OK;
+    int rc = dalloc(e, &e->d_sstat, (size_t)e->v.B * 2);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(e->d_sstat, 0, (size_t)e->v.B * 2 * sizeof(unsigned long long), s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SZ_OK;
+}
+
+int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream) {
+    if (!e || leaves_per_step < 1 || leaves_per_step > SZ_MAX_LEAVES_PER_STEP || !(virtual_loss >= 0.0f) || !std::isfinite(virtual_loss)) return SZ_ERR_INVALID;
+    if (leaves_per_step > 1 && e->v.reuse) return SZ_ERR_INVALID;          // combining the two non-reference options is not supported
+    if (leaves_per_step > 1 && e->solver) return SZ_ERR_INVALID;           // nor leaf batching with the solver
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Ctl> h(e->v.B);
+    HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (const Ctl& c : h)
+        if ((c.status & ST_SEARCHING) && !(c.status & (ST_DONE | ST_ERROR))) return SZ_ERR_STATE;       // only between searches
+    int rc = batch_buffers(e, leaves_per_step);
+    if (rc) return rc;
     e->vb.L = leaves_per_step;
     e->vb.lam = virtual_loss;
     return SZ_OK;
@@ -1336,13 +1395,33 @@ int sz_set_solver(sz_engine* e, int32_t enable, void* stream) {
     int rc = search_in_progress(e, s, &busy);
     if (rc) return rc;
     if (busy) return SZ_ERR_STATE;                                          // only between searches
-    if (enable && !e->d_sstat) {
-        if ((rc = dalloc(e, &e->d_sstat, (size_t)e->v.B * 2))) return rc;
-        HIPCHK(hipMemsetAsync(e->d_sstat, 0, (size_t)e->v.B * 2 * sizeof(unsigned long long), s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
+    if (enable && (rc = solver_counters(e, s))) return rc;
     e->solver = enable ? 1 : 0;
     e->v.sstat = enable ? e->d_sstat : nullptr;
+    return SZ_OK;
+}
+
+int sz_set_search_options(sz_engine* e, const sz_search_options* opt, void* stream) {
+    if (!e || !opt || opt->leaves_per_step < 1 || opt->leaves_per_step > SZ_MAX_LEAVES_PER_STEP || !(opt->virtual_loss >= 0.0f) || !std::isfinite(opt->virtual_loss))
+        return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    const int solver = opt->solver ? 1 : 0;
+    if ((rc = batch_buffers(e, opt->leaves_per_step))) return rc;
+    if (solver && (rc = solver_counters(e, s))) return rc;
+    if (e->v.reuse && (opt->leaves_per_step != e->vb.L || solver != e->solver)) {
+        // a kept subtree built under other settings has no `complete` bits, or its in-flight counts were never written: start fresh
+        hipLaunchKernelGGL(k_drop_subtrees, dim3((e->v.B + 255) / 256), dim3(256), 0, s, e->v);
+        HIPCHK(hipGetLastError());
+    }
+    e->vb.L = opt->leaves_per_step;
+    e->vb.lam = opt->virtual_loss;
+    e->solver = solver;
+    e->v.sstat = solver ? e->d_sstat : nullptr;
     return SZ_OK;
 }
 

@@ -101,18 +101,24 @@ class SelfPlayEngine:
             raise ValueError("args['leaves_per_step'] must be an integer in 1..%d, got %r" % (N.SZ_MAX_LEAVES_PER_STEP, L))
         if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not (math.isfinite(lam) and lam >= 0):
             raise ValueError("args['virtual_loss'] must be a finite number >= 0, got %r" % (lam,))
-        if L > 1 and self.args.get("reuse_subtree", False):
-            raise ValueError("args['leaves_per_step'] > 1 and args['reuse_subtree'] exclude each other")
+        # NON-REFERENCE option (default off): args["combine_options"] = True lets leaves_per_step > 1, solver and reuse_subtree run in one
+        # search, in any combination (sz_set_search_options); without it each pair is refused as before
+        combine = self.args.get("combine_options", False)
+        if not isinstance(combine, (bool, np.bool_)):
+            raise ValueError("args['combine_options'] must be True or False, got %r" % (combine,))
+        self.combine = bool(combine)
+        if L > 1 and self.args.get("reuse_subtree", False) and not combine:
+            raise ValueError("args['leaves_per_step'] > 1 and args['reuse_subtree'] exclude each other (without args['combine_options'])")
         self.L, self.virtual_loss = int(L), float(lam)
         # NON-REFERENCE option (default off): args["solver"] = True carries proven results (forced wins, draws and losses) up the tree
         # (sz_set_solver): descents end at proven nodes, refuted moves are not selected, play() takes the proving move of a won root
         solver = self.args.get("solver", False)
         if not isinstance(solver, (bool, np.bool_)):
             raise ValueError("args['solver'] must be True or False, got %r" % (solver,))
-        if solver and self.args.get("reuse_subtree", False):
-            raise ValueError("args['solver'] and args['reuse_subtree'] exclude each other")
-        if solver and L > 1:
-            raise ValueError("args['solver'] and args['leaves_per_step'] > 1 exclude each other")
+        if solver and self.args.get("reuse_subtree", False) and not combine:
+            raise ValueError("args['solver'] and args['reuse_subtree'] exclude each other (without args['combine_options'])")
+        if solver and L > 1 and not combine:
+            raise ValueError("args['solver'] and args['leaves_per_step'] > 1 exclude each other (without args['combine_options'])")
         self.solver = bool(solver)
         self.last_steps = 0           # network calls made by the last search()
         self.last_rows = 0            # network rows evaluated by the last search()
@@ -143,10 +149,13 @@ class SelfPlayEngine:
             self.planes = torch.zeros(rows, 64, 128, dtype=torch.bfloat16, device=dev)
         else:
             self.planes = torch.zeros(rows, N.SZ_PLANES, 8, 8, dtype=planes_dtype, device=dev)
-        if self.L > 1:
-            N.check(N.lib().sz_set_leaf_batching(self._e, self.L, self.virtual_loss, self._stream()), "sz_set_leaf_batching")
-        if self.solver:
-            N.check(N.lib().sz_set_solver(self._e, 1, self._stream()), "sz_set_solver")
+        if self.combine:
+            self.set_search_options(self.L, self.virtual_loss, self.solver)
+        else:
+            if self.L > 1:
+                N.check(N.lib().sz_set_leaf_batching(self._e, self.L, self.virtual_loss, self._stream()), "sz_set_leaf_batching")
+            if self.solver:
+                N.check(N.lib().sz_set_solver(self._e, 1, self._stream()), "sz_set_solver")
         self.uniforms = torch.zeros(self.B, dtype=torch.float64, device=dev)
         self.root_action = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
         self.root_visits = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
@@ -200,6 +209,16 @@ class SelfPlayEngine:
         self.n_rows = int(n.value) if enable else self.B
         self._compact_on, self._restore = bool(enable), False
         return self.n_rows
+
+    def set_search_options(self, leaves_per_step, virtual_loss, solver):
+        """leaves_per_step / virtual_loss and the solver in one call, any combination, with and without reuse_subtree (sz_set_search_options);
+        between searches only.  On a reuse_subtree engine a change of leaves_per_step or of the solver drops every kept subtree.  The planes
+        buffer grows with leaves_per_step (network rows = boards * leaves_per_step)."""
+        opt = N.sz_search_options(int(leaves_per_step), float(virtual_loss), int(bool(solver)))
+        N.check(N.lib().sz_set_search_options(self._e, C.byref(opt), self._stream()), "sz_set_search_options")
+        self.L, self.virtual_loss, self.solver = int(leaves_per_step), float(virtual_loss), bool(solver)
+        if self.planes.shape[0] < self.B * self.L:
+            self.planes = torch.zeros((self.B * self.L,) + tuple(self.planes.shape[1:]), dtype=self.planes.dtype, device=self.device)
 
     def set_budgets(self, budgets):
         """Per-board search budgets (sz_set_search_budgets, a NON-REFERENCE option): budgets[b] in 0..num_searches simulations for board b
