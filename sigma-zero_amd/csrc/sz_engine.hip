@@ -29,6 +29,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 #include "sz_chess.h"
 #include "../../include/sigmazero.h"
@@ -125,55 +126,28 @@ __device__ __forceinline__ float ucb_value(int vc, double wsum, float prior, flo
 
 // Node.select (mctsnode.py:23-31): argmax of get_ucb over the n contiguous children, first maximum wins (torch.argmax).
 // Lanes = children; wave64 xor-butterfly with lowest-index tie-break.  ucb_out (optional, test hook) receives every child's value.
-__device__ __forceinline__ int wave_select_child(const EdgeStat* ch, int n, int parentN, float c_puct, float* ucb_out) {
+// VL (sz_set_leaf_batching): child c scores as if its k[c] descents in flight had each returned a loss for the parent, vc = N + k,
+// wsum = W + lam*k (f64); parentVC = N + k of the parent (N alone without VL).  k == 0 everywhere gives the VL = false result exactly.
+// SOLVE (sz_set_solver): the arg-max runs over the children that are not proven WIN (a child whose side to move wins is a refuted move);
+// over all of them when every child is WIN.  ucb_value, its operation order and the tie-break are the same in all four instantiations.
+template <bool VL, bool SOLVE>
+__device__ __forceinline__ int wave_select_child(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam, float* ucb_out) {
     const int lane = lane_id();
-    const float sq = (float)sqrt((double)parentN);                      // math.sqrt(self.visit_count) in double, then a float32 operand
+    const float sq = (float)sqrt((double)parentVC);                     // math.sqrt(self.visit_count) in double, then a float32 operand
+    bool skip_wins = false;
+    if constexpr (SOLVE) {
+        bool open = false;
+        for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
+        skip_wins = __ballot(open) != 0;
+    }
     float best = 0.f; int bi = 0x7fffffff;
     for (int c = lane; c < n; c += 64) {
+        if constexpr (SOLVE) { if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue; }
         EdgeStat s = ch[c];
-        float u = ucb_value(s.N, s.W, s.P, sq, c_puct);
+        float u;
+        if constexpr (VL) { const int kc = k[c]; u = ucb_value(s.N + kc, s.W + (double)lam * (double)kc, s.P, sq, c_puct); }
+        else u = ucb_value(s.N, s.W, s.P, sq, c_puct);
         if (ucb_out) ucb_out[c] = u;
-        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
-    }
-    return uni(bi);
-}
-
-// the same with virtual loss (sz_set_leaf_batching): child c scores as if its k[c] descents in flight had each returned a loss for the
-// parent, vc = N + k, wsum = W + lam*k (f64); parentVC = N + k of the parent.  k == 0 everywhere gives wave_select_child exactly.
-__device__ __forceinline__ int wave_select_child_vl(const EdgeStat* ch, const int* k, int n, int parentVC, float c_puct, float lam) {
-    const int lane = lane_id();
-    const float sq = (float)sqrt((double)parentVC);
-    float best = 0.f; int bi = 0x7fffffff;
-    for (int c = lane; c < n; c += 64) {
-        EdgeStat s = ch[c];
-        const int kc = k[c];
-        float u = ucb_value(s.N + kc, s.W + (double)lam * (double)kc, s.P, sq, c_puct);
-        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
-    }
-    return uni(bi);
-}
-
-// the same with proven results (sz_set_solver): the arg-max runs over the children that are not proven WIN (a child whose side to move wins
-// is a refuted move); over all of them when every child is WIN.  ucb_value, its operation order and the tie-break are wave_select_child's.
-__device__ __forceinline__ int wave_select_child_solver(const EdgeStat* ch, const EdgeMeta* cm, int n, int parentN, float c_puct) {
-    const int lane = lane_id();
-    const float sq = (float)sqrt((double)parentN);
-    bool open = false;
-    for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
-    const bool skip_wins = __ballot(open) != 0;
-    float best = 0.f; int bi = 0x7fffffff;
-    for (int c = lane; c < n; c += 64) {
-        if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue;
-        EdgeStat s = ch[c];
-        float u = ucb_value(s.N, s.W, s.P, sq, c_puct);
         if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
     }
     for (int off = 32; off >= 1; off >>= 1) {
@@ -207,29 +181,6 @@ __device__ __forceinline__ int wave_solver_update(EdgeMeta* em, const int* path,
     return proved;
 }
 
-// both (sz_set_search_options with leaves_per_step > 1 and the solver): wave_select_child_solver's candidate set, wave_select_child_vl's scores.
-// k == 0 everywhere gives wave_select_child_solver exactly.
-__device__ __forceinline__ int wave_select_child_vl_solver(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam) {
-    const int lane = lane_id();
-    const float sq = (float)sqrt((double)parentVC);
-    bool open = false;
-    for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
-    const bool skip_wins = __ballot(open) != 0;
-    float best = 0.f; int bi = 0x7fffffff;
-    for (int c = lane; c < n; c += 64) {
-        if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue;
-        EdgeStat s = ch[c];
-        const int kc = k[c];
-        float u = ucb_value(s.N + kc, s.W + (double)lam * (double)kc, s.P, sq, c_puct);
-        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
-    }
-    return uni(bi);
-}
-
 struct BoardPtrs {
     SzPos* npos; SzPos* ring; EdgeStat* es; EdgeMeta* em; int* gpath; u64* pmask; Ctl* ctl;
 };
@@ -244,6 +195,21 @@ __device__ __forceinline__ BoardPtrs board_ptrs(const View& v, int b) {
     p.gpath = v.gpath + (size_t)b * v.p_cap;
     p.pmask = v.pmask + (size_t)b * PMASK_STRIDE;
     p.ctl = v.ctl + b;
+    return p;
+}
+
+// where pending leaf li of board b keeps its descent path, legal-move mask and depth, and its row in the network batch (planes / policy /
+// value).  VL = false: the board's one leaf, in its own records at row slot(b).  VL = true (sz_set_leaf_batching): leaf li of L, at row slot(b)*L + li.
+struct LeafPtrs { int* path; u64* mask; int* depth; size_t row; };
+template <bool VL>
+__device__ __forceinline__ LeafPtrs leaf_ptrs(const View& v, const BoardPtrs& bp, const Batch& vb, int b, int row, int li) {
+    LeafPtrs p;
+    if constexpr (VL) {
+        const size_t i = (size_t)b * vb.L + li;
+        p.path = vb.path + i * v.p_cap; p.mask = vb.mask + i * PMASK_STRIDE; p.depth = vb.depth + i; p.row = (size_t)(row * vb.L + li);
+    } else {
+        p.path = bp.gpath; p.mask = bp.pmask; p.depth = &bp.ctl->pend_depth; p.row = (size_t)row;
+    }
     return p;
 }
 
@@ -525,7 +491,7 @@ __global__ void k_after_upload(View v, int b, int ply) {
 // ------------------------------------------------------------------------------------------------
 // kernel: search begin — create roots (mcts.py:43-46), root movegen + terminal test, encode root planes
 // ------------------------------------------------------------------------------------------------
-// VL: leaf batching on (sz_set_leaf_batching): the root is pending leaf 0, its network input goes to row slot(b)*L
+// VL: leaf batching on (sz_set_leaf_batching): the root is pending leaf 0 (leaf_ptrs), its network input goes to row slot(b)*L
 // SOLVE: proven results on (sz_set_solver): a terminal root is labelled like any terminal position
 // Both (sz_set_search_options) and either with reuse_subtree: the same code; a kept subtree carries its labels and has no descent in flight
 template <bool VL, bool SOLVE>
@@ -592,21 +558,19 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
     int n_legal, ep_legal; u64 checkers;
     wave_movegen(X, v.chess960, mask, n_legal, ep_legal, checkers);
     __syncthreads();
-    u64* pm = VL ? vb.mask + (size_t)b * vb.L * PMASK_STRIDE : bp.pmask;
-    for (int i = lane; i < SZ_MASK_WORDS; i += 64) pm[i] = mask[i];
+    const int row = v.slot ? uni(v.slot[b]) : b;              // network batch row of this board (compacted batches: live boards first)
+    const LeafPtrs lf = leaf_ptrs<VL>(v, bp, vb, b, row, 0);  // the root is pending leaf 0
+    for (int i = lane; i < SZ_MASK_WORDS; i += 64) lf.mask[i] = mask[i];
     wave_load_history(bp, path, 0, root_ply, X, hist);
     __syncthreads();
-    const int row = v.slot ? uni(v.slot[b]) : b;              // network batch row of this board (compacted batches: live boards first)
-    const size_t row0 = (size_t)row * (VL ? vb.L : 1);       // batched: its leaf i sits at row slot(b)*L + i
-    wave_encode(hist, X, (planes && row >= 0) ? (char*)planes + row0 * planes_board_bytes(v.planes_dtype) : nullptr, v.planes_dtype,
+    wave_encode(hist, X, (planes && row >= 0) ? (char*)planes + lf.row * planes_board_bytes(v.planes_dtype) : nullptr, v.planes_dtype,
                 v.rec_planes ? v.rec_planes + (size_t)b * SZ_NUM_PLANES * 8 : nullptr);
     if (lane == 0) {
         Ctl* c = bp.ctl;
         c->status = st | ST_PENDING; c->n_nodes = 1; c->n_edges = 1; c->sims_done = 0; c->pend_node = 0; c->pend_depth = 0;
         if (v.rec_colour) v.rec_colour[b] = (uint8_t)szm_turn(X.meta);
         if constexpr (VL) {
-            const size_t li = (size_t)b * vb.L;
-            c->n_pend = 1; vb.depth[li] = 0; vb.path[li * v.p_cap] = 0;
+            c->n_pend = 1; *lf.depth = 0; lf.path[0] = 0;
             vb.vk[(size_t)b * v.e_cap] = 1;                     // the root's own evaluation is in flight
         }
     }
@@ -623,6 +587,8 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // is backed up on the spot, a descent that ends on a leaf already pending in this step (a collision) ends the gather.
 // SOLVE = true (sz_set_solver): proven results are carried up the tree; a descent ends at the first proven node on its way.
 // VL && SOLVE (sz_set_search_options): both at once; a proven stop puts nothing in flight and the gather goes on, a pending leaf is unknown.
+// One body for the four: selection is wave_select_child<VL, SOLVE>, a pending leaf's path / mask / depth / network row come from
+// leaf_ptrs<VL>; only the in-flight counts, n_pend, the collision break and "gather on" against "one leaf, stop" sit under if constexpr (VL).
 template <bool VL, bool SOLVE>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb) {
     extern __shared__ u64 lds64[];
@@ -646,14 +612,12 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
       const int n_leaves = VL ? uni(bp.ctl->n_pend) : 1;
       for (int li = 0;;) {                                              // VL = false: one pass, no loop
         // ---- mcts.py:77-109 for the leaf evaluated by the network (batched: every pending leaf, in gather order) -------------------
-        const int d = VL ? uni(vb.depth[(size_t)b * vb.L + li]) : uni(bp.ctl->pend_depth), node = VL ? 0 : uni(bp.ctl->pend_node);
-        const int* gpath = VL ? vb.path + ((size_t)b * vb.L + li) * v.p_cap : bp.gpath;
-        const u64* gmask = VL ? vb.mask + ((size_t)b * vb.L + li) * PMASK_STRIDE : bp.pmask;
-        const int prow = VL ? row * vb.L + li : row;                        // network batch row of this leaf
-        for (int j = lane; j <= d; j += 64) path[j] = gpath[j];
-        for (int i = lane; i < SZ_MASK_WORDS; i += 64) mask[i] = gmask[i];
+        const LeafPtrs lf = leaf_ptrs<VL>(v, bp, vb, b, row, li);
+        const int d = uni(*lf.depth), node = VL ? 0 : uni(bp.ctl->pend_node);
+        for (int j = lane; j <= d; j += 64) path[j] = lf.path[j];
+        for (int i = lane; i < SZ_MASK_WORDS; i += 64) mask[i] = lf.mask[i];
         __syncthreads();
-        const float* pol = policy + (size_t)prow * SZ_NUM_ACTIONS;
+        const float* pol = policy + lf.row * SZ_NUM_ACTIONS;
             // masked sum in the fixed order: per-lane partial over planes ascending, then xor butterfly.
             // Only planes that hold a legal move are fetched (~20 of 73), and in groups of 16 INDEPENDENT loads: a load-wait-add chain per
             // plane cost one full memory latency each, and fetching all 73 planes made the kernel bandwidth-bound at 4096 boards.  The
@@ -737,7 +701,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             }
             n_edges += kept;
             (void)node;
-        const double val = (double)value[prow];                         // node.value = value.item()
+        const double val = (double)value[lf.row];                        // node.value = value.item()
         if constexpr (VL) {                                             // its descent is no longer in flight
             for (int j = lane; j <= d; j += 64) vb.vk[(size_t)b * v.e_cap + path[j]] -= 1;
         }
@@ -764,11 +728,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         int proven = PR_UNKNOWN;                                        // solver: result of the first proven node on the way, the root included
         if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
         while (mn > 0 && !proven) {                                     // Node.select
-            int bi;
-            if constexpr (VL && SOLVE) bi = wave_select_child_vl_solver(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam);
-            else bi = SOLVE ? wave_select_child_solver(bp.es + m.first, bp.em + m.first, mn, parentN, v.c_puct)
-                    : VL ? wave_select_child_vl(bp.es + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam)
-                         : wave_select_child(bp.es + m.first, mn, parentN, v.c_puct, nullptr);
+            const int bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
             cur = m.first + bi;
             d++;
             if (d >= v.p_cap) { err = SZ_ERR_CAPACITY; break; }
@@ -819,30 +779,26 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             if constexpr (SOLVE) n_proved += wave_solver_update(bp.em, path, d);
             continue;
         }
-        // non-terminal leaf: hand it to the network
+        // non-terminal leaf: hand it to the network as pending leaf n_pend (always 0 without batching)
         __syncthreads();
-        if constexpr (VL) {
-            // batched: pending leaf n_pend at row slot(b)*L + n_pend; its descent goes in flight (k + 1 along its path) and the gather goes on
-            const size_t li = (size_t)b * vb.L + n_pend;
-            for (int i = lane; i < SZ_MASK_WORDS; i += 64) vb.mask[li * PMASK_STRIDE + i] = mask[i];
-            for (int j = lane; j <= d; j += 64) { vb.path[li * v.p_cap + j] = path[j]; vk[path[j]] += 1; }
-            if (lane == 0) vb.depth[li] = d;
-            wave_load_history(bp, path, d, root_ply, X, hist);
-            __syncthreads();
-            wave_encode(hist, X, (char*)planes + ((size_t)row * vb.L + n_pend) * planes_board_bytes(v.planes_dtype), v.planes_dtype, nullptr);
+        const LeafPtrs lf = leaf_ptrs<VL>(v, bp, vb, b, row, n_pend);
+        for (int i = lane; i < SZ_MASK_WORDS; i += 64) lf.mask[i] = mask[i];
+        for (int j = lane; j <= d; j += 64) {
+            lf.path[j] = path[j];
+            if constexpr (VL) vk[path[j]] += 1;                         // batched: its descent goes in flight (k + 1 along its path)
+        }
+        if constexpr (VL) { if (lane == 0) *lf.depth = d; }
+        wave_load_history(bp, path, d, root_ply, X, hist);
+        __syncthreads();
+        wave_encode(hist, X, (char*)planes + lf.row * planes_board_bytes(v.planes_dtype), v.planes_dtype, nullptr);
+        status |= ST_PENDING;
+        if constexpr (VL) {                                             // batched: the gather goes on
             __threadfence_block();
             __syncthreads();
             n_pend++;
-            status |= ST_PENDING;
             continue;
         }
-        for (int i = lane; i < SZ_MASK_WORDS; i += 64) bp.pmask[i] = mask[i];
-        for (int j = lane; j <= d; j += 64) bp.gpath[j] = path[j];
-        wave_load_history(bp, path, d, root_ply, X, hist);
-        __syncthreads();
-        wave_encode(hist, X, (char*)planes + (size_t)row * planes_board_bytes(v.planes_dtype), v.planes_dtype, nullptr);
-        status |= ST_PENDING;
-        if (lane == 0) { bp.ctl->pend_node = nid; bp.ctl->pend_depth = d; }
+        if (lane == 0) { bp.ctl->pend_node = nid; *lf.depth = d; }
         STEP_STAMP(4);
         break;
     }
@@ -1031,7 +987,7 @@ __global__ __launch_bounds__(64) void k_debug_select(const int* offsets, const i
     if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane_id() == 0) argmax_out[cs] = -1; return; }
     for (int c = lane_id(); c < n; c += 64) { EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s; }
     __syncthreads();
-    const int bi = wave_select_child(ch, n, parent_visits[cs], c_puct[cs], ucb_out + lo);
+    const int bi = wave_select_child<false, false>(ch, nullptr, nullptr, n, parent_visits[cs], c_puct[cs], 0.f, ucb_out + lo);
     if (lane_id() == 0) argmax_out[cs] = bi;
 }
 
@@ -1073,6 +1029,13 @@ template <typename T> static int dalloc(sz_engine* e, T** p, size_t count) {
     e->allocs.push_back(q);
     *p = (T*)q;
     return SZ_OK;
+}
+
+// the one place that maps the options in force to a kernel instantiation: f(VL, SOLVE) is called with two std::bool_constants,
+// VL = leaf batching on (vb.L > 1), SOLVE = the solver on.  Instantiations without batching take an empty Batch.
+template <typename F> static void with_search_options(const sz_engine* e, F&& f) {
+    if (e->vb.L > 1) { if (e->solver) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else             { if (e->solver) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
 }
 
 extern "C" {
@@ -1298,23 +1261,19 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
 
 // the k_search_step instantiation of the options in force; policy == NULL: the descent-only launch of sz_search_begin
 static void launch_step(sz_engine* e, const float* policy, const float* value, void* planes, hipStream_t s) {
-    if (e->vb.L > 1 && e->solver)
-        hipLaunchKernelGGL((k_search_step<true, true>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, e->vb);
-    else if (e->vb.L > 1)
-        hipLaunchKernelGGL((k_search_step<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, e->vb);
-    else if (e->solver)
-        hipLaunchKernelGGL((k_search_step<false, true>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{});
-    else
-        hipLaunchKernelGGL((k_search_step<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{});
+    with_search_options(e, [&](auto vl, auto solve) {
+        constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
+        hipLaunchKernelGGL((k_search_step<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{});
+    });
 }
 
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    if (e->vb.L > 1 && e->solver) hipLaunchKernelGGL((k_search_begin<true, true>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
-    else if (e->vb.L > 1) hipLaunchKernelGGL((k_search_begin<true, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, e->vb);
-    else if (e->solver) hipLaunchKernelGGL((k_search_begin<false, true>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
-    else hipLaunchKernelGGL((k_search_begin<false, false>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, Batch{});
+    with_search_options(e, [&](auto vl, auto solve) {
+        constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
+        hipLaunchKernelGGL((k_search_begin<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{});
+    });
     HIPCHK(hipGetLastError());
     if (e->v.reuse && planes_dev) {
         // boards that continue on a kept subtree have no root to evaluate: one descent-only launch selects their first leaf (boards whose fresh
@@ -1368,60 +1327,53 @@ static int solver_counters(sz_engine* e, hipStream_t s) {
     return SZ_OK;
 }
 
+// what the three option setters share, after their own argument checks and refusals: only between searches; buffers and counters before
+// the assignment, so a call that fails changes no option (a failed allocation of the batch buffers leaves leaves_per_step = 1)
+static int set_options(sz_engine* e, int leaves_per_step, float virtual_loss, int solver, hipStream_t s) {
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;
+    if ((rc = batch_buffers(e, leaves_per_step))) return rc;
+    if (solver && (rc = solver_counters(e, s))) return rc;
+    e->vb.L = leaves_per_step;
+    e->vb.lam = virtual_loss;
+    e->solver = solver;
+    e->v.sstat = solver ? e->d_sstat : nullptr;
+    return SZ_OK;
+}
+
+static bool batching_args_ok(int leaves_per_step, float virtual_loss) {
+    return leaves_per_step >= 1 && leaves_per_step <= SZ_MAX_LEAVES_PER_STEP && virtual_loss >= 0.0f && std::isfinite(virtual_loss);
+}
+
 int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream) {
-    if (!e || leaves_per_step < 1 || leaves_per_step > SZ_MAX_LEAVES_PER_STEP || !(virtual_loss >= 0.0f) || !std::isfinite(virtual_loss)) return SZ_ERR_INVALID;
+    if (!e || !batching_args_ok(leaves_per_step, virtual_loss)) return SZ_ERR_INVALID;
     if (leaves_per_step > 1 && e->v.reuse) return SZ_ERR_INVALID;          // combining the two non-reference options is not supported
     if (leaves_per_step > 1 && e->solver) return SZ_ERR_INVALID;           // nor leaf batching with the solver
     ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Ctl> h(e->v.B);
-    HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (const Ctl& c : h)
-        if ((c.status & ST_SEARCHING) && !(c.status & (ST_DONE | ST_ERROR))) return SZ_ERR_STATE;       // only between searches
-    int rc = batch_buffers(e, leaves_per_step);
-    if (rc) return rc;
-    e->vb.L = leaves_per_step;
-    e->vb.lam = virtual_loss;
-    return SZ_OK;
+    return set_options(e, leaves_per_step, virtual_loss, e->solver, (hipStream_t)stream);
 }
 
 int sz_set_solver(sz_engine* e, int32_t enable, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     if (enable && (e->v.reuse || e->vb.L > 1)) return SZ_ERR_INVALID;      // not combined with subtree reuse or leaf batching
     ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
-    if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
-    if (enable && (rc = solver_counters(e, s))) return rc;
-    e->solver = enable ? 1 : 0;
-    e->v.sstat = enable ? e->d_sstat : nullptr;
-    return SZ_OK;
+    return set_options(e, e->vb.L, e->vb.lam, enable ? 1 : 0, (hipStream_t)stream);
 }
 
 int sz_set_search_options(sz_engine* e, const sz_search_options* opt, void* stream) {
-    if (!e || !opt || opt->leaves_per_step < 1 || opt->leaves_per_step > SZ_MAX_LEAVES_PER_STEP || !(opt->virtual_loss >= 0.0f) || !std::isfinite(opt->virtual_loss))
-        return SZ_ERR_INVALID;
+    if (!e || !opt || !batching_args_ok(opt->leaves_per_step, opt->virtual_loss)) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
-    if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
     const int solver = opt->solver ? 1 : 0;
-    if ((rc = batch_buffers(e, opt->leaves_per_step))) return rc;
-    if (solver && (rc = solver_counters(e, s))) return rc;
-    if (e->v.reuse && (opt->leaves_per_step != e->vb.L || solver != e->solver)) {
-        // a kept subtree built under other settings has no `complete` bits, or its in-flight counts were never written: start fresh
-        hipLaunchKernelGGL(k_drop_subtrees, dim3((e->v.B + 255) / 256), dim3(256), 0, s, e->v);
+    // a kept subtree built under other settings has no `complete` bits, or its in-flight counts were never written: start fresh
+    const bool drop = e->v.reuse && (opt->leaves_per_step != e->vb.L || solver != e->solver);
+    int rc = set_options(e, opt->leaves_per_step, opt->virtual_loss, solver, (hipStream_t)stream);
+    if (rc) return rc;
+    if (drop) {
+        hipLaunchKernelGGL(k_drop_subtrees, dim3((e->v.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->v);
         HIPCHK(hipGetLastError());
     }
-    e->vb.L = opt->leaves_per_step;
-    e->vb.lam = opt->virtual_loss;
-    e->solver = solver;
-    e->v.sstat = solver ? e->d_sstat : nullptr;
     return SZ_OK;
 }
 
@@ -1489,8 +1441,9 @@ int sz_root_children(sz_engine* e, int32_t* action_dev, int32_t* visits_dev, int
 int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    if (e->solver) hipLaunchKernelGGL(k_play<true>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
-    else hipLaunchKernelGGL(k_play<false>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
+    with_search_options(e, [&](auto, auto solve) {
+        hipLaunchKernelGGL(k_play<decltype(solve)::value>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
+    });
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

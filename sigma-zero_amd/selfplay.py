@@ -80,6 +80,34 @@ def search_segments(budgets, L=1, max_shrinks=4, num_searches=None):
     return [hi - lo for lo, hi in zip(cuts[:-1], cuts[1:])]
 
 
+def search_options_of(args):
+    """The search options of args, checked: (leaves_per_step, virtual_loss, solver, combine_options).  All NON-REFERENCE, default off.
+
+    args["leaves_per_step"] = L > 1 gathers up to L leaves per board per network call, steered apart by a virtual loss args["virtual_loss"]
+    per descent in flight (sz_set_leaf_batching); board b's leaf i is network row slot(b)*L + i.
+    args["solver"] = True carries proven results (forced wins, draws and losses) up the tree (sz_set_solver): descents end at proven nodes,
+    refuted moves are not selected, play() takes the proving move of a won root.
+    args["combine_options"] = True lets leaves_per_step > 1, solver and args["reuse_subtree"] run in one search, in any combination
+    (sz_set_search_options); without it each pair is refused."""
+    L, lam = args.get("leaves_per_step", 1), args.get("virtual_loss", 1.0)
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= L <= N.SZ_MAX_LEAVES_PER_STEP:
+        raise ValueError("args['leaves_per_step'] must be an integer in 1..%d, got %r" % (N.SZ_MAX_LEAVES_PER_STEP, L))
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not (math.isfinite(lam) and lam >= 0):
+        raise ValueError("args['virtual_loss'] must be a finite number >= 0, got %r" % (lam,))
+    combine, solver, reuse = args.get("combine_options", False), args.get("solver", False), args.get("reuse_subtree", False)
+    if not isinstance(combine, (bool, np.bool_)):
+        raise ValueError("args['combine_options'] must be True or False, got %r" % (combine,))
+    if L > 1 and reuse and not combine:
+        raise ValueError("args['leaves_per_step'] > 1 and args['reuse_subtree'] exclude each other (without args['combine_options'])")
+    if not isinstance(solver, (bool, np.bool_)):
+        raise ValueError("args['solver'] must be True or False, got %r" % (solver,))
+    if solver and reuse and not combine:
+        raise ValueError("args['solver'] and args['reuse_subtree'] exclude each other (without args['combine_options'])")
+    if solver and L > 1 and not combine:
+        raise ValueError("args['solver'] and args['leaves_per_step'] > 1 exclude each other (without args['combine_options'])")
+    return int(L), float(lam), bool(solver), bool(combine)
+
+
 class SelfPlayEngine:
     def __init__(self, model, args, n_boards, chess960=False, learning=True, device=None, planes_dtype=torch.float32,
                  noise_value=NOISE_REFERENCE, edges_per_board=0):
@@ -94,32 +122,8 @@ class SelfPlayEngine:
         self.S = int(args["num_searches"])
         self.chess960 = bool(chess960)
         self.planes_dtype = planes_dtype
-        # NON-REFERENCE option (default off): args["leaves_per_step"] = L > 1 gathers up to L leaves per board per network call, steered
-        # apart by a virtual loss args["virtual_loss"] per descent in flight (sz_set_leaf_batching); board b's leaf i is network row slot(b)*L + i
-        L, lam = self.args.get("leaves_per_step", 1), self.args.get("virtual_loss", 1.0)
-        if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= L <= N.SZ_MAX_LEAVES_PER_STEP:
-            raise ValueError("args['leaves_per_step'] must be an integer in 1..%d, got %r" % (N.SZ_MAX_LEAVES_PER_STEP, L))
-        if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not (math.isfinite(lam) and lam >= 0):
-            raise ValueError("args['virtual_loss'] must be a finite number >= 0, got %r" % (lam,))
-        # NON-REFERENCE option (default off): args["combine_options"] = True lets leaves_per_step > 1, solver and reuse_subtree run in one
-        # search, in any combination (sz_set_search_options); without it each pair is refused as before
-        combine = self.args.get("combine_options", False)
-        if not isinstance(combine, (bool, np.bool_)):
-            raise ValueError("args['combine_options'] must be True or False, got %r" % (combine,))
-        self.combine = bool(combine)
-        if L > 1 and self.args.get("reuse_subtree", False) and not combine:
-            raise ValueError("args['leaves_per_step'] > 1 and args['reuse_subtree'] exclude each other (without args['combine_options'])")
-        self.L, self.virtual_loss = int(L), float(lam)
-        # NON-REFERENCE option (default off): args["solver"] = True carries proven results (forced wins, draws and losses) up the tree
-        # (sz_set_solver): descents end at proven nodes, refuted moves are not selected, play() takes the proving move of a won root
-        solver = self.args.get("solver", False)
-        if not isinstance(solver, (bool, np.bool_)):
-            raise ValueError("args['solver'] must be True or False, got %r" % (solver,))
-        if solver and self.args.get("reuse_subtree", False) and not combine:
-            raise ValueError("args['solver'] and args['reuse_subtree'] exclude each other (without args['combine_options'])")
-        if solver and L > 1 and not combine:
-            raise ValueError("args['solver'] and args['leaves_per_step'] > 1 exclude each other (without args['combine_options'])")
-        self.solver = bool(solver)
+        # NON-REFERENCE options (default off): leaf batching, the solver and their combinations, see search_options_of
+        self.L, self.virtual_loss, self.solver, self.combine = search_options_of(self.args)
         self.last_steps = 0           # network calls made by the last search()
         self.last_rows = 0            # network rows evaluated by the last search()
         # NON-REFERENCE option (default off): per-board search budgets (set_budgets) with in-search batch shrinking; at most
@@ -280,60 +284,42 @@ class SelfPlayEngine:
         N.check(N.lib().sz_pending_boards(self._e, C.byref(n), self._stream()), "sz_pending_boards")
         return int(n.value)
 
+    def _run_steps(self, ev, n):
+        """n network calls and search steps on the n_rows in use"""
+        rows = self.n_rows * self.L
+        planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
+        for _ in range(n):
+            policy, value = ev(planes)
+            self.step(policy, value)
+        self.last_steps += n
+        self.last_rows += n * rows
+
+    def _run_pending(self, ev):
+        """leaf batching: a collision ends a board's gather early, so the number of steps depends on the trees (at most S): after the
+        ceil(S/L) steps that run without a host sync, one step at a time until no board waits for the network"""
+        if self.L > 1:
+            while self.last_steps < self.S and self.pending_boards():
+                self._run_steps(ev, 1)
+
     @torch.no_grad()
     def search(self, evaluator=None):
-        """All num_searches simulations for every active board (mcts.py:49-109).  The network sees n_rows * leaves_per_step rows."""
+        """All num_searches simulations for every active board (mcts.py:49-109).  The network sees n_rows * leaves_per_step rows.
+        With budgets set the steps run in segments that end where boards run out of budget (search_segments), and after each segment
+        the batch shrinks to the boards that still search; with max_shrinks > 0 it is also shrunk once right after the roots were made:
+        boards with budget 0 and terminal roots never take a row.  Without budgets there is one segment and no shrink."""
         ev = evaluator or self.evaluate
         self.begin()
         self.last_steps = self.last_rows = 0
         if self.n_rows <= 0:
             return
-        if self.budgets is not None:
-            return self._search_budgeted(ev)
-        rows = self.n_rows * self.L
-        planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
-        if self.L == 1:
-            for _ in range(self.S):
-                policy, value = ev(planes)
-                self.step(policy, value)
-            self.last_steps, self.last_rows = self.S, self.S * rows
-            return
-        # leaf batching: a collision ends a board's gather early, so the number of steps depends on the trees (at most S): ceil(S/L) steps
-        # without a host sync, then one step at a time until no board waits for the network
-        n = -(-self.S // self.L)
-        while n > 0:
-            for _ in range(n):
-                policy, value = ev(planes)
-                self.step(policy, value)
-            self.last_steps += n
-            self.last_rows += n * rows
-            n = 1 if self.last_steps < self.S and self.pending_boards() else 0
-
-    def _search_budgeted(self, ev):
-        """search() with budgets set: the steps run in segments that end where boards run out of budget (search_segments), and after
-        each segment the batch shrinks to the boards that still search.  With max_shrinks > 0 the batch is also shrunk once right after
-        the roots were made: boards with budget 0 and terminal roots never take a row."""
         segs = search_segments(self.budgets, self.L, self.max_shrinks, self.S)
-        if self.max_shrinks > 0 and self._compact_searching() == 0:
+        if self.budgets is not None and self.max_shrinks > 0 and self._compact_searching() == 0:
             return                                          # nothing to search: every board was done at begin
         for i, n in enumerate(segs):
-            rows = self.n_rows * self.L
-            planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
-            for _ in range(n):
-                policy, value = ev(planes)
-                self.step(policy, value)
-            self.last_steps += n
-            self.last_rows += n * rows
+            self._run_steps(ev, n)
             if i + 1 < len(segs) and self._compact_searching() == 0:
                 return
-        if self.L > 1:                                      # collisions: one step at a time until no board waits for the network
-            rows = self.n_rows * self.L
-            planes = self.planes if rows == self.planes.shape[0] else self.planes[:rows]
-            while self.last_steps < self.S and self.pending_boards():
-                policy, value = ev(planes)
-                self.step(policy, value)
-                self.last_steps += 1
-                self.last_rows += rows
+        self._run_pending(ev)
 
     def stats(self):
         st = N.sz_stats()
