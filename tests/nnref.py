@@ -58,6 +58,21 @@ def folded_convs(net, operands=None):
     return [(round_to(w, operands), b) for w, b in convs]
 
 
+def conv2d(x, w, b, padding=0):
+    """F.conv2d in double; on the CPU as unfold + one matrix product (torch's direct fp64 convolution takes 3-4x as long there (measured: 128 vs 37 ms for 256 -> 256 channels on 4 boards), and the CPU tests walk 39 of them per network)"""
+    if x.is_cuda:
+        return F.conv2d(x, w, b, padding=padding)
+    B, co = x.shape[0], w.shape[0]
+    y = w.reshape(co, -1) @ F.unfold(x, w.shape[2], padding=padding)
+    return (y if b is None else y + b.view(1, co, 1)).view(B, co, x.shape[2], x.shape[3])
+
+
+def _peak(peaks, site, v):
+    if peaks is not None:
+        peaks[site] = v.abs().flatten(1).max(1).values
+    return v
+
+
 class Emulated:
     """policyNN `net` in double with FastPolicyNet's rounding points for `operands` (None, "bf16", "fp16"); n_blocks < 19 truncates the tower as
     net.resnet_blocks[:n_blocks] does.  Tensors are on `device` (fp64 convolutions: keep the batch to a few hundred boards)."""
@@ -81,20 +96,29 @@ class Emulated:
     def r(self, x):
         return round_to(x, self.op)
 
-    def tower(self, planes):
-        """planes [B, 119, 8, 8] (0 / 1, any dtype) -> tower output [B, 256, 8, 8] double (values of the operand type when rounding)"""
+    def tower(self, planes, peaks=None):
+        """planes [B, 119, 8, 8] (0 / 1, any dtype) -> tower output [B, 256, 8, 8] double (values of the operand type when rounding).
+        peaks: a dict that receives, per site, each board's largest |value handed to the rounding| (see site_maxima)"""
         x = planes.to(self.dev).double()
         w, b = self.stem
-        x = self.r(torch.relu(F.conv2d(x, w, b, padding=1)))
-        for w1, b1, w2, b2 in self.blocks:
-            t = self.r(torch.relu(F.conv2d(x, w1, b1, padding=1)))
-            x = torch.relu(self.r(F.conv2d(t, w2, b2, padding=1) + x))
+        x = self.r(torch.relu(_peak(peaks, "stem", conv2d(x, w, b, padding=1))))
+        for k, (w1, b1, w2, b2) in enumerate(self.blocks):
+            t = self.r(torch.relu(_peak(peaks, "block%d.t" % k, conv2d(x, w1, b1, padding=1))))
+            x = torch.relu(self.r(_peak(peaks, "block%d.out" % k, conv2d(t, w2, b2, padding=1) + x)))
         return x
 
-    def heads(self, x, inference=False):
+    def site_maxima(self, planes):
+        """{site: [B] largest |v| of each board} over every value the kernels hand to a 16-bit pack, BEFORE the rounding and before the ReLU (the kernels pack, then
+        take the ReLU on the packed pair: a value <= -65520 becomes -inf at the pack too), in the order the kernels compute them: stem, block0.t, block0.out, ...,
+        p1 (the policy head's stored intermediate).  f16 rounds to inf from 65520 on: the first site whose maximum reaches it is where the first inf is created."""
+        peaks = {}
+        self.heads(self.tower(planes, peaks), peaks=peaks)
+        return peaks
+
+    def heads(self, x, inference=False, peaks=None):
         """tower output [B, 256, 8, 8] -> (logits or policy [B, 4672], value [B, 1]) as k_heads16_bf16 + k_value_head compute them"""
         x = x.to(self.dev).double()
-        t = self.r(torch.relu(F.conv2d(x, self.p1[0], self.p1[1])))
+        t = self.r(torch.relu(_peak(peaks, "p1", conv2d(x, self.p1[0], self.p1[1]))))
         logits = torch.flatten(F.conv2d(t, self.wp2, self.bp2), 1)
         policy = torch.softmax(logits, 1) if inference else logits
         v = torch.relu(torch.flatten(F.conv2d(x, self.wv, self.bv), 1))
@@ -175,3 +199,122 @@ def report(net, planes=None):
         lines.append("block %2d  max|w| %9.3g %9.3g  max|t| %9.3g  max|x| %9.3g" % (k, float(w1.abs().max()), float(w2.abs().max()), float(t.abs().max()), float(x.abs().max())))
     print("\n".join(lines))
     return float(x.abs().max())
+
+
+# ---- networks that reach a chosen magnitude at a chosen place (tests of f16's range) -------------------------------------------------------------------------
+F16_INF_FROM = 65520.0                                     # f32 -> f16 (round to nearest even) gives inf from 65504 + half a quantum (32 / 2) on
+
+
+def site_names(n_blocks):
+    return ["stem"] + [s % k for k in range(n_blocks) for s in ("block%d.t", "block%d.out")] + ["p1"]
+
+
+def _site_layer(net, site):
+    """(convolution, BatchNorm, padding) that produce `site`"""
+    if site == "stem":
+        return net.conv1, net.norm_layer, 1
+    if site == "p1":
+        return net.conv_p1, net.p_norm1, 0
+    blk, which = site.split(".")
+    blk = net.resnet_blocks[int(blk[5:])]
+    return (blk.conv1, blk.bn1, 1) if which == "t" else (blk.conv2, blk.bn2, 1)
+
+
+def _site_input(em, x, site):
+    """(input of the site's convolution, residual added behind it or None) under emulation `em`: what the layers in front of the site hand it"""
+    x = em.r(torch.relu(conv2d(x.to(em.dev).double(), *em.stem, padding=1))) if site != "stem" else x.to(em.dev).double()
+    if site == "stem":
+        return x, None
+    for k, (w1, b1, w2, b2) in enumerate(em.blocks):
+        if site == "block%d.t" % k:
+            return x, None
+        t = em.r(torch.relu(conv2d(x, w1, b1, padding=1)))
+        if site == "block%d.out" % k:
+            return t, x
+        x = torch.relu(em.r(conv2d(t, w2, b2, padding=1) + x))
+    assert site == "p1", site
+    return x, None
+
+
+@torch.no_grad()
+def scale_site(net, site, target, x, operands=None, rtol=0.01):
+    """a copy of policyNN `net` in which ONE BatchNorm's gamma and beta (the one that produces `site`) are multiplied by a common factor, found by bisection on
+    Emulated(net, operands), such that the largest |value handed to the rounding| at `site` over the boards `x` [B, 119, 8, 8] is within `rtol` of `target`.
+    The layers in front of the site do not change, so their output is computed once and each probe is the site's own convolution.  Returns (net, reached)."""
+    import copy
+    net = copy.deepcopy(net)
+    conv, bn, pad = _site_layer(net, site)
+    inp, res = _site_input(Emulated(net, operands), x, site)
+    g0, b0 = bn.weight.detach().double().clone(), bn.bias.detach().double().clone()
+
+    def peak(s):
+        bn.weight.copy_(g0 * s); bn.bias.copy_(b0 * s)
+        w, b = fold_bn(conv.weight, bn, f32=operands is not None)
+        v = conv2d(inp, round_to(w, operands).to(inp.device), b.to(inp.device), padding=pad)
+        return float((v if res is None else v + res).abs().max())
+
+    s = target / peak(1.0)                                 # exact where the site is its convolution alone (no residual), up to the roundings
+    m = peak(s)
+    if abs(m / target - 1) > rtol:
+        lo = hi = s
+        while peak(lo) > target:
+            lo /= 4
+        while peak(hi) < target:
+            hi *= 4
+        for _ in range(200):
+            s = (lo * hi) ** 0.5
+            m = peak(s)
+            if abs(m / target - 1) <= rtol:
+                break
+            lo, hi = (s, hi) if m < target else (lo, s)
+    assert abs(m / target - 1) <= rtol, (site, target, m)
+    return net, m
+
+
+@torch.no_grad()
+def site_net(net, site, target, x, quiet=1000.0, operands=None, rtol=0.01):
+    """scale_site(net, site, target, x, operands, rtol), then every layer BEHIND the site is turned down (its BatchNorm's gamma and beta times a factor < 1, in fp64 on
+    Emulated(net, None)) so that the site is the one place where the network is that large: a later `t` or `p1` that exceeds `quiet` is scaled to `quiet`; a later
+    convolution into the residual stream is scaled so that it moves the stream by at most target / 1000 (19 blocks: 2 %), since the stream itself carries the
+    site's magnitude to the end of the tower when the site is the stem or a block's output.  Returns the new net."""
+    net, _ = scale_site(net, site, target, x, operands, rtol)
+    names = site_names(len(net.resnet_blocks))
+    em = Emulated(net, None)
+    x = x.double()
+    cur, t = None, None
+    for name in names:
+        conv, bn, pad = _site_layer(net, name)
+        w, b = fold_bn(conv.weight, bn, f32=False)
+        is_out = name.endswith(".out")
+        inp = x if name == "stem" else (t if is_out else cur)
+        v = conv2d(inp, w, b, padding=pad)
+        if names.index(name) > names.index(site):
+            m, cap = float(v.abs().max()), (target / 1000 if is_out else quiet)
+            if m > cap:
+                bn.weight.mul_(cap / m); bn.bias.mul_(cap / m)
+                v = v * (cap / m)
+        if is_out:
+            cur = torch.relu(v + cur)
+        elif name == "stem":
+            cur = torch.relu(v)
+        else:
+            t = torch.relu(v)
+    return net
+
+
+@torch.no_grad()
+def benign_stats(net, seed):
+    """BatchNorm statistics of a healthy network (activations O(1) everywhere), in place: the starting point of the range tests"""
+    g = torch.Generator().manual_seed(seed)
+    for m in net.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            n = m.num_features
+            m.running_mean.copy_(torch.randn(n, generator=g) * 0.05); m.running_var.copy_(0.5 + torch.rand(n, generator=g))
+            m.weight.copy_(0.7 + 0.6 * torch.rand(n, generator=g)); m.bias.copy_(torch.randn(n, generator=g) * 0.05)
+    net.conv_p2.bias.copy_(torch.randn(net.conv_p2.bias.shape, generator=g) * 0.5)
+    return net
+
+
+def random_planes(n, seed, density=0.12):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(n, 119, 8, 8, generator=g) < density).double()

@@ -113,3 +113,51 @@ def test_trained_regime_is_what_it_says():
     from nnref import report
     xmax = report(net)
     assert 30 < xmax < 3000, xmax                                             # the residual stream is O(100) after block 19
+
+
+# ---- the inputs of the f16 range tests (tests/f16range.py): networks that reach f16's rounding-to-inf point at one chosen site -----------------------------------
+import f16range as R
+from nnref import F16_INF_FROM, scale_site, site_names
+
+
+@pytest.mark.parametrize("site", R.SITES)
+def test_range_nets_reach_their_target_at_their_site_and_nowhere_else_first(site):
+    """per site: scale_site's bisection reaches its target to 1 %; the 0.9 x 65504 net stays below f16's rounding-to-inf point 65520 at EVERY site, with f16-rounded
+    weights (what the kernels multiply) as without rounding; the 2 x 65504 net has its FIRST excess at the intended site, every site in front of it is O(1)"""
+    x = R.boards()
+    for target in (R.IN_RANGE, R.OUT_OF_RANGE):
+        _, reached = scale_site(R.base_net(), site, target, x)
+        assert abs(reached / target - 1) <= 0.01, (site, target, reached)
+    names = site_names(19)
+    for op in (None, "fp16"):
+        peaks = Emulated(R.net_at(site, R.IN_RANGE), op).site_maxima(x)
+        assert list(peaks) == names
+        worst = max(float(v.max()) for v in peaks.values())
+        assert abs(float(peaks[site].max()) / R.IN_RANGE - 1) <= 0.011 and worst < F16_INF_FROM * 0.95, (site, op, float(peaks[site].max()), worst)
+    peaks = Emulated(R.net_at(site, R.OUT_OF_RANGE), None).site_maxima(x)
+    over = [n for n in names if float(peaks[n].max()) >= F16_INF_FROM]
+    assert over and over[0] == site, (site, over[:3])
+    assert all(float(peaks[n].max()) < 10 for n in names[:names.index(site)]), site
+    assert float(peaks[site].min()) >= F16_INF_FROM, (site, peaks[site])          # every one of the four boards overflows there
+
+
+def test_range_boundary_nets_straddle_the_rounding_to_inf_point():
+    """the stem-only nets of the boundary test: the largest stem value on f16-rounded weights is 65400 resp. 65650 to 1e-5, i.e. 1.8e-3 below / 2.0e-3 above 65520
+    (the kernel's f32 accumulation of at most 1071 terms is off by at most 1071 x 2^-24 = 6.4e-5 relative); round_to agrees: finite below, inf above"""
+    for target, finite in ((65400.0, True), (65650.0, False)):
+        net, reached = R.stem_net_at(target)
+        peaks = Emulated(net, "fp16", n_blocks=0).site_maxima(R.boards())
+        assert abs(float(peaks["stem"].max()) / target - 1) <= 1e-5 and reached == float(peaks["stem"].max()), (target, reached)
+        assert bool(torch.isfinite(round_to(peaks["stem"].max(), "fp16"))) == finite
+        assert bool(torch.isfinite(Emulated(net, "fp16", n_blocks=0).tower(R.boards())).all()) == finite
+
+
+def test_one_bad_board_net_has_a_gap_around_the_rounding_to_inf_point():
+    """one board's peak at block9.t is above 65520 and every other board's below, each by more than 2e-3 relative (30 x the f32 accumulation error); every site
+    in front of block9.t is O(1) and, for the three good boards, every site behind it is in range"""
+    net, bad, peaks = R.one_bad_board()
+    p = peaks["block9.t"]
+    good = [b for b in range(R.N_BOARDS) if b != bad]
+    assert float(p[bad]) > F16_INF_FROM * 1.002 and float(p[good].max()) < F16_INF_FROM * 0.998, (bad, p.tolist())
+    clean = Emulated(net, "fp16").site_maxima(R.boards()[good])
+    assert max(float(v.max()) for v in clean.values()) < F16_INF_FROM * 0.998
