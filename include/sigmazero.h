@@ -424,6 +424,17 @@ int sz_nn_pack_head16(const float* w_in, uint16_t* out);
 int sz_nn_heads_bf16(const void* x, const void* w_p1_packed, const float* b_p1, const void* w_p2_packed, const float* b_p2, const float* wv, float bv,
                      const float* fc1_w_t, const float* fc1_b, const float* fc2_w, float fc2_b, float* probs, float* value, float* v1_scratch,
                      int32_t n_boards, int32_t do_softmax, void* stream);
+/* sz_nn_tower_bf16 / sz_nn_heads_bf16 / sz_nn_forward_split with a range flag for f16 operands (SZ_NN_F16): the device word *range_flag is OR-ed with 1 when an
+ * activation that the kernels stored as f16 (stem, t, block output, the policy head's t; split precision: the hi image) was 65520 or more, i.e. +inf.  The next convolution makes NaN of such a value and the
+ * integer ReLU can erase that NaN again, so the outputs alone do not show it.  NULL, or bf16 operands: nothing is reported. */
+int sz_nn_tower_f16_checked(const void* planes, const void* const* w_packed, const float* const* bias, int32_t n_blocks, void* out,
+                            int32_t n_boards, int32_t flags, uint32_t* range_flag, void* stream);
+int sz_nn_heads_f16_checked(const void* x, const void* w_p1_packed, const float* b_p1, const void* w_p2_packed, const float* b_p2, const float* wv, float bv,
+                            const float* fc1_w_t, const float* fc1_b, const float* fc2_w, float fc2_b, float* probs, float* value, float* v1_scratch,
+                            int32_t n_boards, int32_t do_softmax, uint32_t* range_flag, void* stream);
+int sz_nn_forward_split_checked(const void* planes, const void* w_stream, const float* bias, int32_t n_blocks, const void* w_p2_packed, const float* b_p2,
+                                const float* wv, float bv, const float* fc1_w_t, const float* fc1_b, const float* fc2_w, float fc2_b, float* probs, float* value,
+                                float* v1_scratch, float* tower_out, int32_t n_boards, int32_t do_softmax, int32_t flags, uint32_t* range_flag, void* stream);
 
 const char* sz_error_string(int code);
 int sz_device_count(void);

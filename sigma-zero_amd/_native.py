@@ -94,6 +94,10 @@ EXPORTS = {
     "sz_set_root_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sz_nn_debug_tower_stamps": (C.c_int, [C.c_void_p, C.c_int32]),
     "sz_nn_heads_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p]),
+    "sz_nn_tower_f16_checked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sz_nn_heads_f16_checked": (C.c_int, [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2),
+    "sz_nn_forward_split_checked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sz_nn_value_head_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "sz_nn_pack_head16": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sz_nn_pack_head16_f16": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -605,7 +605,7 @@ template <int WGB, class E = ElemBF16> struct EpiResidual16 {
 
 // epilogue of ONE accumulator tile (channel tile i, position tile j): relu?(acc) -> bf16 -> LDS image (the accumulators started at the bias)
 template <int WGB, class E = ElemBF16>
-__device__ __forceinline__ void acc_tile_to_lds16(unsigned char* lds, const f32x4 (&acc)[4][4 * WGB], int i, int j, bool relu) {
+__device__ __forceinline__ void acc_tile_to_lds16(unsigned char* lds, const f32x4 (&acc)[4][4 * WGB], int i, int j, bool relu, RangeSeen& seen) {
     constexpr int OPITCH = NN_COUT * 2 + NN_PAD16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = tile_row<WGB>(j, lane & 15), co = (wave * 4 + i) * 16 + 4 * (lane >> 4);
@@ -613,12 +613,12 @@ __device__ __forceinline__ void acc_tile_to_lds16(unsigned char* lds, const f32x
     uint2 o;
     o.x = E::pack2(v[0], v[1]);
     o.y = E::pack2(v[2], v[3]);
-    if (relu) { o.x = relu_bf16x2(o.x); o.y = relu_bf16x2(o.y); }
+    if (relu) { o.x = relu_bf16x2(o.x); o.y = relu_bf16x2(o.y); range_track<E>(seen, o.x, o.y); }
     *(uint2*)(lds + epi_slot16(row, co)) = o;
 }
 // the same with the residual: x <- relu(acc + x) in place on the LDS image (f32 add, one bf16 rounding)
 template <int WGB, class E = ElemBF16>
-__device__ __forceinline__ void acc_tile_residual16(unsigned char* xlds, const f32x4 (&acc)[4][4 * WGB], int i, int j) {
+__device__ __forceinline__ void acc_tile_residual16(unsigned char* xlds, const f32x4 (&acc)[4][4 * WGB], int i, int j, RangeSeen& seen) {
     constexpr int OPITCH = NN_COUT * 2 + NN_PAD16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = tile_row<WGB>(j, lane & 15), co = (wave * 4 + i) * 16 + 4 * (lane >> 4);
@@ -628,12 +628,32 @@ __device__ __forceinline__ void acc_tile_residual16(unsigned char* xlds, const f
     uint2 o;
     o.x = relu_bf16x2(E::pack2(v[0] + E::lo(r.x), v[1] + E::hi(r.x)));
     o.y = relu_bf16x2(E::pack2(v[2] + E::lo(r.y), v[3] + E::hi(r.y)));
+    range_track<E>(seen, o.x, o.y);
     *px = o;
 }
 
+// f16 range tracking of the tiles that EpiTile16 / EpiResidual16 stored under the last tap (the first position half of the two-board form): every lane reads its
+// own 16 stored pairs back from the image, after the K loop, where registers are free again; the staged epilogue inside the K loop stays as it is (tracking
+// there cost two spilled registers and 5 % of the f16 tower).  A lane reads only what it wrote itself: no barrier.
+template <int WGB, class E>
+__device__ __forceinline__ void range_track_first_half(const unsigned char* img, RangeSeen& seen) {
+    if constexpr (std::is_same<E, ElemF16>::value) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int j = 0; j < 2 * WGB; j++)
+#pragma unroll
+            for (int i = 0; i < 4; i += 2) {
+                const uint2 o0 = *(const uint2*)(img + epi_slot16(tile_row<WGB>(j, lane & 15), (wave * 4 + i) * 16 + 4 * (lane >> 4)));
+                const uint2 o1 = *(const uint2*)(img + epi_slot16(tile_row<WGB>(j, lane & 15), (wave * 4 + i + 1) * 16 + 4 * (lane >> 4)));
+                const i16x2 m = __builtin_elementwise_max(__builtin_elementwise_max(__builtin_bit_cast(i16x2, o0.x), __builtin_bit_cast(i16x2, o0.y)), __builtin_bit_cast(i16x2, o1.x));
+                range_track<E>(seen, __builtin_bit_cast(uint32_t, m), o1.y);
+            }
+    }
+}
+
 // bias == nullptr: the accumulators already started at the bias (conv_kloop16's `bias` argument)
-template <int WGB, class E = ElemBF16>
-__device__ __forceinline__ void acc_to_lds16(unsigned char* lds, const f32x4 (&acc)[4][4 * WGB], const float* __restrict__ bias, bool relu) {
+template <int WGB, class E = ElemBF16, class SEEN = RangeSeen /* or uint32_t: see range_track */>
+__device__ __forceinline__ void acc_to_lds16(unsigned char* lds, const f32x4 (&acc)[4][4 * WGB], const float* __restrict__ bias, bool relu, SEEN* seen = nullptr) {
     constexpr int OPITCH = NN_COUT * 2 + NN_PAD16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int p16 = lane & 15, kg = lane >> 4;
@@ -649,6 +669,7 @@ __device__ __forceinline__ void acc_to_lds16(unsigned char* lds, const f32x4 (&a
             o.x = E::pack2(v[0], v[1]);
             o.y = E::pack2(v[2], v[3]);
             if (relu) { o.x = relu_bf16x2(o.x); o.y = relu_bf16x2(o.y); }
+            if (relu && seen) range_track<E>(*seen, o.x, o.y);
             *(uint2*)(lds + row * OPITCH + co * 2) = o;
         }
     }
@@ -926,7 +947,8 @@ __global__ __launch_bounds__(256) void k_value_head(const uint16_t* __restrict__
 template <class E /* operand element of x, t and the packed weights: ElemBF16 or ElemF16 */>
 __global__ __launch_bounds__(256, 2) void k_heads16_bf16(const uint16_t* __restrict__ x, const uint4* __restrict__ w_p1, const float* __restrict__ b_p1,
                                                           const uint4* __restrict__ w_p2, const float* __restrict__ b_p2, const float* __restrict__ wv, float bv,
-                                                          float* __restrict__ probs, float* __restrict__ v1_out, int n_boards, int do_softmax) {
+                                                          float* __restrict__ probs, float* __restrict__ v1_out, int n_boards, int do_softmax,
+                                                          unsigned int* __restrict__ range_flag /* f16: see range_track; may be NULL */) {
     constexpr int WGB = 2, PITCH = NN_COUT * 2 + NN_PAD16;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     float* red = (float*)(lds + WGB * 64 * PITCH + NN_ZERO16);    // [4 waves][2]: softmax max / sum exchange between the two waves of a board
@@ -960,7 +982,9 @@ __global__ __launch_bounds__(256, 2) void k_heads16_bf16(const uint16_t* __restr
     f32x4 acc[4][4 * WGB];
     conv_kloop16<256, 1, WGB, 2, false, 0, false, E>(lds, w_p1, acc, false, false, nullptr, 0, b_p1);
     __syncthreads();
-    acc_to_lds16<WGB, E>(lds, acc, nullptr, true);            // t over x, in the layout the MFMA B operand is read from
+    uint32_t seen = 0;
+    acc_to_lds16<WGB, E>(lds, acc, nullptr, true, &seen);     // t over x, in the layout the MFMA B operand is read from
+    range_report<E>(seen, range_flag);
     __syncthreads();
     // policy logits: wave -> board wave>>1, position tiles 2*(wave&1) + {0,1}; 5 channel tiles (73 padded to 80), K = 256
     const int pboard = wave >> 1, j0 = (wave & 1) * 2;
@@ -1089,6 +1113,7 @@ struct TowerParams {
     const float* b[NN_MAX_CONVS];
     unsigned long long* pace;                              // 8 arrival counters, one per XCD residue class of blockIdx (XCD-paced tile rounds); NULL = off (SZ_NN_PACE=0)
     unsigned long long pace_base;                          // arrivals per counter before this launch
+    unsigned int* range_flag;                              // f16 operands: OR-ed with 1 when a stored activation left f16's range (range_track); NULL = not reported
 };
 
 // STAMP = diagnostic build (tools/tower_stamps.py): s_memtime stamps around the phases of block 3 of a workgroup's second tile (its only tile at small batches) go to
@@ -1122,6 +1147,8 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
     f32x4 acc[4][4 * WGB];
     constexpr int TRING = WGB == 1 ? NN_ONE_RING : 4;
     uint4 ring[TRING][4];                                              // next convolution's first weight fragments, fetched under the current epilogue
+    RangeSeen seen;                                                    // f16: per-half maximum of every pair this lane stored (range_track)
+    if constexpr (std::is_same<E, ElemF16>::value) seen = range_none();
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int board0 = tile * WGB;
         TILESTAMP(0);
@@ -1146,18 +1173,19 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
         conv_kloop16<128, 9, WGB, 4, true, 0, false, E>(lds, prm.w[0], acc, false, false, ring, IMG, prm.b[0], addr_tab);  // stem (reads bufT): x = relu(bn(conv1(planes)))
         TILESTAMP(3);
         if (n_blocks > 0) conv_prefetch16<TRING>(prm.w[1], ring);
-        acc_to_lds16<WGB, E>(bufX, acc, nullptr, true);
+        acc_to_lds16<WGB, E>(bufX, acc, nullptr, true, &seen);
         __syncthreads();
         TILESTAMP(4);
         for (int blk = 0; blk < n_blocks; blk++) {
             const bool stamp_now = STAMP_ && blk == 3 && tile == stamp_tile;
             TSTAMP(0);
             wave_stagger();
-            auto epi_t = [&](int i, int j) { acc_tile_to_lds16<WGB, E>(bufT, acc, i, j, true); };          // t = relu(bn1(conv1(x))); bufT is idle
+            auto epi_t = [&](int i, int j) { acc_tile_to_lds16<WGB, E>(bufT, acc, i, j, true, seen); };          // t = relu(bn1(conv1(x))); bufT is idle
             if constexpr (WGB == 2) conv_kloop16<256, 9, WGB, 4, true, ABL, false, E>(bufX, prm.w[1 + 2 * blk], acc, false, false, ring, 0, prm.b[1 + 2 * blk], addr_tab, EpiTile16<WGB, E>(bufT, acc));
             else conv_kloop16_one<ABL, E>(bufX, prm.w[1 + 2 * blk], acc, ring, 0, prm.b[1 + 2 * blk], addr_tab);
             TSTAMP(1);
             conv_prefetch16<TRING>(prm.w[2 + 2 * blk], ring);
+            if constexpr (WGB == 2) range_track_first_half<WGB, E>(bufT, seen);
 #pragma unroll
             for (int j = (WGB == 2 ? 2 * WGB : 0); j < 4 * WGB; j++)           // second position half; the first went out under the last tap (2-board form)
 #pragma unroll
@@ -1166,11 +1194,12 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
             __syncthreads();
             TSTAMP(3);
             wave_stagger();
-            auto epi_x = [&](int i, int j) { acc_tile_residual16<WGB, E>(bufX, acc, i, j); };             // x = relu(bn2(conv2(t)) + x): own elements only, nobody reads bufX now
+            auto epi_x = [&](int i, int j) { acc_tile_residual16<WGB, E>(bufX, acc, i, j, seen); };             // x = relu(bn2(conv2(t)) + x): own elements only, nobody reads bufX now
             if constexpr (WGB == 2) conv_kloop16<256, 9, WGB, 4, true, ABL, false, E>(lds, prm.w[2 + 2 * blk], acc, false, false, ring, IMG, prm.b[2 + 2 * blk], addr_tab, EpiResidual16<WGB, E>(bufX, acc));   // reads bufT
             else conv_kloop16_one<ABL, E>(lds, prm.w[2 + 2 * blk], acc, ring, IMG, prm.b[2 + 2 * blk], addr_tab);
             TSTAMP(4);
             if (blk + 1 < n_blocks) conv_prefetch16<TRING>(prm.w[3 + 2 * blk], ring);
+            if constexpr (WGB == 2) range_track_first_half<WGB, E>(bufX, seen);
 #pragma unroll
             for (int j = (WGB == 2 ? 2 * WGB : 0); j < 4 * WGB; j++)
 #pragma unroll
@@ -1184,6 +1213,7 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
         lds_to_out<WGB, NN_PAD16>(bufX, nullptr, out, board0, n_boards, false);
         TILESTAMP(6);
     }
+    range_report<E>(seen, prm.range_flag);
 }
 
 
@@ -1335,8 +1365,14 @@ int sz_nn_debug_tower_stamps(void* dev_buffer, int32_t mode) { g_tower_stamps = 
 // Whole tower (stem + n_blocks BasicBlocks) in one persistent launch.  planes [n_boards,64,128] bf16 (NHWC, 119 real channels),
 // out [n_boards,64,256] bf16.  w/b: n_convs = 1 + 2*n_blocks device pointers each (weights from sz_nn_pack_weights16, stem with
 // cin_padded 128; biases [256] f32 with BatchNorm folded), given as HOST arrays of device pointers.
-static int tower_launch(const void* planes, const void* const* w_packed, const float* const* bias, int32_t n_blocks, void* out, int32_t n_boards, int32_t flags, void* stream);
+static int tower_launch(const void* planes, const void* const* w_packed, const float* const* bias, int32_t n_blocks, void* out, int32_t n_boards, int32_t flags, unsigned int* range_flag, void* stream);
 int sz_nn_tower_bf16(const void* planes, const void* const* w_packed, const float* const* bias, int32_t n_blocks, void* out, int32_t n_boards, int32_t flags, void* stream) {
+    return sz_nn_tower_f16_checked(planes, w_packed, bias, n_blocks, out, n_boards, flags, nullptr, stream);
+}
+// sz_nn_tower_bf16 with a range flag: with SZ_NN_F16 the device word *range_flag is OR-ed with 1 when an activation the tower stored (stem, t, block output) had
+// left f16's range; ignored with bf16 operands
+int sz_nn_tower_f16_checked(const void* planes, const void* const* w_packed, const float* const* bias, int32_t n_blocks, void* out, int32_t n_boards, int32_t flags,
+                            uint32_t* range_flag, void* stream) {
     if (!planes || !w_packed || !bias || !out || n_boards <= 0 || n_blocks < 0 || 1 + 2 * n_blocks > NN_MAX_CONVS) return SZ_ERR_INVALID;
     StreamDeviceGuard _guard(stream);
     // A last round of at most #CUs boards runs in the one-board form as a launch of its own: 768 boards on 256 CUs = one round of 256 two-board tiles + 256 boards with a
@@ -1345,15 +1381,16 @@ int sz_nn_tower_bf16(const void* planes, const void* const* w_packed, const floa
     if (n_boards > 2 * n_cu && rem > 0 && rem <= n_cu && !(flags & (SZ_NN_TOWER_WGB1 | SZ_NN_TOWER_WGB2)) && !g_tower_stamps) {
         const int head = n_boards - rem;
         const size_t plane_bytes = (flags & SZ_NN_IN_BITS) ? 64 * sizeof(uint4) : (size_t)64 * 128 * 2, out_bytes = (size_t)64 * NN_COUT * 2;
-        const int rc = tower_launch(planes, w_packed, bias, n_blocks, out, head, flags | SZ_NN_TOWER_WGB2, stream);
+        const int rc = tower_launch(planes, w_packed, bias, n_blocks, out, head, flags | SZ_NN_TOWER_WGB2, (unsigned int*)range_flag, stream);
         if (rc != SZ_OK) return rc;
-        return tower_launch((const unsigned char*)planes + head * plane_bytes, w_packed, bias, n_blocks, (unsigned char*)out + head * out_bytes, rem, flags | SZ_NN_TOWER_WGB1, stream);
+        return tower_launch((const unsigned char*)planes + head * plane_bytes, w_packed, bias, n_blocks, (unsigned char*)out + head * out_bytes, rem, flags | SZ_NN_TOWER_WGB1, (unsigned int*)range_flag, stream);
     }
-    return tower_launch(planes, w_packed, bias, n_blocks, out, n_boards, flags, stream);
+    return tower_launch(planes, w_packed, bias, n_blocks, out, n_boards, flags, (unsigned int*)range_flag, stream);
 }
-static int tower_launch(const void* planes, const void* const* w_packed, const float* const* bias, int32_t n_blocks, void* out, int32_t n_boards, int32_t flags, void* stream) {
+static int tower_launch(const void* planes, const void* const* w_packed, const float* const* bias, int32_t n_blocks, void* out, int32_t n_boards, int32_t flags, unsigned int* range_flag, void* stream) {
     TowerParams prm;
     memset(&prm, 0, sizeof prm);
+    prm.range_flag = range_flag;
     for (int i = 0; i < 1 + 2 * n_blocks; i++) {
         if (!w_packed[i] || !bias[i]) return SZ_ERR_INVALID;
         prm.w[i] = (const uint4*)w_packed[i]; prm.b[i] = bias[i];
@@ -1485,6 +1522,12 @@ int sz_nn_value_head_bf16(const void* x, const float* wv, float bv, const float*
 int sz_nn_heads_bf16(const void* x, const void* w_p1_packed, const float* b_p1, const void* w_p2_packed, const float* b_p2, const float* wv, float bv,
                      const float* fc1_w_t, const float* fc1_b, const float* fc2_w, float fc2_b, float* probs, float* value, float* v1_scratch,
                      int32_t n_boards, int32_t do_softmax, void* stream) {
+    return sz_nn_heads_f16_checked(x, w_p1_packed, b_p1, w_p2_packed, b_p2, wv, bv, fc1_w_t, fc1_b, fc2_w, fc2_b, probs, value, v1_scratch, n_boards, do_softmax, nullptr, stream);
+}
+// sz_nn_heads_bf16 with a range flag: with SZ_NN_F16 the device word *range_flag is OR-ed with 1 when the policy head's stored intermediate t left f16's range
+int sz_nn_heads_f16_checked(const void* x, const void* w_p1_packed, const float* b_p1, const void* w_p2_packed, const float* b_p2, const float* wv, float bv,
+                            const float* fc1_w_t, const float* fc1_b, const float* fc2_w, float fc2_b, float* probs, float* value, float* v1_scratch,
+                            int32_t n_boards, int32_t do_softmax, uint32_t* range_flag, void* stream) {
     if (!x || !w_p1_packed || !b_p1 || !w_p2_packed || !b_p2 || !wv || !fc1_w_t || !fc1_b || !fc2_w || !probs || !value || !v1_scratch || n_boards <= 0) return SZ_ERR_INVALID;
     StreamDeviceGuard _guard(stream);
     const size_t lds_h = (size_t)(2 * 64) * (256 * 2 + NN_PAD16) + NN_ZERO16 + 64, lds_v = (64 * 256 + 16 * 64) * sizeof(float);
@@ -1499,10 +1542,10 @@ int sz_nn_heads_bf16(const void* x, const void* w_p1_packed, const float* b_p1, 
     }
     if (do_softmax & SZ_NN_F16)
         hipLaunchKernelGGL(k_heads16_bf16<ElemF16>, dim3((n_boards + 1) / 2), dim3(256), lds_h, (hipStream_t)stream, (const uint16_t*)x, (const uint4*)w_p1_packed, b_p1,
-                           (const uint4*)w_p2_packed, b_p2, wv, bv, probs, v1_scratch, n_boards, do_softmax & 1);
+                           (const uint4*)w_p2_packed, b_p2, wv, bv, probs, v1_scratch, n_boards, do_softmax & 1, (unsigned int*)range_flag);
     else
         hipLaunchKernelGGL(k_heads16_bf16<ElemBF16>, dim3((n_boards + 1) / 2), dim3(256), lds_h, (hipStream_t)stream, (const uint16_t*)x, (const uint4*)w_p1_packed, b_p1,
-                           (const uint4*)w_p2_packed, b_p2, wv, bv, probs, v1_scratch, n_boards, do_softmax & 1);
+                           (const uint4*)w_p2_packed, b_p2, wv, bv, probs, v1_scratch, n_boards, do_softmax & 1, (unsigned int*)range_flag);
     HIPCHK(hipGetLastError());
     if (n_boards > 2048)
         hipLaunchKernelGGL(k_value_head<4>, dim3((n_boards + 15) / 16), dim3(256), lds_v, (hipStream_t)stream, (const uint16_t*)x, wv, bv, fc1_w_t, fc1_b, fc2_w, fc2_b,

@@ -72,6 +72,43 @@ struct ElemF16 {
     static uint16_t from_float(float v) { const _Float16 h = (_Float16)v; uint16_t u; memcpy(&u, &h, 2); return u; }                          // host, RNE
 };
 
+// A value written by v_accvgpr_write has an AGPR-class live range: it stays in the accumulator file across a K loop instead of taking a vector register there.
+__device__ __forceinline__ float to_agpr(float v) { float a; asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v)); return a; }
+__device__ __forceinline__ float from_agpr(float a) { float v; asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a)); return v; }
+
+// ---- f16 range tracking (ElemF16 epilogues only; the bf16 instantiations carry none of it) ---------------------------------------------------------------
+// A stored activation of 65520 or more packs to +inf, the next convolution makes NaN of it (inf - inf), and the integer ReLU erases a NaN whose sign bit is set:
+// the overflow can leave a launch as finite garbage.  So it is remembered where it is created: AFTER the ReLU both halves of a packed pair are >= +0 as int16 and
+// inf / NaN are exactly the patterns from 0x7C00 up, so a running per-half integer maximum (v_pk_max_i16) of everything a lane stored tells at the end of the
+// kernel whether a stored value had left the range.  The running maximum lives in an AGPR (read, max, write back per stored tile): the tower kernels have no
+// vector register to spare across their K loops (kept in a VGPR it was spilled to scratch around every update).  A value of -65520 or below packs to -inf and the
+// ReLU makes the 0 of it that the exact value gives too: no overflow.
+struct RangeSeen { float a; };                             // the AGPR-resident running maximum (bit pattern of two int16)
+__device__ __forceinline__ RangeSeen range_none() { RangeSeen r; r.a = to_agpr(0.f); return r; }
+template <class E> __device__ __forceinline__ void range_track(RangeSeen& seen, uint32_t pair0, uint32_t pair1) {           // the two pairs of one stored tile, after the ReLU
+    if constexpr (std::is_same<E, ElemF16>::value) {
+        const i16x2 m = __builtin_elementwise_max(__builtin_elementwise_max(__builtin_bit_cast(i16x2, pair0), __builtin_bit_cast(i16x2, pair1)),
+                                                  __builtin_bit_cast(i16x2, from_agpr(seen.a)));
+        seen.a = to_agpr(__builtin_bit_cast(float, m));
+    }
+}
+// the same with the running maximum in a plain register (the heads kernel: two workgroups per CU, no accumulator file of its own)
+template <class E> __device__ __forceinline__ void range_track(uint32_t& seen, uint32_t pair0, uint32_t pair1) {
+    if constexpr (std::is_same<E, ElemF16>::value)
+        seen = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_elementwise_max(__builtin_bit_cast(i16x2, pair0), __builtin_bit_cast(i16x2, pair1)),
+                                                                      __builtin_bit_cast(i16x2, seen)));
+}
+template <class E> __device__ __forceinline__ void range_report(uint32_t m, unsigned int* flag) {
+    if constexpr (std::is_same<E, ElemF16>::value) { if (flag && ((m & 0xFFFFu) >= 0x7C00u || (m >> 16) >= 0x7C00u)) atomicOr(flag, 1u); }
+}
+// end of a kernel: one vector atomic per lane that saw an overflow (none in a healthy network)
+template <class E> __device__ __forceinline__ void range_report(const RangeSeen& seen, unsigned int* flag) {
+    if constexpr (std::is_same<E, ElemF16>::value) {
+        const uint32_t m = __builtin_bit_cast(uint32_t, from_agpr(seen.a));
+        if (flag && ((m & 0xFFFFu) >= 0x7C00u || (m >> 16) >= 0x7C00u)) atomicOr(flag, 1u);
+    }
+}
+
 // ---- stage WGB boards' activations (NHWC rows of C_in bf16) into LDS, plus one zero row ---------------------
 template <int CIN, int WGB, int PAD = 16, bool NT = false, bool SWZ = false /* chunk swizzle of the split-precision images: chunk ^ ((position >> 2) & 1) */>
 __device__ __forceinline__ void stage_tile(unsigned char* lds, const uint16_t* __restrict__ in, int board0, int n_boards, bool skip) {

@@ -200,8 +200,7 @@ __device__ __forceinline__ void split_kloop(const unsigned char* lds, const int 
 // SIMD).  Left to itself hipcc kept the accumulators and the K loop's operands in the arch VGPRs and sent most of the 128 residual values to scratch
 // memory: the conv2 epilogue was a chain of scratch_load -> s_waitcnt vmcnt(0), 35k cycles per convolution (in-kernel stamps, profiles/r03b_split_stamps.txt).
 // A value written by v_accvgpr_write has an AGPR-class live range, so it stays there across the K loop.
-__device__ __forceinline__ float to_agpr(float v) { float a; asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v)); return a; }
-__device__ __forceinline__ float from_agpr(float a) { float v; asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a)); return v; }
+// (to_agpr / from_agpr: sz_nn_common.h)
 // ReLU on the f32 bit pattern: a negative float is a negative int32 (v_max_i32: one instruction, no canonicalisation; -0 -> +0)
 __device__ __forceinline__ float relu_f32(float v) { const int i = __builtin_bit_cast(int, v); return __builtin_bit_cast(float, i > 0 ? i : 0); }
 
@@ -211,7 +210,7 @@ __device__ __forceinline__ float relu_f32(float v) { const int i = __builtin_bit
 //   MODE 2 (conv2) : x = relu(acc + xres)  -> xres, images      (network.py:74-81; the residual is the exact f32 value, kept in registers)
 // E = ElemF16: the weights (and the bias the accumulators started at) were packed times 2^SP_WSCALE_LOG2: the accumulator is scaled back first (exact)
 template <int WGB, int MODE, class E = ElemBF16>
-__device__ __forceinline__ void split_epilogue(unsigned char* hi_img, unsigned char* lo_img, const f32x4 (&acc)[4][4 * WGB], float (&xres)[4][4 * WGB][4]) {
+__device__ __forceinline__ void split_epilogue(unsigned char* hi_img, unsigned char* lo_img, const f32x4 (&acc)[4][4 * WGB], float (&xres)[4][4 * WGB][4], RangeSeen& seen) {
     constexpr bool SCALED = std::is_same<E, ElemF16>::value;
     constexpr float USC = 1.0f / (float)(1 << SP_WSCALE_LOG2);
     constexpr int PITCH = NN_COUT * 2 + NN_PAD16;
@@ -252,6 +251,7 @@ __device__ __forceinline__ void split_epilogue(unsigned char* hi_img, unsigned c
 #pragma unroll
             for (int d = 0; d < 2; d++) {
                 h[d].x = E::pack2(v[d][0], v[d][1]); h[d].y = E::pack2(v[d][2], v[d][3]);
+                range_track<E>(seen, h[d].x, h[d].y);                                // f16: the hi image is not scaled, v >= 65520 is +inf there (v >= 0 after the ReLU)
                 l[d].x = E::pack2(v[d][0] - E::lo(h[d].x), v[d][1] - E::hi(h[d].x));
                 l[d].y = E::pack2(v[d][2] - E::lo(h[d].y), v[d][3] - E::hi(h[d].y));
             }
@@ -279,6 +279,7 @@ struct SplitHeadsParams {
     float* probs;            // [n_boards][4672] f32, the reference's flatten order plane*64 + position
     float* v1_out;           // [n_boards][64] relu(bn(conv_v1(x))) (the 64 -> 256 -> 1 MLP is k_value_head)
     int do_softmax;
+    unsigned int* range_flag; // f16 operands: OR-ed with 1 when a hi image element left f16's range (range_track, sz_nn_common.h); NULL = not reported
 };
 
 // value : conv_v1 (256 -> 1) + ReLU per position, one f32 fma chain over the channels in ascending order
@@ -290,7 +291,7 @@ struct SplitHeadsParams {
 template <int WGB, class E = ElemBF16>
 __device__ __forceinline__ void split_heads_tail(unsigned char* lds, const int* addr_tab, const WSrc& wr, const uint32_t ks_p1, const float* __restrict__ bias_p1,
                                                  const SplitHeadsParams& hp, f32x4 (&acc)[4][4 * WGB], uint4 (&ring)[SP_RING][8], float (&xres)[4][4 * WGB][4],
-                                                 const int board0, const int n_boards) {
+                                                 const int board0, const int n_boards, RangeSeen& seen) {
     using GEO = SplitGeom<WGB>;
     constexpr int NJ = GEO::NJ, NT = WGB, PITCH = GEO::PITCH;          // NT: position tiles per wave in conv_p2
     unsigned char* imgH = lds;
@@ -322,7 +323,7 @@ __device__ __forceinline__ void split_heads_tail(unsigned char* lds, const int* 
     }
     split_kloop<256, WGB, true, true, 0, 1, E>(lds, 0, GEO::IMG, addr_tab, wr, ks_p1, 0u, bias_p1, acc, ring);     // fetches the next tile's first stem k-step on its way out
     __syncthreads();                                                   // every wave is done reading x
-    split_epilogue<WGB, 1, E>(imgH, imgL, acc, xres);                  // t over x
+    split_epilogue<WGB, 1, E>(imgH, imgL, acc, xres, seen);            // t over x
     __syncthreads();
     // conv_p2: wave w owns position tiles w*NT .. w*NT + NT - 1, all 5 channel tiles; K = 256
     f32x4 pa[5][NT];
@@ -449,6 +450,8 @@ __global__ __launch_bounds__(256, 1) void k_tower_split(const uint16_t* __restri
     f32x4 acc[4][NJ];
     float xres[4][NJ][4];                                              // the residual x (exact f32), one value per AGPR
     uint4 ring[SP_RING][8];
+    RangeSeen seen;                                                    // f16: per-half maximum of every hi pair this lane stored (range_track)
+    if constexpr (std::is_same<E, ElemF16>::value) seen = range_none();
     {   // the first SP_PF k-steps of the stem
         const uint32_t wlane = (uint32_t)((wave * 4) * 64 + lane) * 16u;
 #pragma unroll
@@ -468,7 +471,7 @@ __global__ __launch_bounds__(256, 1) void k_tower_split(const uint16_t* __restri
         split_kloop<128, WGB, false, true, 0, 9, E>(lds, GEO::IMG, GEO::IMG, addr_tab, wr, ks, n_convs > 1 ? 36u : ks_end, bias, acc, ring);
         ks += 36;
         __syncthreads();                                               // every wave is done reading the planes
-        split_epilogue<WGB, 0, E>(imgH, imgL, acc, xres);
+        split_epilogue<WGB, 0, E>(imgH, imgL, acc, xres, seen);
         __syncthreads();
         for (int c = 1; c < n_convs; c++) {
             const bool stamp_now = MODE != 0 && (c == 7 || c == 8) && tile == (int)(blockIdx.x + gridDim.x);
@@ -479,14 +482,14 @@ __global__ __launch_bounds__(256, 1) void k_tower_split(const uint16_t* __restri
             SPSTAMP(sb + 1);
             __syncthreads();                                           // every wave is done reading the images: they are rewritten in place
             SPSTAMP(sb + 2);
-            if (c & 1) split_epilogue<WGB, 1, E>(imgH, imgL, acc, xres);
-            else split_epilogue<WGB, 2, E>(imgH, imgL, acc, xres);
+            if (c & 1) split_epilogue<WGB, 1, E>(imgH, imgL, acc, xres, seen);
+            else split_epilogue<WGB, 2, E>(imgH, imgL, acc, xres, seen);
             SPSTAMP(sb + 3);
             __syncthreads();
             SPSTAMP(sb + 4);
             if (MODE != 0 && stamp_now && c == 8 && (threadIdx.x & 63) == 0) stamps[(size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + 10] = __builtin_amdgcn_s_memrealtime();
         }
-        if constexpr (HEADS) split_heads_tail<WGB, E>(lds, addr_tab, wr, ks_p1, bias + n_convs * NN_COUT, hp, acc, ring, xres, board0, n_boards);
+        if constexpr (HEADS) split_heads_tail<WGB, E>(lds, addr_tab, wr, ks_p1, bias + n_convs * NN_COUT, hp, acc, ring, xres, board0, n_boards, seen);
         // tower output straight from the registers (exact f32): lane = 4 channels of one position per tile, 64-byte pieces
         const int p16 = lane & 15, kg = lane >> 4;
         if (!HEADS || out)
@@ -501,6 +504,7 @@ __global__ __launch_bounds__(256, 1) void k_tower_split(const uint16_t* __restri
             }
         }
     }
+    range_report<E>(seen, hp.range_flag);
 }
 
 // =================================================================================================================
@@ -964,11 +968,19 @@ int sz_nn_value_mlp(const float* v1, const float* fc1_w_t, const float* fc1_b, c
 int sz_nn_forward_split(const void* planes, const void* w_stream, const float* bias, int32_t n_blocks, const void* w_p2_packed, const float* b_p2, const float* wv, float bv,
                         const float* fc1_w_t, const float* fc1_b, const float* fc2_w, float fc2_b, float* probs, float* value, float* v1_scratch, float* tower_out,
                         int32_t n_boards, int32_t do_softmax, int32_t flags, void* stream) {
+    return sz_nn_forward_split_checked(planes, w_stream, bias, n_blocks, w_p2_packed, b_p2, wv, bv, fc1_w_t, fc1_b, fc2_w, fc2_b, probs, value, v1_scratch, tower_out,
+                                       n_boards, do_softmax, flags, nullptr, stream);
+}
+// sz_nn_forward_split with a range flag: with SZ_NN_F16 the device word *range_flag is OR-ed with 1 when an element of a hi image (stem, t, block output, the
+// policy head's t) was 65520 or more, i.e. +inf in f16
+int sz_nn_forward_split_checked(const void* planes, const void* w_stream, const float* bias, int32_t n_blocks, const void* w_p2_packed, const float* b_p2, const float* wv, float bv,
+                                const float* fc1_w_t, const float* fc1_b, const float* fc2_w, float fc2_b, float* probs, float* value, float* v1_scratch, float* tower_out,
+                                int32_t n_boards, int32_t do_softmax, int32_t flags, uint32_t* range_flag, void* stream) {
     if (!planes || !w_stream || !bias || !w_p2_packed || !b_p2 || !wv || !fc1_w_t || !fc1_b || !fc2_w || !probs || !value || !v1_scratch || n_boards <= 0 || n_blocks < 0 ||
         1 + 2 * n_blocks > NN_MAX_CONVS_SPLIT) return SZ_ERR_INVALID;
     StreamDeviceGuard _guard(stream);
     SplitHeadsParams hp;
-    hp.w_p2 = (const uint4*)w_p2_packed; hp.b_p2 = b_p2; hp.wv = wv; hp.bv = bv; hp.probs = probs; hp.v1_out = v1_scratch; hp.do_softmax = do_softmax;
+    hp.w_p2 = (const uint4*)w_p2_packed; hp.b_p2 = b_p2; hp.wv = wv; hp.bv = bv; hp.probs = probs; hp.v1_out = v1_scratch; hp.do_softmax = do_softmax; hp.range_flag = (unsigned int*)range_flag;
     const int rc = launch_split(planes, w_stream, bias, n_blocks, tower_out, n_boards, flags, stream, &hp);
     if (rc != SZ_OK) return rc;
     return sz_nn_value_mlp(v1_scratch, fc1_w_t, fc1_b, fc2_w, fc2_b, value, n_boards, stream);

@@ -46,10 +46,23 @@ def _check_f16_range(named, scale, what):
                              % (what, name, amax, " (weights packed times %g)" % scale if scale != 1 else "", " / %g" % scale if scale != 1 else ""))
 
 
+def _read_range_flag(flag):
+    """overflowed() of both networks: read the device word (synchronises the current stream), clear it when it was set"""
+    if flag is None:
+        return False
+    hit = bool(int(flag.item()))
+    if hit:
+        flag.zero_()
+    return hit
+
+
 class FastPolicyNet:
     """operands: "bf16" (default) or "fp16" — the element type of the MFMA operands (weights and stored activations; accumulation, bias,
     residual add and the value MLP are f32 either way).  fp16 keeps 11 bits of mantissa instead of 8 at the same speed; it needs the
-    16x16x32 kernels with the persistent tower and the fused heads (the defaults)."""
+    16x16x32 kernels with the persistent tower and the fused heads (the defaults).  f16 holds |v| <= 65504: the weights are checked at
+    construction, the activations by every forward: the f16 kernels remember in a device word whether a value they stored was +inf (no host
+    synchronisation, no extra launch), overflowed() reads it and SelfPlayEngine.check_errors() raises on it.  The outputs alone do not tell: the
+    convolution behind an inf gives NaN, and the integer ReLU erases a NaN whose sign bit is set, so an overflowing network can return finite garbage."""
 
     def __init__(self, model, device=None, mfma16=True, operands="bf16"):
         model = model.eval()
@@ -118,6 +131,7 @@ class FastPolicyNet:
             self._tower_w = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
             self._tower_b = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
         self._bufs, self._full, self._cap = {}, None, 0
+        self._oflag = torch.zeros(1, dtype=torch.int32, device=dev) if self.f16 else None      # f16: sticky "a forward returned inf / NaN" (overflowed())
         self.fuse_blocks = True      # one launch per BasicBlock (sz_nn_block_bf16); False = two sz_nn_conv_bf16 launches
         self.timing = None          # optional list: (start, end) HIP event pairs around every 3x3 C_in=256 conv launch
 
@@ -126,6 +140,12 @@ class FastPolicyNet:
 
     def to(self, *a, **k):
         return self
+
+    def overflowed(self):
+        """True when, in a tower() or forward since the last call, an activation that the f16 kernels stored (stem, t, block output, the policy head's t)
+        was 65520 or more, which f16 holds as +inf: what that call returned is then inf / NaN or finite garbage.  Sticky until read, cleared by the read;
+        synchronises the current stream.  Always False with bf16 operands (f32's range; nothing is tracked)."""
+        return _read_range_flag(self._oflag)
 
     def _buffers(self, B):
         """activation / output buffers for a batch of B boards: views of ONE capacity-sized set that only ever grows (a self-play
@@ -173,8 +193,9 @@ class FastPolicyNet:
             if self.timing is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            N.check(N.lib().sz_nn_tower_bf16(C.c_void_p(planes.data_ptr()), self._tower_w, self._tower_b, len(self.blocks), C.c_void_p(a.data_ptr()), B, in_bits | self.eflag | self.force_wgb,
-                                             C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "sz_nn_tower_bf16")
+            N.check(N.lib().sz_nn_tower_f16_checked(C.c_void_p(planes.data_ptr()), self._tower_w, self._tower_b, len(self.blocks), C.c_void_p(a.data_ptr()), B,
+                                                    in_bits | self.eflag | self.force_wgb, C.c_void_p(self._oflag.data_ptr()) if self.f16 else None,
+                                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "sz_nn_tower_bf16")
             if ev is not None:
                 ev[1].record()
                 self.timing.append(ev)
@@ -220,9 +241,9 @@ class FastPolicyNet:
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             if self.fused_heads and self.w16:
                 P = lambda t: C.c_void_p(t.data_ptr())
-                N.check(N.lib().sz_nn_heads_bf16(P(x), P(self.p1[0]), P(self.p1[1]), P(self.wp2_packed), P(self.bp2), P(self.wv_f32), self.bv_f,
-                                                 P(self.fc1_w), P(self.fc1_b), P(self.fc2_w_vec), self.fc2_b_f, P(policy), P(value), P(v1),
-                                                 B, int(bool(inference)) | self.eflag, st), "sz_nn_heads_bf16")
+                N.check(N.lib().sz_nn_heads_f16_checked(P(x), P(self.p1[0]), P(self.p1[1]), P(self.wp2_packed), P(self.bp2), P(self.wv_f32), self.bv_f,
+                                                        P(self.fc1_w), P(self.fc1_b), P(self.fc2_w_vec), self.fc2_b_f, P(policy), P(value), P(v1),
+                                                        B, int(bool(inference)) | self.eflag, P(self._oflag) if self.f16 else None, st), "sz_nn_heads_bf16")
                 return policy, value.view(B, 1)
             if self.f16:
                 raise ValueError("fp16 operands need the fused heads")
@@ -317,6 +338,7 @@ class SplitPolicyNet:
         self.module_heads = False                         # True: run policy_head / value_head of the torch module itself (cross-check)
         self._out, self._cap = None, 0
         self._p = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._oflag = torch.zeros(1, dtype=torch.int32, device=dev) if self.f16 else None      # f16: sticky "a forward returned inf / NaN" (overflowed())
         self.timing = None
 
     def parameters(self):
@@ -327,6 +349,12 @@ class SplitPolicyNet:
 
     def eval(self):
         return self
+
+    def overflowed(self):
+        """operands="fp16": True when, in a forward since the last call (the fused default; not tower() alone nor the cross-check heads), an activation
+        was 65520 or more: its f16 hi image is not scaled and holds +inf then, and what the call returned is inf / NaN or finite garbage.  Sticky until
+        read, cleared by the read; synchronises the current stream.  Always False with bf16 operands."""
+        return _read_range_flag(self._oflag)
 
     @torch.no_grad()
     def tower(self, planes):
@@ -372,9 +400,10 @@ class SplitPolicyNet:
             if self.timing is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            N.check(N.lib().sz_nn_forward_split(P(planes), P(self._wstream), P(self._bias), self.n_blocks, P(self._wp2), P(self.h_bp2), P(self._wv_vec), self._bv_f,
-                                                P(self.h_fc1_w), P(self.h_fc1_b), P(self._fc2_vec), self._fc2_b_f, P(policy), P(value), P(v1), None,
-                                                B, int(bool(inference)), flags, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "sz_nn_forward_split")
+            N.check(N.lib().sz_nn_forward_split_checked(P(planes), P(self._wstream), P(self._bias), self.n_blocks, P(self._wp2), P(self.h_bp2), P(self._wv_vec), self._bv_f,
+                                                        P(self.h_fc1_w), P(self.h_fc1_b), P(self._fc2_vec), self._fc2_b_f, P(policy), P(value), P(v1), None,
+                                                        B, int(bool(inference)), flags, P(self._oflag) if self.f16 else None,
+                                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "sz_nn_forward_split")
             if ev is not None:
                 ev[1].record()
                 self.timing.append(ev)

@@ -108,6 +108,17 @@ def search_options_of(args):
     return int(L), float(lam), bool(solver), bool(combine)
 
 
+def raise_if_overflowed(model):
+    """ValueError when `model` keeps a range flag (FastPolicyNet / SplitPolicyNet: overflowed()) and a forward since the last look returned inf / NaN:
+    with f16 operands a stored activation of 65520 or more is inf, the heads make NaN of it, and the search keeps a NaN prior without complaint.
+    A model without overflowed() (a torch module, a bf16 network's always-False one) passes."""
+    ov = getattr(model, "overflowed", None)
+    if callable(ov) and ov():
+        raise ValueError("%s(operands=%r): an activation left f16's range during the search (f16 holds at most 65504; from 65520 on a stored activation is inf) "
+                         "and the network returned inf / NaN policies or values; the trees searched since the last check are not to be used "
+                         "— use operands=\"bf16\" or SplitPolicyNet" % (type(model).__name__, getattr(model, "operands", None)))
+
+
 class SelfPlayEngine:
     def __init__(self, model, args, n_boards, chess960=False, learning=True, device=None, planes_dtype=torch.float32,
                  noise_value=NOISE_REFERENCE, edges_per_board=0):
@@ -327,9 +338,12 @@ class SelfPlayEngine:
         return {k: getattr(st, k) for k, _ in N.sz_stats._fields_}
 
     def check_errors(self):
+        """raises on a board that ended in an error state (NativeError) and on an f16 network whose forwards left f16's range since the last check
+        (ValueError, raise_if_overflowed); stats() has synchronised the stream by then"""
         st = self.stats()
         if st["boards_error"]:
             raise N.NativeError(st["first_error"], "search (%d boards)" % st["boards_error"])
+        raise_if_overflowed(self.model)
         return st
 
     def root_children(self):

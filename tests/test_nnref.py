@@ -161,3 +161,27 @@ def test_one_bad_board_net_has_a_gap_around_the_rounding_to_inf_point():
     assert float(p[bad]) > F16_INF_FROM * 1.002 and float(p[good].max()) < F16_INF_FROM * 0.998, (bad, p.tolist())
     clean = Emulated(net, "fp16").site_maxima(R.boards()[good])
     assert max(float(v.max()) for v in clean.values()) < F16_INF_FROM * 0.998
+    # the bad board overflows to +inf (a peak of -65520 or below would pack to -inf and the ReLU would make the correct 0 of it): the emulation's probabilities
+    # are non-finite on that board and on no other
+    assert float(R.site_values(net, "block9.t", R.boards())[bad].max()) > F16_INF_FROM * 1.002
+    pi, v = Emulated(net, "fp16")(R.boards(), inference=True)
+    assert (~torch.isfinite(pi).all(1)).tolist() == [b == bad for b in range(R.N_BOARDS)] and bool(torch.isfinite(v[good]).all())
+
+
+@pytest.mark.parametrize("site", R.SPLIT_SITES)
+def test_split_range_nets_fit_the_split_packing_and_reach_their_target(site):
+    """the two-layer nets for SplitPolicyNet(operands="fp16"): every folded weight below 65520 / 2^10 (what its constructor accepts); the 0.9 x net below 65520
+    everywhere; the 2 x net first exceeds it at the site, and there every board's largest POSITIVE value does (the split kernels pack after the f32 ReLU)"""
+    x = R.boards()
+    names = site_names(19)
+    for target in (R.IN_RANGE, R.OUT_OF_RANGE):
+        net = R.split_net_at(site, target)
+        assert R.largest_folded_weight(net) < R.SPLIT_W_LIMIT * 0.99, (site, target, R.largest_folded_weight(net))
+        peaks = Emulated(net, None).site_maxima(x)
+        assert abs(float(peaks[site].max()) / target - 1) <= 0.011
+        if target == R.IN_RANGE:
+            assert max(float(v.max()) for v in peaks.values()) < F16_INF_FROM * 0.95
+        else:
+            over = [n for n in names if float(peaks[n].max()) >= F16_INF_FROM]
+            assert over[0] == site and all(float(peaks[n].max()) < 1000 for n in names[:names.index(site)])
+            assert float(R.site_values(net, site, x, None).flatten(1).max(1).values.min()) > F16_INF_FROM * 1.5
