@@ -2,7 +2,7 @@
 
 One object per source (compiled in parallel, rebuilt only when the source, a header or the flag string changed), then one link.
 A/B builds: SIGMAZERO_LIB=<other .so path> selects the output (and the library `_native` loads); SIGMAZERO_EXTRA_FLAGS (e.g.
--DNN_ROWSKIP=0) is honoured ONLY together with SIGMAZERO_LIB, so a leftover variable can never turn the default library into an
+-DSP_PF=0) is honoured ONLY together with SIGMAZERO_LIB, so a leftover variable can never turn the default library into an
 ablated one.  The flag string a library was built with is kept next to it (<lib>.flags) and is part of the up-to-date check.
 """
 import hashlib

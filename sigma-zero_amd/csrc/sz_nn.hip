@@ -1,56 +1,26 @@
 // sz_nn.hip — hand-written CDNA4 MFMA kernels for the policy/value network of the reference
 // (/root/reference/network.py:36-83 BasicBlock, :105-137 policyNN stem/tower, :141-174 heads).
+// What ships multiplies on v_mfma_f32_16x16x32 (bf16 or f16 operands, f32 accumulation); NHWC in/out, C_out = 256,
+// C_in in {128 (zero-padded 119-plane stem), 256}.
 //
-//   k_tower16_bf16  THE SHIPPED PATH: stem + all BasicBlocks in one persistent launch (16x16x32 MFMA; one workgroup per CU takes
-//                   2-board tiles through all 39 convolutions with the activations resident in LDS) — see its own header below
-//   k_heads16_bf16  both heads from one read of the tower output (+ k_value_head for the 64->256->1 MLP)
-//   building blocks / cross-checks, per-layer launches:
-//   k_conv_bf16, k_conv16_bf16    one fused layer : conv3x3(pad 1) / conv1x1 + folded BatchNorm + bias (+ residual) (+ ReLU)
-//   k_block_bf16, k_block16_bf16  one fused BasicBlock : relu(bn2(conv2(relu(bn1(conv1(x))))) + x), the intermediate activation
-//                 never leaves the CU (it is written to LDS in exactly the layout the second conv reads)
-// The notes below describe the first (32x32x16) per-layer kernels; the 16x16x32 path has its own section further down.
-// NHWC bf16 in/out, f32 accumulate, C_out = 256, C_in in {128 (zero-padded 119-plane stem), 256}; one launch
-// replaces MIOpen's igemm + batch_norm + clamp + add kernels of the torch graph.
-//
-// MI355X mapping (not a warp-tiling port):
-//   * one workgroup = 4 waves = WGB boards (2 by default -> 68 KB of LDS -> TWO workgroups per CU, so one
-//     workgroup's HBM phases hide partly under the other's MFMA phase; the first co-resident pair is phase-staggered);
-//   * the boards' activations (WGB*64 positions x C_in) are loaded ONCE from HBM into LDS (row pitch
-//     C_in*2+16 B: conflict-free ds_read_b128) and stay resident for all 9 taps — the im2col matrix is
-//     never formed; a tap is just a per-lane row address (off-board taps read a zero row);
-//   * D = W x Act^T on v_mfma_f32_32x32x16_bf16 with the WEIGHTS as the A operand (rows = out channels) and
-//     activations as the B operand (cols = positions); every wave owns a distinct quarter of the output
-//     channels (2 channel tiles x 2*WGB position tiles), so each weight fragment is fetched by one wave only;
-//   * weights are pre-packed on the host in exact fragment order [tap][kstep][co_tile][lane][8]: a weight
-//     fragment is one fully coalesced 1 KiB global_load_dwordx4 from L2 (1.18 MB/layer stays L2-resident),
-//     prefetched 3 k-steps ahead through a 4-deep register ring (8-deep measured no faster); activations are
-//     double-buffered one k-step ahead; the order is pinned with sched_barrier so the compiler's waits become
-//     counted vmcnt/lgkmcnt: the K loop has NO workgroup barrier and no exposed memory latency;
-//   * epilogue through LDS: (acc + bias) -> bf16 -> [pos][co] image, then whole 16-byte chunks are moved with
-//     coalesced residual reads and stores (scattered 8-byte stores from the accumulator layout cost 20 %).
-// `flags` bit 0 = ReLU; higher bits are timing-ablation / A-B switches used by tools/conv_bench.py only
-// (2/4/8 skip load/store/K loop, 16 = 4-board workgroups, 32/64 + bits 8..15 = phase stagger, 0x10000 = no stagger,
-// 0x200000/0x400000/0x800000 = streaming (non-temporal) tile loads / output stores / residual re-read in the fused block:
-// measured with tools/block_ab.py, all-streaming +3 % slower (the residual re-read then misses), stores or residual alone within noise).
+//   k_tower16_bf16  THE SHIPPED PATH: stem + all BasicBlocks in one persistent launch (one workgroup per CU takes 2-board tiles, or
+//                   single boards at small batches, through all 39 convolutions with the activations resident in LDS) — see its own
+//                   header below; MODE > 0 instantiations are the diagnostic builds of tools/tower_stamps.py
+//   k_heads16_bf16  both heads from one read of the tower output (+ k_value_head for the 64->256->1 MLP);
+//                   k_policy_head / k_value_head alone are the separate-launch forms (cross-checks)
+//   building blocks / cross-checks, per-layer launches (one launch replaces MIOpen's igemm + batch_norm + clamp + add kernels):
+//   k_conv16_bf16   one fused layer : conv3x3(pad 1) / conv1x1 + folded BatchNorm + bias (+ residual) (+ ReLU)
+//   k_block16_bf16  one fused BasicBlock : relu(bn2(conv2(relu(bn1(conv1(x))))) + x), the intermediate activation
+//                   never leaves the CU (it is written to LDS in exactly the layout the second conv reads)
+//   k_conv_bf16, k_block_bf16  the same two on v_mfma_f32_32x32x16_bf16: the first generation, kept as a cross-check (no SZ_NN_W16 flag)
+// conv_kloop16 / conv_kloop16_one are the K loops of everything but those two; the MI355X mapping is described in front of them.
 #include "sz_nn_common.h"
 
-// K loop of the persistent tower: ONE explicit s_waitcnt in the last MFMA gap of every half-step (it carries no memory instruction) for everything the next
-// half-step consumes — lgkmcnt(0) for its activation fragments, plus vmcnt(8) at the end of a k-step for the next k-step's weights (two k-steps of loads stay in
-// flight).  hipcc otherwise puts a counted wait in front of each first use, i.e. into the very gaps that also issue a load: 1,276 -> 523 s_waitcnt in the kernel,
-// BasicBlock 81,440 -> 80,196 cycles, launch 7.34 -> 7.24 ms (same box, interleaved: profiles/r03u_explicit_wait_ab.txt).  0 = off (A/B), 1 = LDS only.
-#ifndef NN_EXPLICIT_WAIT
-#define NN_EXPLICIT_WAIT 2
-#endif
-#ifndef NN_TAPGAP
-#define NN_TAPGAP 1                                        // tap bookkeeping (table reads, row addresses) inside MFMA gaps; 0 = between the taps (A/B)
-#endif
-
-
-// ---- the K loop: acc[i][j] += W[tap,k] x Act[tap,k]^T over all taps and channels ----------------------------
+// ---- the first-generation K loop (32x32x16 MFMA): acc[i][j] += W[tap,k] x Act[tap,k]^T over all taps and channels ----
 // Software pipeline, pinned with sched_barrier so that hipcc cannot sink the prefetches to their uses:
 //   issue { weights of k-step ks+PF (L2 -> ring), activations of ks+1 (LDS -> bfrag) } ; NI*NJ MFMAs of ks.
-template <int CIN, int NTAPS, int WGB, bool PROBE16 = false>
-__device__ __forceinline__ void conv_kloop(const unsigned char* lds, const uint4* __restrict__ w, f32x16 (&acc)[NN_NI][2 * WGB], bool skip) {
+template <int CIN, int NTAPS, int WGB>
+__device__ __forceinline__ void conv_kloop(const unsigned char* lds, const uint4* __restrict__ w, f32x16 (&acc)[NN_NI][2 * WGB]) {
     constexpr int PITCH = CIN * 2 + 16;
     constexpr int KSTEPS = CIN / 16;
     constexpr int ZERO_ROW = WGB * 64;
@@ -84,7 +54,7 @@ __device__ __forceinline__ void conv_kloop(const unsigned char* lds, const uint4
     bf16x8 bfrag[2][NJ];
 #pragma unroll
     for (int j = 0; j < NJ; j++) { bcur[j] = tap_addr(0, j); bnxt[j] = bcur[j]; bfrag[0][j] = *(const bf16x8*)(lds + bcur[j]); }
-    for (int tap = 0; tap < (skip ? 0 : NTAPS); tap++) {
+    for (int tap = 0; tap < NTAPS; tap++) {
         if (tap + 1 < NTAPS) {
 #pragma unroll
             for (int j = 0; j < NJ; j++) bnxt[j] = tap_addr(tap + 1, j);
@@ -109,19 +79,7 @@ __device__ __forceinline__ void conv_kloop(const unsigned char* lds, const uint4
             for (int i = 0; i < NI; i++) {
                 bf16x8 a = __builtin_bit_cast(bf16x8, aring[kc & (RING - 1)][i]);
 #pragma unroll
-                for (int j = 0; j < NJ; j++) {
-                    if constexpr (PROBE16) {
-                        // timing probe only (numerically meaningless): the same operands through twice as many 16x16x32 MFMAs
-#pragma unroll
-                        for (int q = 0; q < 2; q++) {
-                            f32x4 c4 = {acc[i][j][8 * q], acc[i][j][8 * q + 1], acc[i][j][8 * q + 2], acc[i][j][8 * q + 3]};
-                            c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfrag[kc & 1][j], c4, 0, 0, 0);
-                            acc[i][j][8 * q] = c4[0]; acc[i][j][8 * q + 1] = c4[1]; acc[i][j][8 * q + 2] = c4[2]; acc[i][j][8 * q + 3] = c4[3];
-                        }
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfrag[kc & 1][j], acc[i][j], 0, 0, 0);
-                    }
-                }
+                for (int j = 0; j < NJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfrag[kc & 1][j], acc[i][j], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -157,7 +115,7 @@ __device__ __forceinline__ void acc_to_lds(unsigned char* lds, const f32x16 (&ac
 
 // ---- LDS image -> (+ residual) -> (ReLU) -> coalesced 16-byte NHWC stores ------------------------------------
 // The residual is added to the bf16-rounded conv+bias value (torch's own bf16 graph rounds there too).
-template <int WGB, int PAD = 16, bool NT = false, bool NTS = NT>
+template <int WGB, int PAD /* row padding of the image: NN_PAD16, or 16 for the 32x32x16 kernels */>
 __device__ __forceinline__ void lds_to_out(const unsigned char* lds, const uint16_t* __restrict__ res, uint16_t* __restrict__ out, int board0, int n_boards, bool relu) {
     constexpr int OPITCH = NN_COUT * 2 + PAD;
     constexpr int OUT_CHUNKS = WGB * 64 * 32;              // 16-byte chunks of the output tile
@@ -170,12 +128,12 @@ __device__ __forceinline__ void lds_to_out(const unsigned char* lds, const uint1
         if (c >= valid) break;
         uint4 v = *(const uint4*)(lds + (c >> 5) * OPITCH + (c & 31) * 16);
         if (!res4 && !relu) {                              // plain copy (the persistent tower's output): element type does not matter
-            if (NTS) st_stream(out4 + c, v); else out4[c] = v;
+            out4[c] = v;
             continue;
         }
         float f[8] = {bf16_lo(v.x), bf16_hi(v.x), bf16_lo(v.y), bf16_hi(v.y), bf16_lo(v.z), bf16_hi(v.z), bf16_lo(v.w), bf16_hi(v.w)};
         if (res4) {
-            uint4 r = NT ? ld_stream(res4 + c) : res4[c];
+            uint4 r = res4[c];
             f[0] += bf16_lo(r.x); f[1] += bf16_hi(r.x); f[2] += bf16_lo(r.y); f[3] += bf16_hi(r.y);
             f[4] += bf16_lo(r.z); f[5] += bf16_hi(r.z); f[6] += bf16_lo(r.w); f[7] += bf16_hi(r.w);
         }
@@ -185,18 +143,27 @@ __device__ __forceinline__ void lds_to_out(const unsigned char* lds, const uint1
         }
         uint4 o;
         o.x = pack_bf16x2(f[0], f[1]); o.y = pack_bf16x2(f[2], f[3]); o.z = pack_bf16x2(f[4], f[5]); o.w = pack_bf16x2(f[6], f[7]);
-        if (NTS) st_stream(out4 + c, o); else out4[c] = o;
+        out4[c] = o;
     }
 }
 
 // =================================================================================================================
-// 16x16x32 MFMA path.  Same data movement and the same number of matrix-pipe cycles as the 32x32x16 path, but the chip
-// holds a ~15 % higher clock on this shape under bf16 load (measured with the timing probe in tools/conv_bench.py:
-// 0.212 vs 0.250 ms per conv at B = 4096; MI355X_MICROARCH.md "DVFS give-back" item 7).
+// The 16x16x32 MFMA convolution.  MI355X mapping (not a warp-tiling port):
+//   * one workgroup = 4 waves = WGB boards; the boards' activations (WGB*64 positions x C_in) sit in LDS (row pitch C_in*2 + 32 B:
+//     conflict-free ds_read_b128) and stay resident for all 9 taps — the im2col matrix is never formed; a tap is just a per-lane row
+//     address (off-board taps read a zero region);
+//   * D = W x Act^T with the WEIGHTS as the A operand (rows = out channels) and activations as the B operand (cols = positions); every
+//     wave owns a distinct quarter of the output channels, so each weight fragment is fetched by one wave only;
+//   * weights are pre-packed on the host in exact fragment order [tap][k32][co_tile16][lane][8] (sz_nn_pack_weights16): a weight fragment
+//     is one fully coalesced 1 KiB load from L2 (1.18 MB/layer stays L2-resident), prefetched through a register ring; the order is
+//     pinned with sched_barrier: the K loop has NO workgroup barrier and no exposed memory latency;
+//   * epilogue through LDS: acc (started at the bias) -> bf16 -> [pos][co] image, then whole 16-byte chunks are moved with coalesced
+//     residual reads and stores (scattered 8-byte stores from the accumulator layout cost 20 %).
 //   wave tile 64 channels x WGB*64 positions = 4 channel tiles(16) x 4*WGB position tiles(16), 4 acc regs each;
 //   one k-step = 32 channels; it is executed as two half-steps over the position halves (16 MFMAs = 256 cycles each):
-//   weights (4 fragments per k-step) ride a 2-deep ring one k-step ahead, activations are double-buffered one
-//   half-step ahead.  Weight order: [tap][k32][co_tile16][lane][8] (sz_nn_pack_weights16).
+//   weights (4 fragments per k-step) ride a 2-deep ring one k-step ahead (4-deep, three ahead, in the persistent tower), activations are
+//   double-buffered one half-step ahead.  The chip holds a ~15 % higher clock on this MFMA shape under bf16 load than on 32x32x16 (0.212 vs
+//   0.250 ms per conv at B = 4096; MI355X_MICROARCH.md "DVFS give-back" item 7).
 // =================================================================================================================
 
 // first PF k-steps of a convolution's weight stream into the ring (issued early, e.g. under the previous layer's epilogue)
@@ -214,13 +181,19 @@ __device__ __forceinline__ void conv_prefetch16(const uint4* __restrict__ w, uin
 }
 
 
-template <int CIN, int NTAPS, int WGB, int RING = 2, bool PREFETCHED = false, int ABL = 0 /* timing ablation: 1 = no weight loads, 2 = no LDS reads in the loop */,
-          bool ACCUM = false /* add onto the accumulators as they are: no bias, no initialisation */,
+// ---- the K loop: acc[i][j] += W[tap,k] x Act[tap,k]^T over all taps and channels ----------------------------
+// Memory instructions are interleaved into the MFMA gaps, one per gap (issued in front of each 16-MFMA group they cost a BasicBlock 108,432 instead of 103,976 cycles: DESIGN.md §3.2).
+// In the persistent tower (RING = 4) there is ONE explicit s_waitcnt in the last MFMA gap of every half-step (it carries no memory instruction) for everything the
+// next half-step consumes — lgkmcnt(0) for its activation fragments, plus vmcnt(8) at the end of a k-step for the next k-step's weights (two k-steps of loads stay
+// in flight).  hipcc otherwise puts a counted wait in front of each first use, i.e. into the very gaps that also issue a load: 1,276 -> 523 s_waitcnt in the kernel,
+// BasicBlock 81,440 -> 80,196 cycles, launch 7.34 -> 7.24 ms (same box, interleaved: profiles/r03u_explicit_wait_ab.txt).
+template <int CIN, int NTAPS, int WGB, int RING = 2, bool PREFETCHED = false,
+          int ABL = 0 /* timing ablation (tools/tower_stamps.py, results garbage): 1 = no weight loads, 2 = no LDS reads */,
           class E = ElemBF16 /* operand element: ElemBF16 or ElemF16 (sz_nn_common.h) */,
           class EPI = std::nullptr_t /* callable (p, stage): stage -1..3 of the epilogue of accumulator tile p = i*NH + j of the FIRST position half (EpiTile16 /
                                         EpiResidual16); when given, the LAST tap runs its two position halves one after the other and the epilogue of the first
                                         half rides in the MFMA gaps of the second */>
-__device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uint4* __restrict__ w, f32x4 (&acc)[4][4 * WGB], bool skip, bool wprobe = false,
+__device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uint4* __restrict__ w, f32x4 (&acc)[4][4 * WGB],
                                              uint4 (*ring_in)[4] = nullptr, const int img_off = 0 /* byte offset of the image inside `lds` */,
                                              const float* __restrict__ bias = nullptr /* accumulators start at the bias (C layout: channel = 16*tile + 4*(lane>>4) + reg) */,
                                              const int* addr_tab = nullptr /* optional LDS table [NTAPS][NJ][64] of conv_tap_addr16 values: a tap's addresses
@@ -230,7 +203,7 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
     constexpr int KSTEPS = CIN / 32;                       // k32-steps per tap
     constexpr int NI = 4, NJ = 4 * WGB, NH = NJ / 2;       // channel tiles, position tiles, position tiles per half-step
     constexpr int TOTAL_KS = NTAPS * KSTEPS;
-    const int W_KSTEP_STRIDE = wprobe ? 0 : 16 * 64;       // uint4 per (tap,k32); 0 = timing probe: every k-step re-reads the same (L1-hot) fragments
+    int W_KSTEP_STRIDE = 16 * 64;                          // uint4 per (tap,k32); not constexpr: DESIGN.md §3.2 "Removed switches"
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int p16 = lane & 15, kg = lane >> 4;             // lane owns position p16 of each 16-position tile; kg selects k 8kg..8kg+7
     const uint32_t wlane = (uint32_t)((wave * NI) * 64 + lane) * 16u;   // the lane's constant byte offset inside a k-step's 16 fragments
@@ -242,26 +215,35 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
     for (int i = 0; i < NI; i++) binit[i] = bias ? *(const f32x4*)(bias + (wave * NI + i) * 16 + 4 * kg) : f32x4{0.f, 0.f, 0.f, 0.f};
     constexpr bool PEEL = RING == 4;                       // 512-register tower only: the peeled copy costs the 256-register kernels spills
     // 2-board tower: position tile 0 (board row 0) is idle under taps 0..2 (they read row -1), tile NJ-1 (row 7) under taps 6..8: no fragment
-    // loads, no MFMAs for them there (tile_row above).  ABL & 4 switches it off (A/B timing build).
-    constexpr bool SKIPROWS = PEEL && NTAPS == 9 && WGB == 2 && !(ABL & 4) && NN_ROWSKIP;
-    if ((skip || !PEEL) && !ACCUM) {
+    // loads, no MFMAs for them there (tile_row in sz_nn_common.h).
+    constexpr bool SKIPROWS = PEEL && NTAPS == 9 && WGB == 2;
+    if (!PEEL) {
 #pragma unroll
         for (int i = 0; i < NI; i++)
 #pragma unroll
             for (int j = 0; j < NJ; j++) acc[i][j] = binit[i];
-    } else if (SKIPROWS && !ACCUM) {
+    } else if (SKIPROWS) {
 #pragma unroll
         for (int i = 0; i < NI; i++) acc[i][0] = binit[i];   // tile 0 takes no MFMA under the first tap, so the bias cannot ride in as its C operand
     }
     constexpr int PF = RING - 1;                           // weight prefetch distance in k-steps (512 matrix-pipe cycles each)
     static_assert(KSTEPS % RING == 0, "ring slots must be compile-time indices");
     uint4 aring[RING][NI];
+    // The ablation instrument: EVERY activation-fragment read and EVERY weight-fragment load of the K loop goes through these two.  Both are captureless (a
+    // capturing lambda nested in the tap lambdas changed the register allocation of the two-board towers), so the weight address is spelled out by WFRAG.
+    auto LDA = [](bf16x8& frag, int addr) {                // LDS -> fragment (see abs_addr below for the address form)
+        if constexpr (!(ABL & 2)) frag = *(const __attribute__((address_space(3))) bf16x8*)(uint32_t)addr;
+    };
+    auto LDW = [](uint4& frag, const WSrc& src, size_t uniform_off, uint32_t lane_bytes) {      // L2 -> ring slot
+        if constexpr (!(ABL & 1)) frag = ld_wfrag(src, uniform_off, lane_bytes);
+    };
+#define WFRAG(slot, ks, i) LDW(aring[slot][i], wr, (size_t)(ks) * W_KSTEP_STRIDE, wlane + (i) * 1024)    /* fragment i of k-step ks into ring slot `slot` */
 #pragma unroll
     for (int s = 0; s < PF; s++)
 #pragma unroll
         for (int i = 0; i < NI; i++) {
             if constexpr (PREFETCHED) aring[s][i] = ring_in[s][i];
-            else aring[s][i] = ld_wfrag(wr, (size_t)s * W_KSTEP_STRIDE, wlane + i * 1024);
+            else WFRAG(s, s, i);
         }
     // the image's offset is folded into the per-lane row address, so the k offset still fits the 16-bit immediate of ds_read for the
     // second image of the persistent tower, which sits beyond 64 KB (otherwise every read pays a v_add)
@@ -295,21 +277,20 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
         asm volatile("" : "+v"(a));                        // opaque: keeps the sum inside the VGPR (hipcc otherwise re-associates it into a per-read v_add)
         return a;
     };
-    auto LD = [](int addr) -> bf16x8 { return *(const __attribute__((address_space(3))) bf16x8*)(uint32_t)addr; };
     int bcur[NJ], bnxt[NJ];
     bf16x8 bfrag[2][NH];
 #pragma unroll
     for (int j = 0; j < NJ; j++) { bnxt[j] = addr_tab ? tab_convert(tap_addr(0, j)) : tap_addr(0, j); bcur[j] = abs_addr(bnxt[j]); }
 #pragma unroll
     for (int j = 0; j < NH; j++)
-        if (!(SKIPROWS && j == 0)) bfrag[0][j] = LD(bcur[j]);
+        if (!(SKIPROWS && j == 0)) LDA(bfrag[0][j], bcur[j]);
     auto tap_body = [&](const int tap, auto first_tag, auto skip_tag) {
         constexpr bool FIRST = decltype(first_tag)::value;
         constexpr int SK = decltype(skip_tag)::value;          // SKIPROWS: 1 = position tile 0 idle under this tap (dy = -1), 2 = the last position tile idle (dy = +1)
         // Tap bookkeeping inside MFMA gaps (persistent tower with the address table): the next tap's NJ table entries are read in the load-free gaps of the
         // first k-step's second half-step, the NJ row addresses are formed in those of the last k-step's — one instruction per gap — instead of a
-        // block of ~15 instructions between two taps with the matrix pipe idle (NN_TAPGAP=0: A/B).
-        constexpr bool TAPGAP = NN_TAPGAP && PEEL && NN_ILV && NH + NJ <= NI * (NH - 1);
+        // block of ~15 instructions between two taps with the matrix pipe idle.
+        constexpr bool TAPGAP = PEEL && NH + NJ <= NI * (NH - 1);
         const bool in_gaps = TAPGAP && addr_tab != nullptr;
         if (tap + 1 < NTAPS && !in_gaps) {
 #pragma unroll
@@ -320,25 +301,6 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
             const int ks = tap * KSTEPS + kc;
 #pragma unroll
             for (int hs = 0; hs < 2; hs++) {
-                if (!NN_ILV) {
-                    if (hs == 0 && ks + PF < TOTAL_KS) {        // weights PF k-steps ahead (slot freed by the previous half-step)
-#pragma unroll
-                        for (int i = 0; i < NI; i++) aring[(kc + PF) & (RING - 1)][i] = ld_wfrag(wr, (size_t)(ks + PF) * W_KSTEP_STRIDE, wlane + i * 1024);
-                    }
-                    // activations of the next half-step
-                    if (hs == 0) {
-#pragma unroll
-                        for (int j = 0; j < NH; j++) if (!(SK == 2 && j == NH - 1)) bfrag[1][j] = LD(bcur[NH + j] + kc * 64);
-                    } else if (kc + 1 < KSTEPS) {
-#pragma unroll
-                        for (int j = 0; j < NH; j++) if (!(SK == 1 && j == 0)) bfrag[0][j] = LD(bcur[j] + (kc + 1) * 64);
-                    } else if (tap + 1 < NTAPS) {
-#pragma unroll
-                        for (int j = 0; j < NH; j++) if (!(SK == 1 && j == 0 && tap + 1 < 3)) bfrag[0][j] = LD(abs_addr(bnxt[j]));
-                    }
-                    asm volatile("" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                }
 #pragma unroll
                 for (int i = 0; i < NI; i++) {
                     bf16x8 a = __builtin_bit_cast(bf16x8, aring[kc & (RING - 1)][i]);
@@ -346,21 +308,19 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
                     for (int j = 0; j < NH; j++) {
                         const bool idle_hs = (SK == 1 && hs == 0) || (SK == 2 && hs == 1);            // this half-step has an idle position tile (border row)
                         const bool idle = idle_hs && j == (SK == 1 ? 0 : NH - 1);
-                        if (!idle) acc[i][hs * NH + j] = E::mfma(a, bfrag[hs][j], (FIRST && kc == 0) ? binit[i] : acc[i][hs * NH + j]);
-                        if (NN_ILV && !idle) {
+                        if (!idle) {
+                            acc[i][hs * NH + j] = E::mfma(a, bfrag[hs][j], (FIRST && kc == 0) ? binit[i] : acc[i][hs * NH + j]);
                             // one memory instruction per MFMA gap (an MFMA leaves 8 of its 16 cycles for other issue): first the next
                             // half-step's activations (LDS), then - in the first half-step - the weights PF k-steps ahead (L2).  m counts the MFMAs
                             // actually issued (a skipped border tile has no gap: its memory instruction would land in its neighbour's)
                             const int NR = idle_hs ? NH - 1 : NH, m = i * NR + (idle_hs && SK == 1 ? j - 1 : j);
                             if (m < NH) {
-                                if ((ABL & 2) || (SK == 2 && hs == 0 && m == NH - 1)) {}
-                                else if (hs == 0) bfrag[1][m] = LD(bcur[NH + m] + kc * 64);
-                                else if (kc + 1 < KSTEPS) { if (!(SK == 1 && m == 0)) bfrag[0][m] = LD(bcur[m] + (kc + 1) * 64); }
-                                else if (tap + 1 < NTAPS) { if (!(SK == 1 && m == 0 && tap + 1 < 3)) bfrag[0][m] = LD(abs_addr(bnxt[m])); }   // tile 0 is needed again from tap 3 on
+                                if (SK == 2 && hs == 0 && m == NH - 1) {}
+                                else if (hs == 0) LDA(bfrag[1][m], bcur[NH + m] + kc * 64);
+                                else if (kc + 1 < KSTEPS) { if (!(SK == 1 && m == 0)) LDA(bfrag[0][m], bcur[m] + (kc + 1) * 64); }
+                                else if (tap + 1 < NTAPS) { if (!(SK == 1 && m == 0 && tap + 1 < 3)) LDA(bfrag[0][m], abs_addr(bnxt[m])); }   // tile 0 is needed again from tap 3 on
                             } else if (m < NH + NI && hs == 0) {
-                                if (ABL & 1) {}
-                                else if (ks + PF < TOTAL_KS)
-                                    aring[(kc + PF) & (RING - 1)][m - NH] = ld_wfrag(wr, (size_t)(ks + PF) * W_KSTEP_STRIDE, wlane + (m - NH) * 1024);
+                                if (ks + PF < TOTAL_KS) WFRAG((kc + PF) & (RING - 1), ks + PF, m - NH);
                             } else if (TAPGAP && hs == 1 && m >= NH && m < NH + NJ) {
                                 if (in_gaps) {
                                     if (kc == 0) bnxt[m - NH] = tap_addr(tap + 1 < NTAPS ? tap + 1 : tap, m - NH);
@@ -368,13 +328,11 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
                                     else if (kc == KSTEPS - 1) bcur[m - NH] = abs_addr(bnxt[m - NH]);
                                 }
                             }
-#if NN_EXPLICIT_WAIT
-                            // last gap of a half-step: one wait for everything the next half-step consumes (see NN_EXPLICIT_WAIT)
+                            // last gap of a half-step: one wait for everything the next half-step consumes (see the header)
                             if (PEEL && m == NI * NR - 1) {
-                                if (NN_EXPLICIT_WAIT >= 2 && hs == 1) __builtin_amdgcn_s_waitcnt(0x0078);      // vmcnt(8) lgkmcnt(0): the next k-step's weights (two k-steps of loads stay in flight)
-                                else __builtin_amdgcn_s_waitcnt(0xC07F);                                     // lgkmcnt(0)
+                                if (hs == 1) __builtin_amdgcn_s_waitcnt(0x0078);      // vmcnt(8) lgkmcnt(0): the next k-step's weights (two k-steps of loads stay in flight)
+                                else __builtin_amdgcn_s_waitcnt(0xC07F);             // lgkmcnt(0)
                             }
-#endif
                             asm volatile("" ::: "memory");
                             __builtin_amdgcn_sched_barrier(0);
                         }
@@ -388,7 +346,7 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
             for (int j = 0; j < NJ; j++) bcur[j] = abs_addr(bnxt[j]);
         }
     };
-    constexpr bool SPLIT = !std::is_same<EPI, std::nullptr_t>::value && NTAPS == 9 && NN_ILV && PEEL && KSTEPS % RING == 0;
+    constexpr bool SPLIT = !std::is_same<EPI, std::nullptr_t>::value && NTAPS == 9 && PEEL && KSTEPS % RING == 0;
     // Last tap with its position halves in sequence (SPLIT): phase A finishes the accumulators of the first half (board 0), phase B runs the second
     // half and carries, in two of every 16 MFMA gaps, one tile of the first half's epilogue (accumulator read-out, bf16 pack, ReLU, LDS write) —
     // work that is otherwise exposed after the K loop.  Phase B reads the tap's weights a second time (virtual k-steps TOTAL_KS .. TOTAL_KS+KSTEPS-1
@@ -407,18 +365,15 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
                         acc[i][j] = E::mfma(a, bfrag[kc & 1][j], acc[i][j]);
                         const int m = i * NH + j;
                         if (m < NH) {
-                            if (ABL & 2) {}
-                            else if (kc + 1 < KSTEPS) bfrag[(kc + 1) & 1][m] = LD(bcur[m] + (kc + 1) * 64);
-                            else if (!(SKIPROWS && m == NH - 1)) bfrag[(kc + 1) & 1][m] = LD(bcur[NH + m]);            // first fragments of phase B
+                            if (kc + 1 < KSTEPS) LDA(bfrag[(kc + 1) & 1][m], bcur[m] + (kc + 1) * 64);
+                            else if (!(SKIPROWS && m == NH - 1)) LDA(bfrag[(kc + 1) & 1][m], bcur[NH + m]);            // first fragments of phase B
                         } else if (m < NH + NI) {
                             const int vks = ks + PF, wks = vks < TOTAL_KS ? vks : vks - KSTEPS;              // phase B re-reads this tap's weights
-                            if (!(ABL & 1)) aring[(kc + PF) & (RING - 1)][m - NH] = ld_wfrag(wr, (size_t)wks * W_KSTEP_STRIDE, wlane + (m - NH) * 1024);
+                            WFRAG((kc + PF) & (RING - 1), wks, m - NH);
                         } else if (kc == KSTEPS - 1 && (m == 2 * NH || m == 3 * NH)) {
                             epi0(m == 2 * NH ? 0 : 1, -1);                                                     // stage -1: operand prefetch for the first two tiles
                         }
-#if NN_EXPLICIT_WAIT >= 2
                         if (m == NI * NH - 1) __builtin_amdgcn_s_waitcnt(0x0078);                              // vmcnt(8) lgkmcnt(0), as in tap_body
-#endif
                         asm volatile("" ::: "memory");
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -435,10 +390,9 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
                             acc[i][NH + j] = E::mfma(a, bfrag[kc & 1][j], acc[i][NH + j]);
                         const int m = i * NH + j;
                         if (m < NH) {
-                            if (!(ABL & 2) && kc + 1 < KSTEPS && !(SKIPROWS && m == NH - 1)) bfrag[(kc + 1) & 1][m] = LD(bcur[NH + m] + (kc + 1) * 64);
+                            if (kc + 1 < KSTEPS && !(SKIPROWS && m == NH - 1)) LDA(bfrag[(kc + 1) & 1][m], bcur[NH + m] + (kc + 1) * 64);
                         } else if (m < NH + NI) {
-                            if (!(ABL & 1) && kc + PF < KSTEPS)
-                                aring[(kc + PF) & (RING - 1)][m - NH] = ld_wfrag(wr, (size_t)(tap * KSTEPS + kc + PF) * W_KSTEP_STRIDE, wlane + (m - NH) * 1024);
+                            if (kc + PF < KSTEPS) WFRAG((kc + PF) & (RING - 1), tap * KSTEPS + kc + PF, m - NH);
                         } else {
                             // 16 tiles of the first half over 8 k-steps: two per k-step, each in four stages of one or two instructions
                             // (gaps 8..11 and 12..15), so that a gap never carries more than an MFMA leaves free
@@ -452,45 +406,39 @@ __device__ __forceinline__ void conv_kloop16(const unsigned char* lds, const uin
             }
         }
     };
-    if (!skip) {
-        using SK0 = std::integral_constant<int, 0>;
-        if constexpr (SKIPROWS) {                              // taps 0..2 look one row up (tile 0 idle), 3..5 stay in the row, 6..8 look one row down (last tile idle)
-            using SK1 = std::integral_constant<int, 1>; using SK2 = std::integral_constant<int, 2>;
-            tap_body(0, std::integral_constant<bool, !ACCUM>{}, SK1{});
-            for (int tap = 1; tap < 3; tap++) tap_body(tap, std::false_type{}, SK1{});
-            for (int tap = 3; tap < 6; tap++) tap_body(tap, std::false_type{}, SK0{});
-            for (int tap = 6; tap < (SPLIT ? NTAPS - 1 : NTAPS); tap++) tap_body(tap, std::false_type{}, SK2{});
-            last_tap_split();
-        } else if constexpr (PEEL) {
-            tap_body(0, std::integral_constant<bool, !ACCUM>{}, SK0{});
-            for (int tap = 1; tap < (SPLIT ? NTAPS - 1 : NTAPS); tap++) tap_body(tap, std::false_type{}, SK0{});
-            last_tap_split();
-        } else {
-            for (int tap = 0; tap < NTAPS; tap++) tap_body(tap, std::false_type{}, SK0{});
-        }
+    using SK0 = std::integral_constant<int, 0>;
+    if constexpr (SKIPROWS) {                              // taps 0..2 look one row up (tile 0 idle), 3..5 stay in the row, 6..8 look one row down (last tile idle)
+        using SK1 = std::integral_constant<int, 1>; using SK2 = std::integral_constant<int, 2>;
+        tap_body(0, std::true_type{}, SK1{});
+        for (int tap = 1; tap < 3; tap++) tap_body(tap, std::false_type{}, SK1{});
+        for (int tap = 3; tap < 6; tap++) tap_body(tap, std::false_type{}, SK0{});
+        for (int tap = 6; tap < (SPLIT ? NTAPS - 1 : NTAPS); tap++) tap_body(tap, std::false_type{}, SK2{});
+        last_tap_split();
+    } else if constexpr (PEEL) {
+        tap_body(0, std::true_type{}, SK0{});
+        for (int tap = 1; tap < (SPLIT ? NTAPS - 1 : NTAPS); tap++) tap_body(tap, std::false_type{}, SK0{});
+        last_tap_split();
+    } else {
+        for (int tap = 0; tap < NTAPS; tap++) tap_body(tap, std::false_type{}, SK0{});
     }
 }
+
+#undef WFRAG
 
 // K loop of the ONE-board workgroup form (256 -> 256 channels, 3x3, persistent tower at up to #CUs boards): the same k-step order and the same MFMAs as conv_kloop16
 // — a board's result is bit-identical in both forms — but scheduled for four position tiles.  conv_kloop16 splits a k-step into two half-steps of NH position tiles; with
 // NH = 2 that is 8 MFMAs (128 cycles) between a fragment's ds_read_b128 and its use, a wait twice per k-step, and no room for the tap bookkeeping in the load-free gaps
 // (stamped: 24.2k cycles for 18.4k of MFMAs, 22.0k with every load removed; tools/tower_stamps.py 128 1 2 3 4).  Here a k-step is ONE phase of 16 MFMAs:
 //   gaps 0..3   the next k-step's four activation fragments (LDS; double-buffered by k-step parity: a whole k-step = 256 cycles ahead of their use)
-//   gaps 4..7   the weights PF = 3 k-steps ahead (L2, through the buffer descriptor)
+//   gaps 4..7   the weights PF = 3 k-steps ahead (L2, through the buffer descriptor; a ring 7 k-steps deep gained 2 %, DESIGN.md "one-board K loop")
 //   gaps 8..11  tap bookkeeping: k-step 0 reads the next tap's table entries, the last k-step forms the row addresses
 //   gap 15      one wait for everything the next k-step consumes.
 // ring_in: the first PF k-steps of weights (conv_prefetch16 under the previous epilogue).  ABL: 1 = no weight loads, 2 = no LDS reads (timing builds, results garbage).
-#ifndef NN_ONE_RING
-#define NN_ONE_RING 4                                      // weight ring of the one-board K loop: 4 or 8 slots (prefetch distance 3 or 7 k-steps of 256 cycles)
-#endif
-#ifndef NN_ONE_WHOT
-#define NN_ONE_WHOT 0                                      // timing probe: 1 = every k-step re-reads the first k-step's (cache-hot) weights; results garbage
-#endif
 template <int ABL = 0, class E = ElemBF16>
-__device__ __forceinline__ void conv_kloop16_one(const unsigned char* lds, const uint4* __restrict__ w, f32x4 (&acc)[4][4], uint4 (*ring_in)[4] /* [NN_ONE_RING - 1][4] */, const int img_off,
+__device__ __forceinline__ void conv_kloop16_one(const unsigned char* lds, const uint4* __restrict__ w, f32x4 (&acc)[4][4], uint4 (*ring_in)[4] /* [PF][4] */, const int img_off,
                                                  const float* __restrict__ bias, const int* addr_tab) {
-    constexpr int KSTEPS = NN_COUT / 32, NI = 4, NJ = 4, NTAPS = 9, RING = NN_ONE_RING, PF = RING - 1, TOTAL_KS = NTAPS * KSTEPS;
-    constexpr int W_KSTEP_STRIDE = NN_ONE_WHOT ? 0 : 16 * 64;
+    constexpr int KSTEPS = NN_COUT / 32, NI = 4, NJ = 4, NTAPS = 9, RING = 4, PF = RING - 1, TOTAL_KS = NTAPS * KSTEPS;
+    constexpr int W_KSTEP_STRIDE = 16 * 64;
     static_assert(KSTEPS % RING == 0, "ring slots must be compile-time indices");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kg = lane >> 4;
     const uint32_t wlane = (uint32_t)((wave * NI) * 64 + lane) * 16u;
@@ -509,13 +457,20 @@ __device__ __forceinline__ void conv_kloop16_one(const unsigned char* lds, const
         asm volatile("" : "+v"(a));                        // see conv_kloop16: keeps base + offset + row in one VGPR, the k offset in the ds_read immediate
         return a;
     };
-    auto LD = [](int addr) -> bf16x8 { return *(const __attribute__((address_space(3))) bf16x8*)(uint32_t)addr; };
+    // the ablation instrument, as in conv_kloop16: every activation-fragment read and every weight-fragment load of the loop.  LDW may capture here: this loop is
+    // not nested in lambdas of several shapes, and its code comes out the same either way; in conv_kloop16 only the captureless form does
+    auto LDA = [](bf16x8& frag, int addr) {
+        if constexpr (!(ABL & 2)) frag = *(const __attribute__((address_space(3))) bf16x8*)(uint32_t)addr;
+    };
+    auto LDW = [&](int slot, int ks, int i) {
+        if constexpr (!(ABL & 1)) aring[slot][i] = ld_wfrag(wr, (size_t)ks * W_KSTEP_STRIDE, wlane + i * 1024);
+    };
     int bcur[NJ], bnxt[NJ];
     bf16x8 bfrag[2][NJ];
 #pragma unroll
     for (int j = 0; j < NJ; j++) { bnxt[j] = addr_tab[j * 64 + lane]; bcur[j] = abs_addr(bnxt[j]); }
 #pragma unroll
-    for (int j = 0; j < NJ; j++) bfrag[0][j] = LD(bcur[j]);
+    for (int j = 0; j < NJ; j++) LDA(bfrag[0][j], bcur[j]);
     auto tap_body = [&](const int tap, auto first_tag) {
         constexpr bool FIRST = decltype(first_tag)::value;
 #pragma unroll
@@ -529,18 +484,15 @@ __device__ __forceinline__ void conv_kloop16_one(const unsigned char* lds, const
                     acc[i][j] = E::mfma(a, bfrag[kc & 1][j], (FIRST && kc == 0) ? binit[i] : acc[i][j]);
                     const int m = i * NJ + j;
                     if (m < NJ) {
-                        if (ABL & 2) {}
-                        else if (kc + 1 < KSTEPS) bfrag[(kc + 1) & 1][m] = LD(bcur[m] + (kc + 1) * 64);
-                        else if (tap + 1 < NTAPS) bfrag[(kc + 1) & 1][m] = LD(abs_addr(bnxt[m]));
+                        if (kc + 1 < KSTEPS) LDA(bfrag[(kc + 1) & 1][m], bcur[m] + (kc + 1) * 64);
+                        else if (tap + 1 < NTAPS) LDA(bfrag[(kc + 1) & 1][m], abs_addr(bnxt[m]));
                     } else if (m < NJ + NI) {
-                        if (!(ABL & 1) && ks + PF < TOTAL_KS)
-                            aring[(kc + PF) & (RING - 1)][m - NJ] = ld_wfrag(wr, (size_t)(ks + PF) * W_KSTEP_STRIDE, wlane + (m - NJ) * 1024);
+                        if (ks + PF < TOTAL_KS) LDW((kc + PF) & (RING - 1), ks + PF, m - NJ);
                     } else if (m < 2 * NJ + NI) {
                         if (kc == 0) bnxt[m - NJ - NI] = addr_tab[((tap + 1 < NTAPS ? tap + 1 : tap) * NJ + (m - NJ - NI)) * 64 + lane];
                         else if (kc == KSTEPS - 1) bcur[m - NJ - NI] = abs_addr(bnxt[m - NJ - NI]);
                     } else if (m == NI * NJ - 1) {
-                        if (RING == 4) __builtin_amdgcn_s_waitcnt(0x0078);  // vmcnt(8) lgkmcnt(0): the next k-step's weights and activations (two k-steps of weight loads stay in flight)
-                        else __builtin_amdgcn_s_waitcnt(0x4078);                // vmcnt(24) lgkmcnt(0): six k-steps of weight loads stay in flight (vmcnt = simm16[15:14]:[3:0])
+                        __builtin_amdgcn_s_waitcnt(0x0078);     // vmcnt(8) lgkmcnt(0): the next k-step's weights and activations (two k-steps of weight loads stay in flight)
                     }
                     asm volatile("" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
@@ -554,18 +506,9 @@ __device__ __forceinline__ void conv_kloop16_one(const unsigned char* lds, const
 
 // Byte offset of the 8-byte epilogue slot (image row, 4 channels from co) inside a 16x16x32-path image.  The 16 lanes of a ds_write_b64 group hold 16 rows
 // at one channel offset; at the 544-B pitch 8 B x (68 row) mod 128 B takes 4 values, so the store is 4-way bank-conflicted (SQ_LDS_BANK_CONFLICT: 17 % of the
-// LDS-array cycles of the tower).  NN_EPI_NOCONFLICT=1 is a TIMING-ONLY A/B build (results garbage): the same stores and residual reads go to conflict-free
-// addresses (the 16 lanes contiguous), which prices the conflicts in in-kernel cycles (tools/tower_stamps.py; profiles/r03g_*).
-#ifndef NN_EPI_NOCONFLICT
-#define NN_EPI_NOCONFLICT 0
-#endif
-__device__ __forceinline__ int epi_slot16(int row, int co) {
-#if NN_EPI_NOCONFLICT
-    return ((row >> 3) & 7) * 8192 + (co >> 2) * 128 + (((row >> 6) << 3) | (row & 7)) * 8;
-#else
-    return row * (NN_COUT * 2 + NN_PAD16) + co * 2;
-#endif
-}
+// LDS-array cycles of the tower).  A timing-only build that sent the same stores and residual reads to conflict-free addresses (the 16 lanes contiguous)
+// priced the conflicts at 0.05 % of a BasicBlock (profiles/r03g_lds_conflict_ab.txt), so the plain layout stays.
+__device__ __forceinline__ int epi_slot16(int row, int co) { return row * (NN_COUT * 2 + NN_PAD16) + co * 2; }
 
 // Staged epilogue functors for conv_kloop16's split last tap: tile p = i*4 + j (channel tile i, position tile j of the first half) in stages
 //   -1: operand prefetch (residual only)   0: accumulator read-out   1, 2: bf16 pack (+ residual) + ReLU of one register pair each   3: LDS write
@@ -606,7 +549,6 @@ template <int WGB, class E = ElemBF16> struct EpiResidual16 {
 // epilogue of ONE accumulator tile (channel tile i, position tile j): relu?(acc) -> bf16 -> LDS image (the accumulators started at the bias)
 template <int WGB, class E = ElemBF16>
 __device__ __forceinline__ void acc_tile_to_lds16(unsigned char* lds, const f32x4 (&acc)[4][4 * WGB], int i, int j, bool relu, RangeSeen& seen) {
-    constexpr int OPITCH = NN_COUT * 2 + NN_PAD16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = tile_row<WGB>(j, lane & 15), co = (wave * 4 + i) * 16 + 4 * (lane >> 4);
     const f32x4 v = acc[i][j];
@@ -619,7 +561,6 @@ __device__ __forceinline__ void acc_tile_to_lds16(unsigned char* lds, const f32x
 // the same with the residual: x <- relu(acc + x) in place on the LDS image (f32 add, one bf16 rounding)
 template <int WGB, class E = ElemBF16>
 __device__ __forceinline__ void acc_tile_residual16(unsigned char* xlds, const f32x4 (&acc)[4][4 * WGB], int i, int j, RangeSeen& seen) {
-    constexpr int OPITCH = NN_COUT * 2 + NN_PAD16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = tile_row<WGB>(j, lane & 15), co = (wave * 4 + i) * 16 + 4 * (lane >> 4);
     const f32x4 v = acc[i][j];
@@ -677,17 +618,15 @@ __device__ __forceinline__ void acc_to_lds16(unsigned char* lds, const f32x4 (&a
 
 // Phase stagger (speed only, never correctness): the two workgroups that share a CU are dispatched together and
 // would run load / MFMA / store phases in lock-step.  Measured: workgroups b and b + #CUs share a CU (round-robin
-// dispatch); HW_ID.WAVE_ID bit 0 selects the same set.  Delaying one of the first pair keeps later rounds out of phase.
-__device__ __forceinline__ void phase_stagger(int flags, int n_cu) {
-    const int stagger = (flags >> 8) & 0xFF;               // sleep units (~8k cycles each); 0 = off
-    if (!stagger) return;
-    bool second = false;
-    if (flags & 32) second = ((int)blockIdx.x >= n_cu && (int)blockIdx.x < 2 * n_cu);
-    if (flags & 64) second = ((int)blockIdx.x < 2 * n_cu) && ((__builtin_amdgcn_s_getreg(0x1804) & 1) != 0);
+// dispatch).  Delaying one of the first pair (3 sleeps of ~8k cycles) keeps later rounds out of phase.
+__device__ __forceinline__ void phase_stagger(int n_cu) {
+    const bool second = (int)blockIdx.x >= n_cu && (int)blockIdx.x < 2 * n_cu;
     if (__builtin_amdgcn_readfirstlane((int)second))
-        for (int i = 0; i < stagger; i++) __builtin_amdgcn_s_sleep(127);
+        for (int i = 0; i < 3; i++) __builtin_amdgcn_s_sleep(127);
 }
 
+// The first-generation 32x32x16 kernels (cross-checks; sz_nn_conv_bf16 / sz_nn_block_bf16 without SZ_NN_W16): one k-step = 16 channels, wave tile
+// 2 channel tiles(32) x 2*WGB position tiles(32), row pitch C_in*2 + 16 B, one shared zero row, weights 3 k-steps ahead through a 4-deep ring.
 // in  : [n_boards][64][CIN]  bf16 (NHWC)            w : packed fragments (see sz_nn_pack_weights)
 // out : [n_boards][64][256]  bf16 (NHWC)            bias : [256] f32 (BN folded)      res : optional residual
 template <int CIN, int NTAPS, int WGB /* boards per workgroup: 4 -> 1 workgroup/CU, 2 -> 2 workgroups/CU */>
@@ -695,16 +634,15 @@ __global__ __launch_bounds__(256, (WGB == 2 ? 2 : 1)) void k_conv_bf16(const uin
                                                       const uint16_t* __restrict__ res, uint16_t* __restrict__ out, int n_boards, int flags, int n_cu) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int board0 = blockIdx.x * WGB;
-    stage_tile<CIN, WGB>(lds, in, board0, n_boards, (flags & 2) != 0);
+    stage_tile<CIN, WGB, 16>(lds, in, board0, n_boards);
     __syncthreads();
-    if (WGB == 2) phase_stagger(flags, n_cu);
+    if (WGB == 2) phase_stagger(n_cu);
     f32x16 acc[NN_NI][2 * WGB];
-    if (CIN == 256 && NTAPS == 9 && WGB == 2 && (flags & 0x20000)) conv_kloop<CIN, NTAPS, WGB, true>(lds, w, acc, (flags & 8) != 0);
-    else conv_kloop<CIN, NTAPS, WGB>(lds, w, acc, (flags & 8) != 0);
+    conv_kloop<CIN, NTAPS, WGB>(lds, w, acc);
     __syncthreads();                                       // all waves are done reading the activation tile
-    if (!((flags & 4) && acc[0][0][0] != 12345.f)) acc_to_lds<WGB>(lds, acc, bias, false);
+    acc_to_lds<WGB>(lds, acc, bias, false);
     __syncthreads();
-    if (!(flags & 4)) lds_to_out<WGB>(lds, res, out, board0, n_boards, (flags & 1) != 0);
+    lds_to_out<WGB, 16>(lds, res, out, board0, n_boards, (flags & 1) != 0);
 }
 
 // One whole BasicBlock (network.py:66-83) per launch: out = relu(conv2(relu(conv1(x)+b1)) + b2 + x).
@@ -713,66 +651,69 @@ __global__ __launch_bounds__(256, (WGB == 2 ? 2 : 1)) void k_conv_bf16(const uin
 template <int WGB>
 __global__ __launch_bounds__(256, (WGB == 2 ? 2 : 1)) void k_block_bf16(const uint16_t* __restrict__ in, const uint4* __restrict__ w1, const float* __restrict__ b1,
                                                        const uint4* __restrict__ w2, const float* __restrict__ b2, uint16_t* __restrict__ out,
-                                                       int n_boards, int flags, int n_cu) {
+                                                       int n_boards, int n_cu) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int board0 = blockIdx.x * WGB;
-    stage_tile<256, WGB>(lds, in, board0, n_boards, false);
+    stage_tile<256, WGB, 16>(lds, in, board0, n_boards);
     __syncthreads();
-    if (WGB == 2) phase_stagger(flags, n_cu);
+    if (WGB == 2) phase_stagger(n_cu);
     f32x16 acc[NN_NI][2 * WGB];
-    conv_kloop<256, 9, WGB>(lds, w1, acc, false);
+    conv_kloop<256, 9, WGB>(lds, w1, acc);
     __syncthreads();
     acc_to_lds<WGB>(lds, acc, b1, true);                   // t = relu(bn1(conv1(x))), bf16, in place of x
     __syncthreads();
-    conv_kloop<256, 9, WGB>(lds, w2, acc, false);
+    conv_kloop<256, 9, WGB>(lds, w2, acc);
     __syncthreads();
     acc_to_lds<WGB>(lds, acc, b2, false);
     __syncthreads();
-    lds_to_out<WGB>(lds, in, out, board0, n_boards, true); // + x (re-read, still L2/MALL-resident), ReLU
+    lds_to_out<WGB, 16>(lds, in, out, board0, n_boards, true); // + x (re-read, still L2/MALL-resident), ReLU
 }
 
-template <int CIN, int NTAPS, int WGB>
-__global__ __launch_bounds__(256, (WGB == 2 ? 2 : 1)) void k_conv16_bf16(const uint16_t* __restrict__ in, const uint4* __restrict__ w, const float* __restrict__ bias,
+// in  : [n_boards][64][CIN]  bf16 (NHWC)            w : packed fragments (see sz_nn_pack_weights16)
+// out : [n_boards][64][256]  bf16 (NHWC)            bias : [256] f32 (BN folded)      res : optional residual
+// flags: bit 0 = ReLU, SZ_NN_IN_BITS = `in` is the bit-packed plane image (stem)
+template <int CIN, int NTAPS, int WGB /* boards per workgroup: 2 -> 70 KB of LDS -> 2 workgroups/CU, one's HBM phases hide partly under the other's MFMA phase */>
+__global__ __launch_bounds__(256, 2) void k_conv16_bf16(const uint16_t* __restrict__ in, const uint4* __restrict__ w, const float* __restrict__ bias,
                                                         const uint16_t* __restrict__ res, uint16_t* __restrict__ out, int n_boards, int flags, int n_cu) {
+    static_assert(WGB == 2, "launch bounds and phase_stagger are those of two-board workgroups");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int board0 = blockIdx.x * WGB;
     if (CIN == 128 && (flags & SZ_NN_IN_BITS)) stage_tile_bits<WGB, NN_PAD16>(lds, in, board0, n_boards);
-    else stage_tile<CIN, WGB, NN_PAD16>(lds, in, board0, n_boards, (flags & 2) != 0);
+    else stage_tile<CIN, WGB, NN_PAD16>(lds, in, board0, n_boards);
     __syncthreads();
-    if (WGB == 2) phase_stagger(flags, n_cu);
+    phase_stagger(n_cu);
     f32x4 acc[4][4 * WGB];
-    conv_kloop16<CIN, NTAPS, WGB>(lds, w, acc, (flags & 8) != 0, (flags & 0x100000) != 0, nullptr, 0, bias);
+    conv_kloop16<CIN, NTAPS, WGB>(lds, w, acc, nullptr, 0, bias);
+    __syncthreads();                                       // all waves are done reading the activation tile
+    acc_to_lds16<WGB>(lds, acc, nullptr, false);
     __syncthreads();
-    if (!((flags & 4) && acc[0][0][0] != 12345.f)) acc_to_lds16<WGB>(lds, acc, nullptr, false);
-    __syncthreads();
-    if (!(flags & 4)) lds_to_out<WGB, NN_PAD16>(lds, res, out, board0, n_boards, (flags & 1) != 0);
+    lds_to_out<WGB, NN_PAD16>(lds, res, out, board0, n_boards, (flags & 1) != 0);
 }
 
+// One whole BasicBlock (network.py:66-83) per launch: out = relu(conv2(relu(conv1(x)+b1)) + b2 + x).
+// conv1's result is written to LDS in the very layout conv2 reads, so it never travels to HBM: one tile load and one
+// tile store per block instead of two of each, and half the launches.  (Streaming, i.e. non-temporal, tile loads / stores / residual
+// re-reads were measured here: all-streaming +3 % slower, the residual re-read then misses; stores or residual alone within noise.)
 template <int WGB>
-__global__ __launch_bounds__(256, (WGB == 2 ? 2 : (WGB == 1 ? 3 : 1))) void k_block16_bf16(const uint16_t* __restrict__ in, const uint4* __restrict__ w1, const float* __restrict__ b1,
+__global__ __launch_bounds__(256, 2) void k_block16_bf16(const uint16_t* __restrict__ in, const uint4* __restrict__ w1, const float* __restrict__ b1,
                                                          const uint4* __restrict__ w2, const float* __restrict__ b2, uint16_t* __restrict__ out,
-                                                         int n_boards, int flags, int n_cu) {
+                                                         int n_boards, int n_cu) {
+    static_assert(WGB == 2, "launch bounds and phase_stagger are those of two-board workgroups");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int board0 = blockIdx.x * WGB;
-    const bool nt = (flags & 0x200000) != 0;               // A/B: streaming tile loads/stores
-    if (nt) stage_tile<256, WGB, NN_PAD16, true>(lds, in, board0, n_boards, false);
-    else stage_tile<256, WGB, NN_PAD16>(lds, in, board0, n_boards, false);
+    stage_tile<256, WGB, NN_PAD16>(lds, in, board0, n_boards);
     __syncthreads();
-    if (WGB == 2) phase_stagger(flags, n_cu);
+    phase_stagger(n_cu);
     f32x4 acc[4][4 * WGB];
-    conv_kloop16<256, 9, WGB>(lds, w1, acc, false, false, nullptr, 0, b1);
+    conv_kloop16<256, 9, WGB>(lds, w1, acc, nullptr, 0, b1);
     __syncthreads();
-    acc_to_lds16<WGB>(lds, acc, nullptr, true);
+    acc_to_lds16<WGB>(lds, acc, nullptr, true);            // t = relu(bn1(conv1(x))), bf16, in place of x
     __syncthreads();
-    conv_kloop16<256, 9, WGB>(lds, w2, acc, false, false, nullptr, 0, b2);
+    conv_kloop16<256, 9, WGB>(lds, w2, acc, nullptr, 0, b2);
     __syncthreads();
     acc_to_lds16<WGB>(lds, acc, nullptr, false);
     __syncthreads();
-    if (nt) lds_to_out<WGB, NN_PAD16, true>(lds, in, out, board0, n_boards, true);
-    else if ((flags & 0xC00000) == 0xC00000) lds_to_out<WGB, NN_PAD16, true, true>(lds, in, out, board0, n_boards, true);
-    else if (flags & 0x400000) lds_to_out<WGB, NN_PAD16, false, true>(lds, in, out, board0, n_boards, true);    // A/B: streaming stores only
-    else if (flags & 0x800000) lds_to_out<WGB, NN_PAD16, true, false>(lds, in, out, board0, n_boards, true);    // A/B: streaming residual re-read only
-    else lds_to_out<WGB, NN_PAD16>(lds, in, out, board0, n_boards, true);
+    lds_to_out<WGB, NN_PAD16>(lds, in, out, board0, n_boards, true);   // + x (re-read, still L2/MALL-resident), ReLU
 }
 
 // =================================================================================================================
@@ -955,7 +896,7 @@ __global__ __launch_bounds__(256, 2) void k_heads16_bf16(const uint16_t* __restr
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int p16 = lane & 15, kg = lane >> 4;
     const int board0 = blockIdx.x * WGB;
-    stage_tile<256, WGB, NN_PAD16>(lds, x, board0, n_boards, false);
+    stage_tile<256, WGB, NN_PAD16>(lds, x, board0, n_boards);
     const float4 wv4 = ((const float4*)wv)[lane];          // conv_v1 weights of channels 4*lane .. 4*lane+3
     __syncthreads();
     {   // value conv: wave w owns rows 32w .. 32w+31 (row = board*64 + position).  Every lane forms its 4-channel partial of all 32
@@ -980,7 +921,7 @@ __global__ __launch_bounds__(256, 2) void k_heads16_bf16(const uint16_t* __restr
         if (!(lane & 1) && board < n_boards) v1_out[(size_t)board * 64 + (row & 63)] = fmaxf(tot + bv, 0.f);
     }
     f32x4 acc[4][4 * WGB];
-    conv_kloop16<256, 1, WGB, 2, false, 0, false, E>(lds, w_p1, acc, false, false, nullptr, 0, b_p1);
+    conv_kloop16<256, 1, WGB, 2, false, 0, E>(lds, w_p1, acc, nullptr, 0, b_p1);
     __syncthreads();
     uint32_t seen = 0;
     acc_to_lds16<WGB, E>(lds, acc, nullptr, true, &seen);     // t over x, in the layout the MFMA B operand is read from
@@ -1056,31 +997,6 @@ __global__ __launch_bounds__(256, 2) void k_heads16_bf16(const uint16_t* __restr
     }
 }
 
-// x <- relu(acc + bias + x) in place on the LDS image (f32 add, one bf16 rounding): every lane owns its 4 channels x 1 position.
-// bias == nullptr: the accumulators already started at the bias.
-template <int WGB>
-__device__ __forceinline__ void acc_residual_inplace16(unsigned char* xlds, const f32x4 (&acc)[4][4 * WGB], const float* __restrict__ bias) {
-    constexpr int OPITCH = NN_COUT * 2 + NN_PAD16;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int p16 = lane & 15, kg = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < 4 * WGB; j++) {
-        const int row = tile_row<WGB>(j, p16);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int co = (wave * 4 + i) * 16 + 4 * kg;
-            f32x4 v = acc[i][j];
-            if (bias) v += *(const f32x4*)(bias + co);
-            uint2* px = (uint2*)(xlds + row * OPITCH + co * 2);
-            const uint2 r = *px;
-            uint2 o;
-            o.x = relu_bf16x2(pack_bf16x2(v[0] + bf16_lo(r.x), v[1] + bf16_hi(r.x)));
-            o.y = relu_bf16x2(pack_bf16x2(v[2] + bf16_lo(r.y), v[3] + bf16_hi(r.y)));
-            *px = o;
-        }
-    }
-}
-
 // =================================================================================================================
 // Whole tower in ONE persistent launch (network.py:176-184: stem + 19 BasicBlocks).  A workgroup (4 waves, one per
 // SIMD, one workgroup per CU) takes a 2-board tile through all 39 convolutions: the running activation x and the
@@ -1094,17 +1010,12 @@ __device__ __forceinline__ void acc_residual_inplace16(unsigned char* xlds, cons
 // =================================================================================================================
 // Phase stagger of the four waves of a persistent-tower workgroup.  After a barrier the waves run the K loop in lock-step, and every wave issues its
 // LDS fragment reads in the same 4 of 16 MFMA gaps of a half-step: 16 KiB wanted in 64 cycles from a 128 B/clk LDS.  Delaying wave w by w x 64 cycles
-// spreads the four read windows over the 256-cycle half-step.  NN_STAGGER=0 builds without it (A/B).
-#ifndef NN_STAGGER
-#define NN_STAGGER 1
-#endif
+// spreads the four read windows over the 256-cycle half-step.
 __device__ __forceinline__ void wave_stagger() {
-#if NN_STAGGER
     const int wave = threadIdx.x >> 6;
-    if (wave == 1) __builtin_amdgcn_s_sleep(1 * NN_STAGGER);
-    else if (wave == 2) __builtin_amdgcn_s_sleep(2 * NN_STAGGER);
-    else if (wave == 3) __builtin_amdgcn_s_sleep(3 * NN_STAGGER);
-#endif
+    if (wave == 1) __builtin_amdgcn_s_sleep(1);
+    else if (wave == 2) __builtin_amdgcn_s_sleep(2);
+    else if (wave == 3) __builtin_amdgcn_s_sleep(3);
 }
 
 #define NN_MAX_CONVS 40
@@ -1128,7 +1039,7 @@ template <int MODE /* 0 = shipped; 1 = stamps; 2/3/4 = stamps + K-loop ablation 
 __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restrict__ planes, TowerParams prm, uint16_t* __restrict__ out, int n_boards, int n_blocks, int flags,
                                                           unsigned long long* __restrict__ stamps) {
     constexpr bool STAMP_ = MODE != 0;
-    constexpr int ABL = MODE == 5 ? 4 : (MODE >= 2 ? MODE - 1 : 0);      // 5: stamps with the border-row skipping switched off (A/B of SKIPROWS)
+    constexpr int ABL = MODE >= 2 ? MODE - 1 : 0;
     constexpr int IMG = WGB * 64 * (NN_COUT * 2 + NN_PAD16) + NN_ZERO16;  // one activation image incl. its zero region
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* bufX = lds;
@@ -1145,14 +1056,13 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
     for (int e = threadIdx.x; e < 9 * 4 * WGB * 64; e += 256)
         addr_tab[e] = conv_tap_addr16<NN_COUT * 2 + NN_PAD16, 9, WGB>(e / (4 * WGB * 64), (e >> 6) % (4 * WGB), e & 15, (e >> 4) & 3);
     f32x4 acc[4][4 * WGB];
-    constexpr int TRING = WGB == 1 ? NN_ONE_RING : 4;
-    uint4 ring[TRING][4];                                              // next convolution's first weight fragments, fetched under the current epilogue
+    uint4 ring[4][4];                                                  // next convolution's first weight fragments, fetched under the current epilogue
     RangeSeen seen;                                                    // f16: per-half maximum of every pair this lane stored (range_track)
     if constexpr (std::is_same<E, ElemF16>::value) seen = range_none();
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int board0 = tile * WGB;
         TILESTAMP(0);
-        conv_prefetch16<4>(prm.w[0], (uint4 (&)[4][4])ring);
+        conv_prefetch16(prm.w[0], ring);
         if (prm.pace && threadIdx.x == 0) {
             // XCD-paced tile rounds: the 32 workgroups that share an XCD (blockIdx mod 8, round-robin dispatch) start every tile round together, so
             // that a layer's weights are fetched into the XCD's 4 MB L2 once per round and hit by the other 31: FETCH_SIZE 2.3-4.5e6 -> 1.43e6 KB raw
@@ -1167,12 +1077,12 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
         __syncthreads();                                               // previous tile's output image fully read
         TILESTAMP(1);
         if (flags & SZ_NN_IN_BITS) stage_tile_bits<WGB, NN_PAD16, E>(bufT, planes, board0, n_boards);
-        else stage_tile<128, WGB, NN_PAD16>(bufT, planes, board0, n_boards, false);
+        else stage_tile<128, WGB, NN_PAD16>(bufT, planes, board0, n_boards);
         __syncthreads();
         TILESTAMP(2);
-        conv_kloop16<128, 9, WGB, 4, true, 0, false, E>(lds, prm.w[0], acc, false, false, ring, IMG, prm.b[0], addr_tab);  // stem (reads bufT): x = relu(bn(conv1(planes)))
+        conv_kloop16<128, 9, WGB, 4, true, 0, E>(lds, prm.w[0], acc, ring, IMG, prm.b[0], addr_tab);  // stem (reads bufT): x = relu(bn(conv1(planes)))
         TILESTAMP(3);
-        if (n_blocks > 0) conv_prefetch16<TRING>(prm.w[1], ring);
+        if (n_blocks > 0) conv_prefetch16(prm.w[1], ring);
         acc_to_lds16<WGB, E>(bufX, acc, nullptr, true, &seen);
         __syncthreads();
         TILESTAMP(4);
@@ -1181,10 +1091,10 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
             TSTAMP(0);
             wave_stagger();
             auto epi_t = [&](int i, int j) { acc_tile_to_lds16<WGB, E>(bufT, acc, i, j, true, seen); };          // t = relu(bn1(conv1(x))); bufT is idle
-            if constexpr (WGB == 2) conv_kloop16<256, 9, WGB, 4, true, ABL, false, E>(bufX, prm.w[1 + 2 * blk], acc, false, false, ring, 0, prm.b[1 + 2 * blk], addr_tab, EpiTile16<WGB, E>(bufT, acc));
+            if constexpr (WGB == 2) conv_kloop16<256, 9, WGB, 4, true, ABL, E>(bufX, prm.w[1 + 2 * blk], acc, ring, 0, prm.b[1 + 2 * blk], addr_tab, EpiTile16<WGB, E>(bufT, acc));
             else conv_kloop16_one<ABL, E>(bufX, prm.w[1 + 2 * blk], acc, ring, 0, prm.b[1 + 2 * blk], addr_tab);
             TSTAMP(1);
-            conv_prefetch16<TRING>(prm.w[2 + 2 * blk], ring);
+            conv_prefetch16(prm.w[2 + 2 * blk], ring);
             if constexpr (WGB == 2) range_track_first_half<WGB, E>(bufT, seen);
 #pragma unroll
             for (int j = (WGB == 2 ? 2 * WGB : 0); j < 4 * WGB; j++)           // second position half; the first went out under the last tap (2-board form)
@@ -1195,10 +1105,10 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
             TSTAMP(3);
             wave_stagger();
             auto epi_x = [&](int i, int j) { acc_tile_residual16<WGB, E>(bufX, acc, i, j, seen); };             // x = relu(bn2(conv2(t)) + x): own elements only, nobody reads bufX now
-            if constexpr (WGB == 2) conv_kloop16<256, 9, WGB, 4, true, ABL, false, E>(lds, prm.w[2 + 2 * blk], acc, false, false, ring, IMG, prm.b[2 + 2 * blk], addr_tab, EpiResidual16<WGB, E>(bufX, acc));   // reads bufT
+            if constexpr (WGB == 2) conv_kloop16<256, 9, WGB, 4, true, ABL, E>(lds, prm.w[2 + 2 * blk], acc, ring, IMG, prm.b[2 + 2 * blk], addr_tab, EpiResidual16<WGB, E>(bufX, acc));   // reads bufT
             else conv_kloop16_one<ABL, E>(lds, prm.w[2 + 2 * blk], acc, ring, IMG, prm.b[2 + 2 * blk], addr_tab);
             TSTAMP(4);
-            if (blk + 1 < n_blocks) conv_prefetch16<TRING>(prm.w[3 + 2 * blk], ring);
+            if (blk + 1 < n_blocks) conv_prefetch16(prm.w[3 + 2 * blk], ring);
             if constexpr (WGB == 2) range_track_first_half<WGB, E>(bufX, seen);
 #pragma unroll
             for (int j = (WGB == 2 ? 2 * WGB : 0); j < 4 * WGB; j++)
@@ -1217,11 +1127,6 @@ __global__ __launch_bounds__(256, 1) void k_tower16_bf16(const uint16_t* __restr
 }
 
 
-static int default_flags(int flags, int wgb) {
-    if (wgb == 2 && !(flags & (32 | 64 | 0xFF00)) && !(flags & 0x10000)) flags |= 32 | (3 << 8);   // stagger the first co-resident pair
-    return flags;
-}
-
 template <int CIN, int NTAPS, int WGB> static int launch_conv(const void* in, const void* w, const float* bias, const void* res, void* out, int n_boards, int flags, hipStream_t s) {
     constexpr int PITCH = CIN * 2 + 16;
     const size_t lds_in = (size_t)(WGB * 64 + 1) * PITCH, lds_out = (size_t)(WGB * 64) * (NN_COUT * 2 + 16);
@@ -1234,12 +1139,12 @@ template <int CIN, int NTAPS, int WGB> static int launch_conv(const void* in, co
     }
     const int grid = (n_boards + WGB - 1) / WGB;
     hipLaunchKernelGGL((k_conv_bf16<CIN, NTAPS, WGB>), dim3(grid), dim3(256), lds, s, (const uint16_t*)in, (const uint4*)w, bias, (const uint16_t*)res,
-                       (uint16_t*)out, n_boards, default_flags(flags, WGB), device_cus());
+                       (uint16_t*)out, n_boards, flags, device_cus());
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
 
-template <int WGB> static int launch_block(const void* in, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int n_boards, int flags, hipStream_t s) {
+template <int WGB> static int launch_block(const void* in, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int n_boards, hipStream_t s) {
     const size_t lds = (size_t)(WGB * 64 + 1) * (256 * 2 + 16);
     static bool attr_flags[NN_MAX_DEVICES] = {};                       // function attributes are per device
     bool& attr_set = attr_flags[current_device_slot()];
@@ -1249,7 +1154,7 @@ template <int WGB> static int launch_block(const void* in, const void* w1, const
     }
     const int grid = (n_boards + WGB - 1) / WGB;
     hipLaunchKernelGGL((k_block_bf16<WGB>), dim3(grid), dim3(256), lds, s, (const uint16_t*)in, (const uint4*)w1, b1, (const uint4*)w2, b2, (uint16_t*)out,
-                       n_boards, default_flags(flags, WGB), device_cus());
+                       n_boards, device_cus());
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
@@ -1265,11 +1170,12 @@ template <int CIN, int NTAPS> static int launch_conv16(const void* in, const voi
         attr_set = true;
     }
     hipLaunchKernelGGL((k_conv16_bf16<CIN, NTAPS, WGB>), dim3((n_boards + WGB - 1) / WGB), dim3(256), lds, s, (const uint16_t*)in, (const uint4*)w, bias,
-                       (const uint16_t*)res, (uint16_t*)out, n_boards, default_flags(flags, WGB), device_cus());
+                       (const uint16_t*)res, (uint16_t*)out, n_boards, flags, device_cus());
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
-template <int WGB> static int launch_block16(const void* in, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int n_boards, int flags, hipStream_t s) {
+static int launch_block16(const void* in, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int n_boards, hipStream_t s) {
+    constexpr int WGB = 2;
     const size_t lds = (size_t)(WGB * 64) * (256 * 2 + NN_PAD16) + NN_ZERO16;
     static bool attr_flags[NN_MAX_DEVICES] = {};                       // function attributes are per device
     bool& attr_set = attr_flags[current_device_slot()];
@@ -1278,10 +1184,31 @@ template <int WGB> static int launch_block16(const void* in, const void* w1, con
         attr_set = true;
     }
     hipLaunchKernelGGL((k_block16_bf16<WGB>), dim3((n_boards + WGB - 1) / WGB), dim3(256), lds, s, (const uint16_t*)in, (const uint4*)w1, b1, (const uint4*)w2, b2,
-                       (uint16_t*)out, n_boards, default_flags(flags, WGB), device_cus());
+                       (uint16_t*)out, n_boards, device_cus());
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
+
+// Every instantiation of k_tower16_bf16 that exists, from one list: what selects a form, and its attribute call and its launch (both typed by TowerKernel).
+struct TowerForm {
+    int mode; bool f16, one;
+    hipError_t (*set_attr)();
+    void (*launch)(dim3 grid, hipStream_t s, const uint16_t* planes, const TowerParams& prm, uint16_t* out, int n_boards, int n_blocks, int flags, unsigned long long* stamps);
+};
+template <int MODE, class E, int WGB> struct TowerKernel {
+    static constexpr size_t LDS = 2 * ((size_t)(WGB * 64) * (NN_COUT * 2 + NN_PAD16) + NN_ZERO16) + 9 * 4 * WGB * 64 * sizeof(int);     // two images + tap address table
+    static hipError_t set_attr() { return hipFuncSetAttribute((const void*)k_tower16_bf16<MODE, E, WGB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); }
+    static void launch(dim3 grid, hipStream_t s, const uint16_t* planes, const TowerParams& prm, uint16_t* out, int n_boards, int n_blocks, int flags, unsigned long long* stamps) {
+        hipLaunchKernelGGL((k_tower16_bf16<MODE, E, WGB>), grid, dim3(256), LDS, s, planes, prm, out, n_boards, n_blocks, flags, stamps);
+    }
+    static constexpr TowerForm form() { return {MODE, std::is_same<E, ElemF16>::value, WGB == 1, &set_attr, &launch}; }
+};
+static const TowerForm TOWER_FORMS[] = {
+    TowerKernel<0, ElemBF16, 2>::form(), TowerKernel<0, ElemF16, 2>::form(), TowerKernel<0, ElemBF16, 1>::form(), TowerKernel<0, ElemF16, 1>::form(),     // shipped
+    TowerKernel<1, ElemBF16, 2>::form(), TowerKernel<1, ElemF16, 2>::form(), TowerKernel<1, ElemBF16, 1>::form(),                                        // stamps
+    TowerKernel<2, ElemBF16, 2>::form(), TowerKernel<3, ElemBF16, 2>::form(), TowerKernel<4, ElemBF16, 2>::form(),                                       // stamps + K-loop ablation
+    TowerKernel<2, ElemBF16, 1>::form(), TowerKernel<3, ElemBF16, 1>::form(), TowerKernel<4, ElemBF16, 1>::form(),
+};
 
 // host-side weight packing into MFMA A-fragment order of the 16x16x32 path, for either operand element
 template <class E> static int pack_weights16_impl(const float* w_in, int32_t cin_real, int32_t cin_padded, int32_t ksize, uint16_t* out) {
@@ -1316,6 +1243,7 @@ extern "C" {
 // Fused conv (+folded BN) + bias (+ residual) (+ ReLU), NHWC bf16, C_out = 256.
 //   ksize 3: 3x3 pad 1 (network.py:17-29 conv3x3) ; ksize 1: 1x1 (network.py:32-34 conv1x1)
 //   cin: 128 (stem, channels >= 119 are zero; with SZ_NN_W16 | SZ_NN_IN_BITS `in` is the bit-packed plane image) or 256.
+//   relu: bit 0 = ReLU; SZ_NN_W16 = 16x16x32 kernels and weight order; without it bit 16 selects 4-board workgroups of the 32x32x16 kernel (1 per CU).
 int sz_nn_conv_bf16(const void* in, const void* w_packed, const float* bias, const void* residual, void* out,
                     int32_t n_boards, int32_t cin, int32_t ksize, int32_t relu, void* stream) {
     if (!in || !w_packed || !bias || !out || n_boards <= 0) return SZ_ERR_INVALID;
@@ -1328,7 +1256,7 @@ int sz_nn_conv_bf16(const void* in, const void* w_packed, const float* bias, con
         if (ksize == 1 && cin == 256) return launch_conv16<256, 1>(in, w_packed, bias, residual, out, n_boards, relu, s);
         return SZ_ERR_INVALID;
     }
-    const bool wg4 = (relu & 16) != 0;                   // A/B switch: 4-board workgroups (1 per CU)
+    const bool wg4 = (relu & 16) != 0;
     if (ksize == 3 && cin == 256) return wg4 ? launch_conv<256, 9, 4>(in, w_packed, bias, residual, out, n_boards, relu, s)
                                              : launch_conv<256, 9, 2>(in, w_packed, bias, residual, out, n_boards, relu, s);
     if (ksize == 3 && cin == 128) return launch_conv<128, 9, 2>(in, w_packed, bias, residual, out, n_boards, relu, s);
@@ -1337,14 +1265,14 @@ int sz_nn_conv_bf16(const void* in, const void* w_packed, const float* bias, con
 }
 
 // One BasicBlock (network.py:36-83) in one launch: out = relu(conv3x3(relu(conv3x3(in, w1) + b1), w2) + b2 + in).
-// in/out [n_boards,64,256] bf16 NHWC (out must not alias in), weights from sz_nn_pack_weights, biases [256] f32.
+// in/out [n_boards,64,256] bf16 NHWC (out must not alias in), biases [256] f32; flags: SZ_NN_W16 = 16x16x32 kernel with weights from
+// sz_nn_pack_weights16, else the 32x32x16 kernel with weights from sz_nn_pack_weights.
 int sz_nn_block_bf16(const void* in, const void* w1_packed, const float* bias1, const void* w2_packed, const float* bias2, void* out,
                      int32_t n_boards, int32_t flags, void* stream) {
     if (!in || !w1_packed || !bias1 || !w2_packed || !bias2 || !out || in == out || n_boards <= 0) return SZ_ERR_INVALID;
     StreamDeviceGuard _guard(stream);
-    if (flags & SZ_NN_W16) return (flags & 0x80000) ? launch_block16<1>(in, w1_packed, bias1, w2_packed, bias2, out, n_boards, flags, (hipStream_t)stream)   // A/B: 1-board workgroups, 3-4 per CU
-                                                    : launch_block16<2>(in, w1_packed, bias1, w2_packed, bias2, out, n_boards, flags, (hipStream_t)stream);
-    return launch_block<2>(in, w1_packed, bias1, w2_packed, bias2, out, n_boards, flags, (hipStream_t)stream);
+    if (flags & SZ_NN_W16) return launch_block16(in, w1_packed, bias1, w2_packed, bias2, out, n_boards, (hipStream_t)stream);
+    return launch_block<2>(in, w1_packed, bias1, w2_packed, bias2, out, n_boards, (hipStream_t)stream);
 }
 
 // Weight packing for the 16x16x32 path: [taps][cin/32 k-steps][16 co tiles][64 lanes][8] bf16;
@@ -1395,25 +1323,10 @@ static int tower_launch(const void* planes, const void* const* w_packed, const f
         if (!w_packed[i] || !bias[i]) return SZ_ERR_INVALID;
         prm.w[i] = (const uint4*)w_packed[i]; prm.b[i] = bias[i];
     }
-    const size_t lds = 2 * ((size_t)(2 * 64) * (NN_COUT * 2 + NN_PAD16) + NN_ZERO16) + 9 * 8 * 64 * sizeof(int);   // two images + tap address table
-    const size_t lds1 = 2 * ((size_t)64 * (NN_COUT * 2 + NN_PAD16) + NN_ZERO16) + 9 * 4 * 64 * sizeof(int);         // the one-board form
     static bool attr_flags[NN_MAX_DEVICES] = {};                       // function attributes are per device
     bool& attr_set = attr_flags[current_device_slot()];
     if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<0, ElemF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<1, ElemF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<0, ElemBF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<0, ElemF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<1, ElemBF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<2, ElemBF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<3, ElemBF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        HIPCHK(hipFuncSetAttribute((const void*)k_tower16_bf16<4, ElemBF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+        for (const TowerForm& f : TOWER_FORMS) HIPCHK(f.set_attr());
         attr_set = true;
     }
     const int n_cu = device_cus();
@@ -1435,27 +1348,15 @@ static int tower_launch(const void* planes, const void* const* w_packed, const f
             pace_add = (unsigned long long)(n_tiles / (int)grid.x) * (grid.x / 8); pace_slot = &pace_total[slot];
         }
     }
-#define TOWER_LAUNCH(M) hipLaunchKernelGGL(k_tower16_bf16<M>, grid, dim3(256), lds, (hipStream_t)stream, (const uint16_t*)planes, prm, (uint16_t*)out, n_boards, n_blocks, (int)flags, g_tower_stamps)
-#define TOWER_LAUNCH1(M) hipLaunchKernelGGL((k_tower16_bf16<M, ElemBF16, 1>), grid, dim3(256), lds1, (hipStream_t)stream, (const uint16_t*)planes, prm, (uint16_t*)out, n_boards, n_blocks, (int)flags, g_tower_stamps)
-    if (one && g_tower_stamps && !(flags & SZ_NN_F16)) {               // diagnostic builds of the one-board form (bf16 operands): stamps, K-loop ablations 2-4
-        if (g_tower_mode == 2) TOWER_LAUNCH1(2); else if (g_tower_mode == 3) TOWER_LAUNCH1(3); else if (g_tower_mode == 4) TOWER_LAUNCH1(4); else TOWER_LAUNCH1(1);
-    }
-    else if (one && (flags & SZ_NN_F16))
-        hipLaunchKernelGGL((k_tower16_bf16<0, ElemF16, 1>), grid, dim3(256), lds1, (hipStream_t)stream, (const uint16_t*)planes, prm, (uint16_t*)out, n_boards, n_blocks, (int)flags, g_tower_stamps);
-    else if (one)
-        hipLaunchKernelGGL((k_tower16_bf16<0, ElemBF16, 1>), grid, dim3(256), lds1, (hipStream_t)stream, (const uint16_t*)planes, prm, (uint16_t*)out, n_boards, n_blocks, (int)flags, g_tower_stamps);
-    else if ((flags & SZ_NN_F16) && g_tower_stamps)
-        hipLaunchKernelGGL((k_tower16_bf16<1, ElemF16>), grid, dim3(256), lds, (hipStream_t)stream, (const uint16_t*)planes, prm, (uint16_t*)out, n_boards, n_blocks, (int)flags, g_tower_stamps);
-    else if (flags & SZ_NN_F16)
-        hipLaunchKernelGGL((k_tower16_bf16<0, ElemF16>), grid, dim3(256), lds, (hipStream_t)stream, (const uint16_t*)planes, prm, (uint16_t*)out, n_boards, n_blocks, (int)flags, g_tower_stamps);
-    else if (!g_tower_stamps) TOWER_LAUNCH(0);
-    else if (g_tower_mode == 2) TOWER_LAUNCH(2);
-    else if (g_tower_mode == 3) TOWER_LAUNCH(3);
-    else if (g_tower_mode == 4) TOWER_LAUNCH(4);
-    else if (g_tower_mode == 5) TOWER_LAUNCH(5);
-    else TOWER_LAUNCH(1);
-#undef TOWER_LAUNCH
-#undef TOWER_LAUNCH1
+    // the diagnostic builds (tools/tower_stamps.py) exist for bf16 operands, plus plain stamps for the two-board f16 form
+    const bool f16 = (flags & SZ_NN_F16) != 0;
+    int mode = !g_tower_stamps ? 0 : (g_tower_mode >= 2 && g_tower_mode <= 4 && !f16) ? g_tower_mode : 1;
+    if (one && f16) mode = 0;
+    const TowerForm* form = nullptr;
+    for (const TowerForm& f : TOWER_FORMS)
+        if (f.mode == mode && f.f16 == f16 && f.one == one) form = &f;
+    if (!form) return SZ_ERR_INVALID;
+    form->launch(grid, (hipStream_t)stream, (const uint16_t*)planes, prm, (uint16_t*)out, n_boards, n_blocks, (int)flags, g_tower_stamps);
     HIPCHK(hipGetLastError());
     if (pace_slot) *pace_slot += pace_add;
     return SZ_OK;

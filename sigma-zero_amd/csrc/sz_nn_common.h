@@ -12,26 +12,11 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-// streaming (non-temporal) 16-byte accesses for activation tiles: they are touched once per launch and should not evict
-// the layer's weights (2.4 MB per block, re-read by every workgroup) from the XCD's L2
-__device__ __forceinline__ uint4 ld_stream(const uint4* p) {
-    u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void st_stream(uint4* p, uint4 v) {
-    u32x4 t = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(t, (u32x4*)p);
-}
 
 #define NN_COUT 256
-#define NN_NI 2                                            // channel tiles (32) per wave
+#define NN_NI 2                                            // channel tiles (32) per wave of the 32x32x16 kernels
 #define NN_PAD16 32                                        // LDS row padding of the 16x16x32 path (bytes)
 #define NN_ZERO16 768                                      // zero region behind the rows of a 16x16x32-path image (see conv_kloop16 tap_addr)
-#ifndef NN_ILV
-#define NN_ILV 1                                           // K loop of the 16x16x32 path: memory instructions interleaved into the MFMA gaps (0 = issued in front of each group)
-#endif
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
@@ -109,9 +94,9 @@ template <class E> __device__ __forceinline__ void range_report(const RangeSeen&
     }
 }
 
-// ---- stage WGB boards' activations (NHWC rows of C_in bf16) into LDS, plus one zero row ---------------------
-template <int CIN, int WGB, int PAD = 16, bool NT = false, bool SWZ = false /* chunk swizzle of the split-precision images: chunk ^ ((position >> 2) & 1) */>
-__device__ __forceinline__ void stage_tile(unsigned char* lds, const uint16_t* __restrict__ in, int board0, int n_boards, bool skip) {
+// ---- stage WGB boards' activations (NHWC rows of C_in bf16) into LDS, plus the zero region (PAD 16: one zero row) behind them ----
+template <int CIN, int WGB, int PAD, bool SWZ = false /* chunk swizzle of the split-precision images: chunk ^ ((position >> 2) & 1) */>
+__device__ __forceinline__ void stage_tile(unsigned char* lds, const uint16_t* __restrict__ in, int board0, int n_boards) {
     constexpr int PITCH = CIN * 2 + PAD;
     constexpr int CHUNKS_PER_POS = CIN / 8;                // 16-B chunks per position
     constexpr int TOTAL = WGB * 64 * CHUNKS_PER_POS;
@@ -125,7 +110,7 @@ __device__ __forceinline__ void stage_tile(unsigned char* lds, const uint16_t* _
 #pragma unroll
     for (int i = 0; i < PER_THREAD; i++) {
         const int c = tid + i * 256;
-        stage[i] = (c < valid_chunks && !skip) ? (NT ? ld_stream(src + c) : src[c]) : make_uint4(0, 0, 0, 0);
+        stage[i] = c < valid_chunks ? src[c] : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < PER_THREAD; i++) {
@@ -164,28 +149,18 @@ __device__ __forceinline__ void stage_tile_bits(unsigned char* lds, const uint16
 // One weight fragment through a buffer descriptor: UNIFORM base (kernel argument -> 4 SGPRs) + uniform element offset (soffset, SGPR)
 // + the lane's constant 32-bit byte offset (voffset, one VGPR).  With flat global_load hipcc carried a 64-bit per-lane pointer per
 // weight stream and hoisted a dozen of them out of the tile loop of the persistent tower: those were its 24 spilled VGPRs (100 B/lane of
-// scratch, reloaded with vmcnt(0) waits once per tile — never inside a K loop, but serialising the first prefetch of every tile).
+// scratch, reloaded with vmcnt(0) waits once per tile — never inside a K loop, but serialising the first prefetch of every tile;
+// profiles/r02c_tower_stamps_buffer_loads.txt against r02c_tower_stamps_flat_loads.txt).
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-#ifndef NN_WBUF
-#define NN_WBUF 1                                          // 0: A/B build with flat global loads for the weight stream (SIGMAZERO_EXTRA_FLAGS=-DNN_WBUF=0)
-#endif
-#ifndef NN_ROWSKIP
-#define NN_ROWSKIP 1                                       // 0: A/B build that multiplies the all-zero border-row tiles too
-#endif
-struct WSrc { __amdgpu_buffer_rsrc_t r; const uint4* p; };
+struct WSrc { __amdgpu_buffer_rsrc_t r; };
 __device__ __forceinline__ WSrc wfrag_rsrc(const uint4* __restrict__ w) {
     WSrc s;
     s.r = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, 0x7FFFFFFF, 0x00020000);   // raw buffer, no stride; weights of one conv are < 2 MB
-    s.p = w;
     return s;
 }
 __device__ __forceinline__ uint4 ld_wfrag(const WSrc& s, size_t uniform_off, uint32_t lane_bytes) {
-#if NN_WBUF
     const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(s.r, (int)lane_bytes, (int)(uniform_off * 16), 0);
     return make_uint4(v.x, v.y, v.z, v.w);
-#else
-    return *(const uint4*)((const char*)(s.p + uniform_off) + lane_bytes);
-#endif
 }
 
 // Which 16 positions form MFMA position tile j: image row (= board*64 + position) of the tile's column p16.

@@ -59,7 +59,7 @@ __device__ __forceinline__ void split_kloop(const unsigned char* lds, const int 
     constexpr int KSTEPS = CIN / 32;
     constexpr int NJ = 4 * WGB, G = WGB;                   // position tiles; groups of 4 tiles per k-step
     constexpr int NPROD = BLO ? 3 : 2;
-    constexpr bool SKIPROWS = WGB == 2 && NN_ROWSKIP && NTAPS == 9;
+    constexpr bool SKIPROWS = WGB == 2 && NTAPS == 9;
     static_assert(NTAPS == 9 || NTAPS == 1, "3x3 or 1x1");
     static_assert(KSTEPS % SP_RING == 0, "ring slots must be compile-time indices");
     static_assert(8 + 2 * NI <= NPROD * NI * 3, "every memory instruction needs an MFMA gap of its own");
@@ -162,7 +162,7 @@ __device__ __forceinline__ void split_kloop(const unsigned char* lds, const int 
                             }
 #if SP_EXPLICIT_WAIT
                             // one explicit wait in a gap that carries no memory instruction, instead of hipcc's counted wait in front of every first use
-                            // (sz_nn.hip NN_EXPLICIT_WAIT): before the third product for the lo fragments, at the end of a group for the next group's hi
+                            // (as in sz_nn.hip conv_kloop16): before the third product for the lo fragments, at the end of a group for the next group's hi
                             // fragments, at the end of a k-step also for the next k-step's weights (SP_PF - 1 k-steps of 8 loads stay in flight)
                             if (q == 2 * NI * NR - 1 && NPROD == 3) __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0)
                             if (q == NPROD * NI * NR - 1) {
@@ -463,7 +463,7 @@ __global__ __launch_bounds__(256, 1) void k_tower_split(const uint16_t* __restri
         const int board0 = tile * WGB;
         // nobody reads the images here: the previous tile ended with epilogue + barrier, its output went out from registers
         if (flags & SZ_NN_IN_BITS) stage_tile_bits<WGB, NN_PAD16, E, true>(imgL, planes, board0, n_boards);
-        else stage_tile<128, WGB, NN_PAD16, false, true>(imgL, planes, board0, n_boards, false);
+        else stage_tile<128, WGB, NN_PAD16, true>(imgL, planes, board0, n_boards);
         __syncthreads();
         uint32_t ks = 0;
         const uint32_t ks_p1 = 36u + 72u * (uint32_t)(n_convs - 1);    // conv_p1's 8 k-steps follow the tower's in the stream

@@ -1,6 +1,6 @@
 #!/bin/bash
-# FETCH_SIZE of k_tower16_bf16 for A/B builds of the library (ab/lib_<name>.so built with SIGMAZERO_EXTRA_FLAGS, see sigma-zero_amd/build.py):
-#   bash tools/fetch_ab.sh <tag> new noskip flat flat_noskip        ("new" = the in-tree library)
+# FETCH_SIZE of k_tower16_bf16 for A/B builds of the library (ab/lib_<name>.so: SIGMAZERO_LIB builds of another checkout or flag set, see sigma-zero_amd/build.py):
+#   bash tools/fetch_ab.sh <tag> new <name>...        ("new" = the in-tree library)
 set -o pipefail
 TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
