@@ -5,7 +5,7 @@
 // One workgroup per channel: the channel's n_boards x 64 values (32 KB at batch 128) are read once into registers (re-read from L2 beyond 256 boards), two-pass
 // statistics (mean, then the sum of squared deviations — the same formula torch's native kernel uses, no E[x^2] - E[x]^2 cancellation), one pass out.
 // Backward (dy' = gy where y > 0): dbeta = sum dy', dgamma = sum dy' * xhat, dx = gamma * invstd * (dy' - dbeta / N - xhat * dgamma / N); the skip connection's
-// gradient is dy' itself.  All sums run in a fixed order (lane-strided partials, wave shuffles, then the sixteen wave sums in order): results are reproducible.
+// gradient is dy' itself.  All sums run in a fixed order (lane-strided f32 partials, then in double the wave shuffles and the sixteen wave sums in order): results are reproducible.
 // x, y, residual, gy, dx, dres: device [n_boards, channels, 8, 8] f32 NCHW.
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -16,15 +16,18 @@
 #define BN_NT 1024                                          // threads per workgroup: 16 waves keep enough loads in flight for a latency-bound pass over 32 KB
 #define BN_MAXV 4                                           // float4 per thread kept in registers: 1024 threads x 4 x 4 = 16,384 values = 256 boards
 
-__device__ __forceinline__ float bn_block_sum(float v, float* red) {
+// A thread's partial (f32, a few dozen terms) is widened to double for the cross-lane part: the 22 additions between a lane's partial and the channel's sum run
+// over partial sums as large as the result, and in f32 their rounding was most of a per-channel dbeta / dgamma / mean's error (tests/test_gpu_train_rows.py).
+__device__ __forceinline__ float bn_block_sum(float v32, double* red) {
+    double v = (double)v32;
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
     __syncthreads();                                                   // `red` may still be read from the previous reduction
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    float t = 0.f;
+    double t = 0.0;
 #pragma unroll
     for (int w = 0; w < BN_NT / 64; w++) t += red[w];                  // the wave sums in order
-    return t;
+    return (float)t;
 }
 
 // float4 index i of a channel's values -> element offset in the NCHW tensor: board i / 16, positions 4 * (i % 16) ..
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(BN_NT) void k_bn_act_fwd(const float* __restrict__ 
                                                     float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps,
                                                     const float* __restrict__ residual, float* __restrict__ y, float* __restrict__ save_mean,
                                                     float* __restrict__ save_invstd, int n_boards, int channels) {
-    __shared__ float red[BN_NT / 64];
+    __shared__ double red[BN_NT / 64];
     const int c = blockIdx.x, nv = n_boards * 16;                      // float4 per channel
     float4 v[BN_MAXV];
     float s = 0.f;
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(BN_NT) void k_bn_act_fwd(const float* __restrict__ 
 __global__ __launch_bounds__(BN_NT) void k_bn_act_bwd(const float* __restrict__ gy, const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gamma,
                                                     const float* __restrict__ save_mean, const float* __restrict__ save_invstd, float* __restrict__ dx,
                                                     float* __restrict__ dres, float* __restrict__ dgamma, float* __restrict__ dbeta, int n_boards, int channels) {
-    __shared__ float red[BN_NT / 64];
+    __shared__ double red[BN_NT / 64];
     const int c = blockIdx.x, nv = n_boards * 16;
     const float mean = save_mean[c], invstd = save_invstd[c];
     float4 d[BN_MAXV], h[BN_MAXV];                                     // dy' and xhat of the cached part

@@ -8,6 +8,16 @@ magnitude lands in [2^11, 2^12), the output is scaled back — gradients of 1e-7
   weight gradient         k_wgrad3x3_split + k_wgrad_reduce: the MFMA's reduction dimension is the position (a lane's 8 k-elements = one board row), the x block is
                           staged per board in LDS in three column-shifted copies (the next board's loads in flight under this board's MFMAs), 16 board groups write
                           partial sums that a second kernel adds.
+Range contract of the scaling (tests/trainref.py restates the arithmetic in fp64; tests/test_trainref.py, tests/test_gpu_train_rows.py and
+profiles/trainconv_rows.txt hold the kernels to it): "fp32's accuracy" holds per scaling UNIT — the board for forward and backward-data, the whole tensor (gy, and x)
+for the weight gradient — not per channel.  The unit's largest magnitude is scaled into [2^11, 2^12); an element within 2^14 of it has a normal f16 lo part and keeps
+22 bits; below that its absolute error stays at 2^-36 .. 2^-37 of the unit's maximum, so it loses one bit per octave: 11 bits (hi alone) 2^25 below the maximum,
+zero 2^36 below.  A convolution output sums over all input channels and stays in fp32's class whatever the spread inside a board.  A weight-gradient ROW dw[co]
+(COLUMN dw[:, ci]) whose gy (x) channel lies more than about 2^12 below the tensor's largest — Gaussian elements reach 2^2 under their channel's largest — is
+outside the contract: 1e-6 at 2^16, 2e-5 at 2^20, 3e-4 at 2^24, 2e-2 at 2^30 below (torch fp32: 2e-7 in every row), while the whole tensor's figure stays at 8e-8.
+Adam's update of a row does not shrink with its gradient, and channels with a BatchNorm gamma near zero make such rows (tests: one step in the trained regime of
+tests/nnref.py has 8 % of its dw rows and columns outside, worst row 1.3e-4 from fp64).  The follow-up is one scale per CHANNEL in the weight gradient: it factors out of the sum
+over boards and positions (dw[co][ci] = 2^-(k_co + k_ci) * sum), unlike a scale per board.
 One call through the C ABI per direction (sz_nn_conv3x3_train_fwd / _bwd): the host's time per convolution counts as much as the GPU's here.
   BatchNorm + skip + ReLU  k_bn_act_fwd / k_bn_act_bwd (csrc/sz_train.hip): one launch per direction and site; ConvBNAct makes convolution + BatchNorm + skip + ReLU ONE autograd node.
 MIOpen's fp32 kernels take 90-105 us (forward), 216 us (backward) per convolution at batch 128 — 78 % of an optimiser step; these take 41 us and 95 us.
