@@ -771,7 +771,7 @@ __global__ __launch_bounds__(256) void k_policy_head(const uint16_t* __restrict_
                 const int co = i * 16 + 4 * kg + r;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    float e = co < 73 ? __expf(acc[i][j][r] - mx) : 0.f;
+                    float e = co < 73 ? softmax_exp(acc[i][j][r] - mx) : 0.f;
                     acc[i][j][r] = e;
                     sum += e;
                 }
@@ -972,7 +972,7 @@ __global__ __launch_bounds__(256, 2) void k_heads16_bf16(const uint16_t* __restr
                 const int co = i * 16 + 4 * kg + r;
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
-                    const float e = co < 73 ? __expf(pa[i][j][r] - mx) : 0.f;
+                    const float e = co < 73 ? softmax_exp(pa[i][j][r] - mx) : 0.f;
                     pa[i][j][r] = e;
                     sum += e;
                 }

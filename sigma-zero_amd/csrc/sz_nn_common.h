@@ -61,6 +61,13 @@ struct ElemF16 {
 __device__ __forceinline__ float to_agpr(float v) { float a; asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v)); return a; }
 __device__ __forceinline__ float from_agpr(float a) { float v; asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a)); return v; }
 
+// exp(d), d = logit - row maximum <= 0, of the three softmax epilogues (k_policy_head, k_heads16_bf16, split_heads_tail).  __expf is one multiply by log2(e) and one
+// v_exp_f32, and v_exp_f32 delivers no subnormal result: everything below 2^-126 (d < -87.34) came out as 0, where torch's fp32 softmax keeps f32's subnormals
+// down to d = -103.97, and the search keeps a child iff its probability is not 0.  exp2f on the same product is the same v_exp_f32 from 2^-126 up (bit for bit
+// what __expf gave); below, the exponential is taken 2^64 higher (the + 64 is exact: the product's quantum is at least the sum's) and scaled down by one
+// v_ldexp_f32, which rounds once into the subnormal range.
+__device__ __forceinline__ float softmax_exp(float d) { return exp2f(d * 1.44269504088896340736f); }
+
 // ---- f16 range tracking (ElemF16 epilogues only; the bf16 instantiations carry none of it) ---------------------------------------------------------------
 // A stored activation of 65520 or more packs to +inf, the next convolution makes NaN of it (inf - inf), and the integer ReLU erases a NaN whose sign bit is set:
 // the overflow can leave a launch as finite garbage.  So it is remembered where it is created: AFTER the ReLU both halves of a packed pair are >= +0 as int16 and

@@ -386,7 +386,7 @@ __device__ __forceinline__ void split_heads_tail(unsigned char* lds, const int* 
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int co = i * 16 + 4 * kg + r;
-                    const float e = co < 73 ? __expf(pa[i][t][r] - mx) : 0.f;
+                    const float e = co < 73 ? softmax_exp(pa[i][t][r] - mx) : 0.f;
                     pa[i][t][r] = e;
                     ps += e;
                 }
