@@ -151,7 +151,8 @@ int sz_fetch_ply(sz_engine* e, uint8_t* packed_planes, int32_t* action, int32_t*
  * f32 of Gamma(alpha,1) draws, read when a search's ROOT is expanded (the step after sz_search_begin): root prior k becomes
  * 0.75*p_k + 0.25*g_k/sum_{j<K} g_j (one Dirichlet(alpha) sample over the K legal moves); inner nodes get no noise.  NULL restores
  * the reference behaviour (mcts.py:91-98: the constant noise_value at every expansion).  Needs learning = 1.  Refused (SZ_ERR_STATE) on an engine created
- * with reuse_subtree: a reused root is never expanded again, the noise would silently reach the first ply of a game only. */
+ * with reuse_subtree: a reused root is never expanded again, the noise would silently reach the first ply of a game only; sz_set_search_root_noise
+ * below noises kept roots as well and is the setter for such an engine. */
 int sz_set_root_noise(sz_engine* e, const float* gamma_dev);
 
 /* NON-REFERENCE option (default L = 1, lambda ignored): gather up to `leaves_per_step` leaves per board per
@@ -195,6 +196,50 @@ int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream);
  * on the mapping.  Synchronises the stream to return n_live. */
 int sz_compact_searching(sz_engine* e, void* planes_dev, int32_t* n_live_out, void* stream);
 
+/* NON-REFERENCE option, off by default: a ROOT VISIT TARGET per board, the form of a search budget that works with reuse_subtree (lc0 / KataGo:
+ * the budget names the root's visit count at the END of the search, visits a kept subtree already holds count towards it).
+ * targets: HOST array [n_boards], each entry in 0..num_searches; NULL = off (every board makes num_searches new simulations again).  Accepted on
+ * engines with and without reuse_subtree.  Only between searches (SZ_ERR_STATE during a search, the rule of sz_set_search_budgets; nothing is
+ * changed then); SZ_ERR_INVALID: an entry outside 0..num_searches.  Takes effect at the next sz_search_begin and holds until changed.
+ * With targets set, board b's search makes `goal` NEW simulations, computed by sz_search_begin where the root is known:
+ *   fresh root       goal = t_b: a new game, an upload, any of the three fresh-start conditions of sz_config.reuse_subtree, dropped subtrees,
+ *                    and every search of an engine without reuse_subtree.  This is exactly a budget of t_b: on an engine without reuse_subtree
+ *                    the call equals sz_set_search_budgets(targets) bit for bit.
+ *   continued search on a kept root with visit count N_kept: goal = max(0, t_b + 1 - N_kept).  The search ends with root visit count
+ *                    max(N_kept, 1 + t_b): what a fresh search with budget t_b ends with, or what was kept if that was more.
+ * With goal == 0 the board is done when sz_search_begin returns: it takes no network row after the next sz_compact_searching, and sz_play samples
+ * from the kept visit counts.  num_searches stays the capacity; the fresh-start conditions are unchanged.  Everything that reads a budget reads
+ * the goal: the gather end (simulations done + pending == goal), the done test, the solver counting a proven root out, the terminal-root shortcut
+ * (N = 1 + t_b).  sz_stats.simulations counts new simulations only; the per-ply record (sz_fetch_ply visits) is the root's children as they stand,
+ * kept visits included.  Targets and budgets exclude each other, the later setter wins (sz_set_search_budgets, NULL included, switches targets
+ * off); on a reuse_subtree engine sz_set_search_budgets(non-NULL) stays refused.  Works with sz_set_search_options (any L, solver on or off),
+ * sz_compact and sz_compact_searching.  With targets always on a kept subtree never exceeds num_searches nodes, so the doubled stores of
+ * reuse_subtree could be halved; that is not done.  Held bit for bit to the host restatement tests/targetref.py by
+ * tests/test_gpu_visit_targets.py.  Its effect on playing strength is unmeasured. */
+int sz_set_visit_targets(sz_engine* e, const int32_t* targets, void* stream);
+/* Valid after sz_search_begin: the NEW simulations each board's search makes (HOST array [n_boards]): the goal above with targets set, else the
+ * board's budget, else num_searches; 0 for a board that does not search.  Synchronises the stream.  It is what the host plans its segments of
+ * steps and shrinks from (search_segments). */
+int sz_search_goals(sz_engine* e, int32_t* goals, void* stream);
+/* NON-REFERENCE option, off by default: the root noise of sz_set_root_noise applied at the root of EVERY search, continued ones included, so
+ * that it works with reuse_subtree.  gamma_dev: device array [n_boards][SZ_MAX_MOVES] f32 of Gamma(alpha,1) draws, read by sz_search_begin
+ * (continued search) and by the step after it (fresh root); NULL = the reference behaviour.  Needs learning = 1.
+ *   continued search the kept root's K children get P_c = (0.75f*P_c) + (0.25f*(g_c / gs)), in place, in sz_search_begin before its descent-only
+ *                    launch.  The kept root was expanded as an inner node under this mode, inner nodes get no noise, so its children's priors
+ *                    are the clean renormalised policy.
+ *   fresh root       noised at expansion exactly as sz_set_root_noise does.
+ *   arithmetic       one device function for both sites: gs from lane-strided partial sums (lane l adds g[l], g[l+64], ... ascending) and an
+ *                    xor butterfly, every operator one IEEE rounding (-ffp-contract=off).
+ *   quiet            HOST array [n_boards] or NULL (no board is quiet).  quiet[b] != 0: board b's root gets no noise in the searches that
+ *                    follow, fresh or continued; its priors stay clean (KataGo: no noise on fast plies).
+ * On a reuse_subtree engine a call that switches between gamma_dev == NULL and non-NULL drops every kept subtree (a tree built under the
+ * reference's noise carries the constant in every node's priors, one built under root-only noise carries it nowhere); a call that only changes
+ * the pointer or `quiet` keeps them.  While this mode is on, a reuse_subtree engine refuses sz_set_root_noise (SZ_ERR_STATE): leave the mode
+ * through this setter.  Only between searches (SZ_ERR_STATE during a search; nothing is changed then).  On an engine without reuse_subtree and
+ * with quiet == NULL the call equals sz_set_root_noise.  Orthogonal to sz_set_search_options, sz_set_visit_targets, sz_compact and
+ * sz_compact_searching.  Held bit for bit to tests/targetref.py by tests/test_gpu_visit_targets.py.  Its effect on playing strength is unmeasured. */
+int sz_set_search_root_noise(sz_engine* e, const float* gamma_dev, const uint8_t* quiet, void* stream);
+
 /* NON-REFERENCE option, off by default: proven-result propagation (MCTS-Solver; lc0's "certainty propagation").  The reference backs a
  * checkmate leaf up as one more sample of -1; with enable != 0 the search also carries what is PROVEN up the tree.  Off, every kernel that
  * runs today runs unchanged (the solver is a template instantiation of its own, like leaf batching).
@@ -230,7 +275,8 @@ int sz_set_solver(sz_engine* e, int32_t enable, void* stream);
  * L > SZ_MAX_LEAVES_PER_STEP, virtual_loss negative or not finite.  {1, x, 0} leaves the engine exactly as if no setter had been called;
  * {L, lam, 0} on an engine without reuse_subtree equals sz_set_leaf_batching(L, lam), {1, x, 1} there equals sz_set_solver(1).  After it
  * sz_set_leaf_batching and sz_set_solver still apply their own refusals against the state now in force.  Still refused, and not part of
- * this option: sz_set_search_budgets with budgets != NULL on a reuse_subtree engine, sz_set_root_noise on a reuse_subtree engine.
+ * this option: sz_set_search_budgets with budgets != NULL on a reuse_subtree engine, sz_set_root_noise on a reuse_subtree engine (their
+ * counterparts for a reuse_subtree engine are sz_set_visit_targets and sz_set_search_root_noise).
  * Never called, every kernel that runs today runs unchanged (the combination is a template instantiation of its own).
  *
  * Setting changes on a reuse_subtree engine: a call that changes leaves_per_step or the solver flag drops every board's kept subtree; the next

@@ -59,6 +59,9 @@ EXPORTS = {
     "sz_solver_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_set_visit_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_search_goals": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_set_search_root_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sz_get_stats": (C.c_int, [C.c_void_p, C.POINTER(sz_stats), C.c_void_p]),
     "sz_root_children": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]),
     "sz_play": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -44,7 +44,8 @@ struct alignas(16) EdgeMeta { int first; int node; unsigned short n; unsigned sh
 // codes of sz_root_proven) and `complete` (bit 2: expansion kept every legal move as a child).  Zero when the option is off.
 enum { PR_UNKNOWN = 0, PR_WIN = 1, PR_DRAW = 2, PR_LOSS = 3, PR_MASK = 3, PR_COMPLETE = 4 };
 
-enum { ST_ACTIVE = 1, ST_PENDING = 2, ST_DONE = 4, ST_GAMEOVER = 8, ST_ERROR = 16, ST_SEARCHING = 32 };
+enum { ST_ACTIVE = 1, ST_PENDING = 2, ST_DONE = 4, ST_GAMEOVER = 8, ST_ERROR = 16, ST_SEARCHING = 32,
+       ST_QUIET = 64 };         // this search's root gets no root noise (sz_set_search_root_noise's quiet[b]); set by k_search_begin, gone after k_play
 
 struct alignas(16) Ctl {
     int status, n_nodes, n_edges, sims_done;
@@ -180,6 +181,24 @@ __device__ __forceinline__ int wave_solver_update(EdgeMeta* em, const int* path,
     }
     return proved;
 }
+
+// the root-noise mix of sz_set_root_noise / sz_set_search_root_noise over the K children ch[0..K) of a root, g = the board's Gamma draws:
+// gs from lane-strided partial sums (lane l adds g[l], g[l+64], ... ascending) and an xor butterfly, then P = 0.75*P + 0.25*(g/gs) in place.
+// One function for both sites: the d == 0 expansion of k_search_step (fresh root) and k_search_begin's reuse branch (kept root).
+__device__ __forceinline__ void wave_root_noise(EdgeStat* ch, const float* g, int K) {
+    const int lane = lane_id();
+    float gs = 0.f;
+    for (int c = lane; c < K; c += 64) gs = gs + g[c];
+    gs = wave_sum_butterfly(gs);
+    for (int c = lane; c < K; c += 64) ch[c].P = (0.75f * ch[c].P) + (0.25f * (g[c] / gs));
+}
+
+// what k_search_begin alone reads of sz_set_visit_targets / sz_set_search_root_noise: an argument of its own, so that View, which every kernel takes, stays as it is
+struct BeginOpts {
+    const int* target;          // sz_set_visit_targets: root visit target t of board b in 0..S, NULL = off.  k_search_begin turns it into the new
+    int* goal;                  //   simulations of this search, goal[b] (t on a fresh root, max(0, t + 1 - N_kept) on a kept one); View::budget points at goal
+    const uint8_t* quiet;       // sz_set_search_root_noise: quiet[b] != 0 = no root noise for board b; NULL = no board is quiet
+};
 
 struct BoardPtrs {
     SzPos* npos; SzPos* ring; EdgeStat* es; EdgeMeta* em; int* gpath; u64* pmask; Ctl* ctl;
@@ -495,13 +514,14 @@ __global__ void k_after_upload(View v, int b, int ply) {
 // SOLVE: proven results on (sz_set_solver): a terminal root is labelled like any terminal position
 // Both (sz_set_search_options) and either with reuse_subtree: the same code; a kept subtree carries its labels and has no descent in flight
 template <bool VL, bool SOLVE>
-__global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb) {
+__global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb, BeginOpts o) {
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
     BoardPtrs bp = board_ptrs(v, b);
     int status = uni(bp.ctl->status);
     if (v.rec_active && lane == 0) v.rec_active[b] = 0;
+    if (o.goal && lane == 0) o.goal[b] = 0;                   // sz_set_visit_targets: a board that does not search makes no simulation
     if (!(status & ST_ACTIVE) || (status & (ST_GAMEOVER | ST_ERROR))) {
         if (lane == 0) bp.ctl->status = status & ~(ST_PENDING | ST_DONE | ST_SEARCHING);
         return;
@@ -512,6 +532,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
         return;
     }
     const int root_ply = uni(bp.ctl->game_ply);
+    const int qbit = (o.quiet && uni((int)o.quiet[b])) ? ST_QUIET : 0;
     SzPos X = load_pos(bp.ring + (root_ply & (SZ_RING - 1)));
     path[0] = 0;
     if (v.reuse && uni(bp.ctl->reuse_ready) && uni(bp.ctl->n_nodes) <= v.S && 2 * (long long)uni(bp.ctl->n_edges) <= v.e_cap && v.S > 0) {
@@ -521,10 +542,19 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
         wave_load_history(bp, path, 0, root_ply, X, hist);
         __syncthreads();
         wave_encode(hist, X, nullptr, v.planes_dtype, v.rec_planes ? v.rec_planes + (size_t)b * SZ_NUM_PLANES * 8 : nullptr);   // training record of the root only
+        // sz_set_visit_targets: the kept root's visits count towards the target; the search ends with root N = max(N_kept, 1 + t).  goal == 0: done here
+        int goal = 1;
+        if (o.target) { goal = uni(o.target[b]) + 1 - uni(bp.es[0].N); if (goal < 0) goal = 0; }
+        // sz_set_search_root_noise: the kept root was expanded as an inner node, so its children hold the clean renormalised policy; mix them in place
+        if (v.learning && v.root_gamma && !qbit) {
+            const EdgeMeta rm = bp.em[0];
+            wave_root_noise(bp.es + uni(rm.first), v.root_gamma + (size_t)b * SZ_MAX_MOVES, uni((int)rm.n));
+        }
         if (lane == 0) {
             bp.npos[0] = X;
             Ctl* c = bp.ctl;
-            c->status = (status & ST_ACTIVE) | ST_SEARCHING; c->sims_done = 0; c->pend_node = -1; c->pend_depth = 0; c->reuse_ready = 0;
+            if (o.target) o.goal[b] = goal;
+            c->status = (status & ST_ACTIVE) | ST_SEARCHING | qbit | (goal == 0 ? ST_DONE : 0); c->sims_done = 0; c->pend_node = -1; c->pend_depth = 0; c->reuse_ready = 0;
             if constexpr (VL) c->n_pend = 0;                    // no root evaluation in flight: every in-flight count of the kept tree is 0, k[0] included
             if (v.rec_colour) v.rec_colour[b] = (uint8_t)szm_turn(X.meta);
         }
@@ -541,8 +571,9 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
         bp.em[0] = m;
         bp.gpath[0] = 0;
     }
-    int st = (status & ST_ACTIVE) | ST_SEARCHING;
-    const int budget = board_budget(v, b);
+    int st = (status & ST_ACTIVE) | ST_SEARCHING | qbit;
+    const int budget = o.target ? uni(o.target[b]) : board_budget(v, b);     // a fresh root: the visit target is a budget
+    if (o.target && lane == 0) o.goal[b] = budget;
     if (szm_term(X.meta) || budget <= 0) {
         // a terminal root: every simulation re-visits it (mcts.py:104-109); children stay empty
         if (lane == 0) {
@@ -685,15 +716,12 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
                 kept += __popcll(km);
             }
             if (first + kept > v.e_cap) { err = SZ_ERR_CAPACITY; kept = 0; }
-            if (v.learning && v.root_gamma && d == 0 && kept > 0) {
+            if (v.learning && v.root_gamma && d == 0 && kept > 0 && !(status & ST_QUIET)) {
                 // non-reference option (sz_set_root_noise): AlphaZero's root-only noise.  The K Gamma(alpha,1) draws of this board,
                 // normalised over its K children, are one Dirichlet(alpha) sample of dimension K; inner nodes keep their priors.
-                const float* g = v.root_gamma + (size_t)b * SZ_MAX_MOVES;
+                // A quiet board (ST_QUIET, sz_set_search_root_noise) keeps its clean priors.
                 __threadfence_block();                                      // the children were written by other lanes of this wave
-                float gs = 0.f;
-                for (int c = lane; c < kept; c += 64) gs = gs + g[c];
-                gs = wave_sum_butterfly(gs);
-                for (int c = lane; c < kept; c += 64) bp.es[first + c].P = (0.75f * bp.es[first + c].P) + (0.25f * (g[c] / gs));
+                wave_root_noise(bp.es + first, v.root_gamma + (size_t)b * SZ_MAX_MOVES, kept);
             }
             if (lane == 0) {
                 bp.em[leaf_edge].first = first; bp.em[leaf_edge].n = (unsigned short)kept;
@@ -1003,6 +1031,9 @@ struct sz_engine {
     int* d_slot; int* d_nlive;
     int* d_slot_next;               // sz_compact_searching: the mapping being built (swapped with d_slot when the call succeeds)
     int* d_budget;                  // sz_set_search_budgets: [n_boards], View::budget points here while budgets are set
+    int* d_target; int* d_goal;     // sz_set_visit_targets: [n_boards] each; bo.target / bo.goal and View::budget point here while targets are set
+    uint8_t* d_quiet;               // sz_set_search_root_noise: [n_boards], bo.quiet points here while a quiet array is set
+    BeginOpts bo;                   // k_search_begin's view of the two options; all NULL = off
     void* stage; size_t stage_bytes;    // sz_compact_searching: staging buffer of the row move, allocated on first use
     Batch vb;                       // sz_set_leaf_batching; vb.L == 1: the reference's search, nothing allocated
     int vb_cap;                     // L the batching buffers were allocated for
@@ -1102,13 +1133,15 @@ int sz_create(const sz_config* cfg, sz_engine** out) {
         (rc = dalloc(e, &v.rec_over, B)) || (rc = dalloc(e, &v.rec_result, B)) || (rc = dalloc(e, &v.rec_active, B)) ||
         (v.reuse && (rc = dalloc(e, &v.nmap, B * v.n_cap))) ||
         (rc = dalloc(e, &e->d_scharnagl, B)) || (rc = dalloc(e, &e->d_active, B)) || (rc = dalloc(e, &e->d_slot, B)) || (rc = dalloc(e, &e->d_nlive, 1)) ||
-        (rc = dalloc(e, &e->d_slot_next, B)) || (rc = dalloc(e, &e->d_budget, B))) {
+        (rc = dalloc(e, &e->d_slot_next, B)) || (rc = dalloc(e, &e->d_budget, B)) ||
+        (rc = dalloc(e, &e->d_target, B)) || (rc = dalloc(e, &e->d_goal, B)) || (rc = dalloc(e, &e->d_quiet, B))) {
         sz_destroy(e);
         return rc;
     }
     HIPCHK(hipMemset(v.ctl, 0, B * sizeof(Ctl)));
     HIPCHK(hipMemset(v.ring, 0, B * SZ_RING * sizeof(SzPos)));
     HIPCHK(hipMemset(v.rec_active, 0, B));
+    HIPCHK(hipMemset(e->d_goal, 0, B * sizeof(int)));
     HIPCHK(hipDeviceSynchronize());
     *out = e;
     return SZ_OK;
@@ -1189,6 +1222,44 @@ int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream) {
         HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
     }
     e->v.budget = budgets ? e->d_budget : nullptr;
+    e->bo.target = nullptr; e->bo.goal = nullptr;                             // budgets and visit targets exclude each other: the later setter wins
+    return SZ_OK;
+}
+
+int sz_set_visit_targets(sz_engine* e, const int32_t* targets, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (targets)
+        for (int b = 0; b < e->v.B; b++)
+            if (targets[b] < 0 || targets[b] > e->v.S) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if (targets) {
+        HIPCHK(hipMemcpyAsync(e->d_target, targets, (size_t)e->v.B * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
+    }
+    // k_search_begin writes each board's goal into d_goal; everything that reads a budget reads it from there
+    e->bo.target = targets ? e->d_target : nullptr;
+    e->bo.goal = targets ? e->d_goal : nullptr;
+    e->v.budget = targets ? e->d_goal : nullptr;
+    return SZ_OK;
+}
+
+int sz_search_goals(sz_engine* e, int32_t* goals, void* stream) {
+    if (!e || !goals) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = e->v.B;
+    std::vector<Ctl> h(B);
+    std::vector<int> bud(e->v.budget ? B : 0);                              // the goals (targets set), the budgets, or nothing: num_searches
+    HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, B * sizeof(Ctl), hipMemcpyDeviceToHost, s));
+    if (e->v.budget) HIPCHK(hipMemcpyAsync(bud.data(), e->v.budget, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < B; b++)
+        goals[b] = (h[b].status & ST_SEARCHING) ? (e->v.budget ? bud[b] : e->v.S) : 0;
     return SZ_OK;
 }
 
@@ -1233,7 +1304,33 @@ int sz_set_root_noise(sz_engine* e, const float* gamma_dev) {
     // a reused root (sz_config.reuse_subtree) was expanded as an inner node, on un-noised priors, and is never expanded again: root noise would silently
     // apply to the first ply of a game only.  The two non-reference options are therefore mutually exclusive.
     if (gamma_dev && e->v.reuse) return SZ_ERR_STATE;
+    // ... and a reuse engine that runs sz_set_search_root_noise leaves that mode through the same setter, which drops the kept subtrees
+    if (e->v.reuse && e->v.root_gamma) return SZ_ERR_STATE;
     e->v.root_gamma = gamma_dev;
+    e->bo.quiet = nullptr;
+    return SZ_OK;
+}
+
+int sz_set_search_root_noise(sz_engine* e, const float* gamma_dev, const uint8_t* quiet, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if (quiet) {
+        HIPCHK(hipMemcpyAsync(e->d_quiet, quiet, (size_t)e->v.B, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
+    }
+    // a tree built under the reference's noise carries the constant in every node's priors, one built under root-only noise carries it nowhere
+    const bool drop = e->v.reuse && ((gamma_dev != nullptr) != (e->v.root_gamma != nullptr));
+    e->v.root_gamma = gamma_dev;
+    e->bo.quiet = quiet ? e->d_quiet : nullptr;
+    if (drop) {
+        hipLaunchKernelGGL(k_drop_subtrees, dim3((e->v.B + 255) / 256), dim3(256), 0, s, e->v);
+        HIPCHK(hipGetLastError());
+    }
     return SZ_OK;
 }
 
@@ -1272,7 +1369,7 @@ int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     ENGINE_GUARD(e);
     with_search_options(e, [&](auto vl, auto solve) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
-        hipLaunchKernelGGL((k_search_begin<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{});
+        hipLaunchKernelGGL((k_search_begin<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo);
     });
     HIPCHK(hipGetLastError());
     if (e->v.reuse && planes_dev) {

@@ -108,6 +108,25 @@ def search_options_of(args):
     return int(L), float(lam), bool(solver), bool(combine)
 
 
+def visit_target_options_of(args):
+    """The self-play configuration of subtree reuse, checked: (visit_targets, quiet_fast_plies).  NON-REFERENCE, default off.
+
+    args["visit_targets"] = True lets args["reuse_subtree"] run together with args["playout_cap"] and args["root_dirichlet_alpha"], which are
+    refused without it.  The engine then uses sz_set_visit_targets in place of sz_set_search_budgets (a board's number names its root's visit
+    count at the END of the search; the visits a kept subtree already holds count towards it, so a cheap ply after a full one often needs no
+    network call at all) and sz_set_search_root_noise in place of sz_set_root_noise (the root is noised at every search, kept roots included).
+    Without args["playout_cap"] every board's target is num_searches.
+    args["quiet_fast_plies"] = True (needs visit_targets, playout_cap and root_dirichlet_alpha): fast plies are searched without root noise
+    (KataGo); the sampling temperature is not touched.  The effect of either on playing strength is unmeasured."""
+    vt, quiet = args.get("visit_targets", False), args.get("quiet_fast_plies", False)
+    for key, val in (("visit_targets", vt), ("quiet_fast_plies", quiet)):
+        if not isinstance(val, (bool, np.bool_)):
+            raise ValueError("args[%r] must be True or False, got %r" % (key, val))
+    if quiet and not (vt and args.get("playout_cap") is not None and args.get("root_dirichlet_alpha") is not None):
+        raise ValueError("args['quiet_fast_plies'] needs args['visit_targets'], args['playout_cap'] and args['root_dirichlet_alpha']")
+    return bool(vt), bool(quiet)
+
+
 def raise_if_overflowed(model):
     """ValueError when `model` keeps a range flag (FastPolicyNet / SplitPolicyNet: overflowed()) and a forward since the last look returned inf / NaN:
     with f16 operands a stored activation of 65520 or more is inf, the heads make NaN of it, and the search keeps a NaN prior without complaint.
@@ -144,6 +163,11 @@ class SelfPlayEngine:
             raise ValueError("args['max_shrinks'] must be an integer >= 0, got %r" % (ms,))
         self.max_shrinks = int(ms)
         self.budgets = None           # host copy of the budgets in force (None: every board num_searches)
+        # NON-REFERENCE option (default off): reuse_subtree as a self-play configuration, see visit_target_options_of
+        self.visit_targets, self.quiet_fast_plies = visit_target_options_of(self.args)
+        self.targets = None           # host copy of the visit targets in force (set_visit_targets)
+        self.quiet = None             # boards whose next searches get no root noise (set_quiet; visit_targets mode)
+        self.last_goals = None        # visit_targets mode: search_goals() of the last search()
         self._compact_on = False      # the mapping chosen by the last compact() call
         self._restore = False         # a search shrank the batch: the caller's mapping is put back before the next search begins
         # planes_dtype: torch.float32 / torch.bfloat16 -> [B,119,8,8] NCHW (reference layout);
@@ -182,10 +206,13 @@ class SelfPlayEngine:
         # NON-REFERENCE option (default off): args["root_dirichlet_alpha"] = alpha switches from the reference's noise (the constant
         # 1-2^-24 at every expansion, mcts.py:91-98) to AlphaZero's Dirichlet(alpha) noise on the root's children only
         self.root_alpha = self.args.get("root_dirichlet_alpha")
-        if self.root_alpha is not None and self.args.get("reuse_subtree", False):
+        if self.root_alpha is not None and self.args.get("reuse_subtree", False) and not self.visit_targets:
             raise ValueError("args['root_dirichlet_alpha'] and args['reuse_subtree'] exclude each other: a reused root was expanded as an inner node "
                              "(un-noised priors) and is never expanded again, so the root noise would reach the first ply of a game only")
         self._gamma = None
+        self.next_gamma = None        # [B, SZ_MAX_MOVES] draws for the next begin() in place of torch's generator (play_games' root_gamma)
+        if self.visit_targets:        # every board's target is num_searches until set_visit_targets says otherwise
+            self.set_visit_targets(np.full(self.B, self.S, np.int32))
 
     def close(self):
         if self._e:
@@ -249,6 +276,41 @@ class SelfPlayEngine:
         N.check(N.lib().sz_set_search_budgets(self._e, b.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "sz_set_search_budgets")
         self.budgets = b.copy()
 
+    def set_visit_targets(self, targets):
+        """Per-board root visit targets (sz_set_visit_targets, a NON-REFERENCE option): board b's next searches end with root visit count
+        max(N_kept, 1 + targets[b]); on a fresh root that is a budget of targets[b], a kept root's visits count towards it.  None = off.
+        Targets and budgets exclude each other: the later call wins."""
+        if targets is None:
+            N.check(N.lib().sz_set_visit_targets(self._e, None, self._stream()), "sz_set_visit_targets")
+            self.targets = None
+            return
+        t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        if t.shape[0] != self.B:
+            raise ValueError("set_visit_targets: %d targets for %d boards" % (t.shape[0], self.B))
+        N.check(N.lib().sz_set_visit_targets(self._e, t.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "sz_set_visit_targets")
+        self.targets, self.budgets = t.copy(), None
+
+    def search_goals(self):
+        """after begin(): the new simulations each board's search makes (sz_search_goals; synchronises the stream) -> int32 [B]"""
+        g = np.zeros(self.B, np.int32)
+        N.check(N.lib().sz_search_goals(self._e, g.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "sz_search_goals")
+        return g
+
+    def set_search_root_noise(self, gamma, quiet=None):
+        """set_root_noise for every search's root, continued searches on a kept subtree included (sz_set_search_root_noise).  quiet: per board,
+        != 0 = no root noise for that board in the searches that follow; None = no board is quiet.  On a reuse_subtree engine switching
+        between None and a tensor drops every kept subtree."""
+        self._gamma = None if gamma is None else gamma.to(self.device, torch.float32).contiguous()
+        q = None if quiet is None else np.ascontiguousarray(quiet, dtype=np.uint8).reshape(-1)
+        if q is not None and q.shape[0] != self.B:
+            raise ValueError("set_search_root_noise: %d quiet flags for %d boards" % (q.shape[0], self.B))
+        N.check(N.lib().sz_set_search_root_noise(self._e, _ptr(self._gamma), None if q is None else q.ctypes.data_as(C.c_void_p), self._stream()),
+                "sz_set_search_root_noise")
+
+    def set_quiet(self, quiet):
+        """visit_targets mode with root_dirichlet_alpha: the boards whose searches get no root noise from the next begin() on (None: none)"""
+        self.quiet = None if quiet is None else np.ascontiguousarray(quiet, dtype=np.uint8).reshape(-1).copy()
+
     def _compact_searching(self):
         """sz_compact_searching; returns n_live, or 0 when no board searches any more (the mapping is left alone then)"""
         n = C.c_int32()
@@ -282,8 +344,13 @@ class SelfPlayEngine:
         if self._restore:               # the last search shrank the batch: back to the mapping the caller chose (synchronises, like compact())
             self.compact(self._compact_on)
         if self.root_alpha is not None:
-            alpha = torch.full((self.B, N.SZ_MAX_MOVES), float(self.root_alpha), device=self.device)
-            self.set_root_noise(torch._standard_gamma(alpha))
+            gamma, self.next_gamma = self.next_gamma, None
+            if gamma is None:
+                gamma = torch._standard_gamma(torch.full((self.B, N.SZ_MAX_MOVES), float(self.root_alpha), device=self.device))
+            if self.visit_targets:
+                self.set_search_root_noise(gamma, self.quiet)
+            else:
+                self.set_root_noise(gamma)
         N.check(N.lib().sz_search_begin(self._e, _ptr(self.planes), self._stream()), "sz_search_begin")
 
     def step(self, policy, value):
@@ -317,14 +384,21 @@ class SelfPlayEngine:
         """All num_searches simulations for every active board (mcts.py:49-109).  The network sees n_rows * leaves_per_step rows.
         With budgets set the steps run in segments that end where boards run out of budget (search_segments), and after each segment
         the batch shrinks to the boards that still search; with max_shrinks > 0 it is also shrunk once right after the roots were made:
-        boards with budget 0 and terminal roots never take a row.  Without budgets there is one segment and no shrink."""
+        boards with budget 0 and terminal roots never take a row.  Without budgets there is one segment and no shrink.
+        args["visit_targets"]: the segments are planned from search_goals(), read after begin(); a board whose kept root already holds its
+        target is done at begin and never takes a row."""
         ev = evaluator or self.evaluate
         self.begin()
         self.last_steps = self.last_rows = 0
+        self.last_goals = None
         if self.n_rows <= 0:
             return
-        segs = search_segments(self.budgets, self.L, self.max_shrinks, self.S)
-        if self.budgets is not None and self.max_shrinks > 0 and self._compact_searching() == 0:
+        budgets = self.budgets
+        if self.visit_targets and self.targets is not None:
+            # the goals are known only once the roots are made (a kept root's visits count): one more stream synchronisation, in this mode only
+            budgets = self.last_goals = self.search_goals()
+        segs = search_segments(budgets, self.L, self.max_shrinks, self.S)
+        if budgets is not None and self.max_shrinks > 0 and self._compact_searching() == 0:
             return                                          # nothing to search: every board was done at begin
         for i, n in enumerate(segs):
             self._run_steps(ev, n)

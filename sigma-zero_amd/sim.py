@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -65,13 +65,13 @@ def playout_cap_of(args):
         raise ValueError("args['playout_cap']['fast'] must be an integer in 2..num_searches (%d), got %r" % (full, fast))
     if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= p <= 1.0:       # NaN fails both comparisons
         raise ValueError("args['playout_cap']['p_full'] must be a probability in [0, 1], got %r" % (p,))
-    if args.get("reuse_subtree", False):
+    if args.get("reuse_subtree", False) and not visit_target_options_of(args)[0]:
         raise ValueError("args['playout_cap'] and args['reuse_subtree'] exclude each other (sz_set_search_budgets)")
     return int(fast), float(p)
 
 
 def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, learning=True, planes_dtype=None, max_plies=100000,
-               verbose=False, n_boards=None, compact=True, stats=None, full_search=None):
+               verbose=False, n_boards=None, compact=True, stats=None, full_search=None, root_gamma=None):
     """Plays n_games games to the end and returns a list of per-game history dicts (sim.py:38-43 layout), game g at index g.
 
     The games run concurrently on `n_boards` board slots of one engine (default: one slot per game).  A slot whose game ends is
@@ -87,8 +87,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
       for every running game in game order (n_games == 1 reproduces the reference's stream; for several concurrent games the order of
       the draws necessarily differs from the reference's one-game-after-another order — generate_training_data(rng_order="reference")).
     max_plies: a game still running after that many plies is cut (result None, rewards 0); one number or one per game.
-    stats: optional dict, receives 'sims', 'nn_rows', 'plies' (work done; nn_rows = network rows evaluated), 'full_plies' / 'fast_plies' (game plies searched with
-      the full / the fast budget) and 'host_seconds' (the host's wall time per phase of the ply loop: enqueue_search returns before the GPU is done,
+    stats: optional dict, receives 'sims', 'nn_rows', 'plies' (work done; sims = new simulations, nn_rows = network rows evaluated), 'full_plies' / 'fast_plies' (game
+      plies searched with the full / the fast budget), 'searches_without_network' (lock-step searches that made no network call: args["visit_targets"]) and 'host_seconds' (the host's wall time per phase of the ply loop: enqueue_search returns before the GPU is done,
       wait_search is the wait for it).
 
     NON-REFERENCE option, off by default (the reference searches every ply with args['num_searches'] and records every ply, sim.py:46-76):
@@ -97,12 +97,21 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     full-search plies become training samples (states / actions / colours / packed_states); the game dict's 'sample_plies' lists the ply of
     each sample and 'rewards' takes its sign from that ply.  The batch shrinks to the full-search boards once the fast ones are done
     (SelfPlayEngine.search).  Noise and temperature are the same on fast and full plies (`learning` is per engine).
+    args["visit_targets"] = True (NON-REFERENCE, selfplay.visit_target_options_of): playout_cap and root_dirichlet_alpha together with
+    args["reuse_subtree"].  The per-ply numbers np.where(sampled, num_searches, n_fast) are then root visit TARGETS: the visits of the kept
+    subtree count, stats['sims'] are the new simulations actually made, and the root is noised at every ply.  With
+    args["quiet_fast_plies"] = True fast plies are searched without root noise; the sampling temperature is not touched.  Strength effect unmeasured.
     full_search(game, ply) -> bool: the full / fast decision, like `uniforms`.  Default: a numpy Generator of its own, drawn per ply for every
-      running game in game order — never the global numpy or `random` state, whose draw order the callers above depend on."""
+      running game in game order — never the global numpy or `random` state, whose draw order the callers above depend on.
+    root_gamma(game, ply) -> 218 floats: the Gamma(alpha, 1) draws of args["root_dirichlet_alpha"] for that game's root at that ply, like
+      `uniforms`.  Default: torch's generator, one draw per board slot and ply (the records then depend on the slot a game runs in)."""
     import random
     pcap = playout_cap_of(args)                             # validated before anything is created
+    vt, quiet_fast = visit_target_options_of(args)
     if full_search is not None and pcap is None:
         raise ValueError("full_search needs args['playout_cap']")
+    if root_gamma is not None and args.get("root_dirichlet_alpha") is None:
+        raise ValueError("root_gamma needs args['root_dirichlet_alpha']")
     if not torch.cuda.is_available():
         raise RuntimeError("self-play needs an MI355X (HIP) device: the search has no CPU fallback")
     dev = model_device(model)                               # the model's own GPU (a rank with local_rank > 0 plays on ITS device)
@@ -127,7 +136,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     slot_game = np.full(B, -1, dtype=np.int64)            # game running on each board slot, -1 = none
     plies = np.zeros(n_games, dtype=np.int64)             # plies played so far per game
     next_game = 0
-    work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0)
+    work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0, searches_without_network=0)
 
     def refill(slots):
         """start the next waiting games on these slots (ChessTensor.__init__/start_board for each); the rest go dark"""
@@ -188,7 +197,17 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             for s_ in running[np.argsort(slot_game[running], kind="stable")]:      # decisions in game order
                 g = int(slot_game[s_])
                 sampled[s_] = bool(full_search(g, int(plies[g]))) if full_search is not None else bool(cap_rng.random() < pcap[1])
-            eng.set_budgets(np.where(sampled, S, pcap[0]))
+            if vt:
+                eng.set_visit_targets(np.where(sampled, S, pcap[0]))
+                if quiet_fast:
+                    eng.set_quiet(~sampled)
+            else:
+                eng.set_budgets(np.where(sampled, S, pcap[0]))
+        if root_gamma is not None:
+            gam = np.zeros((B, 218), dtype=np.float32)
+            for s_ in running:
+                gam[s_] = np.asarray(root_gamma(int(slot_game[s_]), int(plies[slot_game[s_]])), dtype=np.float32)
+            eng.next_gamma = torch.from_numpy(gam).to(dev)
         eng.search()                                       # enqueues num_searches x (network + tree step); returns before the GPU is done
         t0 = lap("enqueue_search", t0)
         if pending is not None:
@@ -209,7 +228,11 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         ply_of_slot = np.where(slot_game >= 0, plies[np.maximum(slot_game, 0)], -1)
         pending = (rec, slot_game.copy(), sampled, ply_of_slot)
         n_full = int(sampled[running].sum())
-        work["sims"] += S * n_full + (pcap[0] if pcap is not None else 0) * (len(running) - n_full); work["nn_rows"] += eng.last_rows; work["plies"] += 1
+        if vt:                                             # the goals actually made: a kept root's visits count towards its target
+            work["sims"] += int(eng.last_goals[running].sum()) if eng.last_goals is not None else 0
+        else:
+            work["sims"] += S * n_full + (pcap[0] if pcap is not None else 0) * (len(running) - n_full)
+        work["nn_rows"] += eng.last_rows; work["plies"] += 1; work["searches_without_network"] += eng.last_steps == 0
         work["full_plies"] += n_full; work["fast_plies"] += len(running) - n_full
         plies[slot_game[running]] += 1
         done = [int(s_) for s_ in running if (rec["game_over"][s_] and rec["active"][s_]) or plies[slot_game[s_]] >= cap[slot_game[s_]]]

@@ -499,6 +499,15 @@ def main(argv=None):
                     help="NON-REFERENCE: playout-cap randomisation, simulations of a fast ply (2..--searches); fast plies are played but not trained on (0 = off: "
                          "every ply gets --searches and becomes a sample, like the reference)")
     ap.add_argument("--playout-cap-full-prob", type=float, default=0.25, help="probability that a ply gets the full --searches (with --playout-cap-fast)")
+    ap.add_argument("--visit-targets", action="store_true",
+                    help="NON-REFERENCE: self-play keeps the subtree of the move played (reuse_subtree) and the per-ply simulation numbers are root visit "
+                         "targets: kept visits count, the root is re-noised at every ply (args['visit_targets']); strength effect unmeasured")
+    ap.add_argument("--root-dirichlet-alpha", type=float, default=0.0,
+                    help="NON-REFERENCE: Dirichlet(alpha) noise on the root's children only instead of the reference's constant (0 = off); with subtree reuse "
+                         "only together with --visit-targets")
+    ap.add_argument("--quiet-fast-plies", action="store_true",
+                    help="NON-REFERENCE: fast plies are searched without root noise (needs --visit-targets, --playout-cap-fast and --root-dirichlet-alpha); the "
+                         "sampling temperature is not touched; strength effect unmeasured")
     a = ap.parse_args(argv)
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     gpr = [int(x) for x in str(a.games_per_rank).split(",")]
@@ -534,6 +543,14 @@ def main(argv=None):
         args["solver"] = True
     if a.playout_cap_fast:
         args["playout_cap"] = {"fast": a.playout_cap_fast, "p_full": a.playout_cap_full_prob}
+    if a.root_dirichlet_alpha:
+        args["root_dirichlet_alpha"] = a.root_dirichlet_alpha
+    if a.visit_targets:
+        args.update(reuse_subtree=True, visit_targets=True)
+        if a.leaves_per_step != 1 or a.solver:
+            args["combine_options"] = True
+    if a.quiet_fast_plies:
+        args["quiet_fast_plies"] = True
     import random
     random.seed(1000 + rank)
     np.random.seed(1000 + rank)
@@ -562,7 +579,9 @@ def main(argv=None):
                 with open(os.path.join(a.log_dir, "RL_cycles.jsonl"), "a") as f:        # one record per cycle: what self-play cost and what it yielded (rank 0's share)
                     f.write(json.dumps({"epoch": epoch, "games": a.games_per_rank, "samples": n_samples, "full_plies": sp_stats.get("full_plies"),
                                         "fast_plies": sp_stats.get("fast_plies"), "network_rows": sp_stats.get("nn_rows"), "simulations": sp_stats.get("sims"),
-                                        "playout_cap": args.get("playout_cap")}) + "\n")
+                                        "playout_cap": args.get("playout_cap"), "visit_targets": bool(args.get("visit_targets", False)),
+                                        "quiet_fast_plies": bool(args.get("quiet_fast_plies", False)),
+                                        "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"
                   % (epoch, world, a.games_per_rank, n_samples, len(hist), last[0], last[1]), flush=True)
