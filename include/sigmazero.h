@@ -330,6 +330,51 @@ int sz_debug_tree_proven(sz_engine* e, int32_t board, int32_t max_nodes, int8_t*
  * NON-terminal node, out[1] nodes proven by the update rule (terminal leaves not counted).  sz_stats is unchanged. */
 int sz_solver_stats(sz_engine* e, uint64_t out[2], void* stream);
 
+/* NON-REFERENCE option, off by default: FORCED PLAYOUTS and POLICY-TARGET PRUNING (KataGo).  Root noise only helps if a noised move that is
+ * good gets enough visits to show it, and the visits noise buys for bad moves must not end up in the policy target.  With the option on, the
+ * root of a board's search orders a minimum of visits for every child it has tried, and sz_play takes them out of the record again where the
+ * search did not confirm them.  Never switched on, every kernel that runs today runs unchanged (the option is a template instantiation of its
+ * own, k_search_begin / k_search_step / k_play<.., ForcedOpts>, as leaf batching and the solver are).
+ * k == 0 switches the option off (boards is ignored); k > 0 and finite switches it on for the boards with boards[b] != 0 (HOST array
+ * [n_boards]; NULL = all boards).  SZ_ERR_INVALID: k negative or not finite, or k > 0 on an engine created with learning = 0 (an exploration
+ * option of self-play, like root noise).  Only between searches (SZ_ERR_STATE during a search, the rule of sz_set_search_budgets; nothing is
+ * changed then).  Takes effect at the next sz_search_begin, which latches the board's bit into its status word (ST_FORCED beside ST_QUIET;
+ * sz_play clears it), and holds until changed: a call between the end of a search and its sz_play does not change that sz_play.
+ * The tree is never modified by the option, so changing k or boards does not drop kept subtrees.  Orthogonal to sz_set_search_options (any L,
+ * solver on or off), sz_set_visit_targets, sz_set_search_budgets, sz_set_search_root_noise, sz_compact and sz_compact_searching, on engines
+ * with and without reuse_subtree.  Every operator below is one IEEE rounding (-ffp-contract=off).
+ *   forced selection  in sz_search_step and in sz_search_begin's descent-only launch, at depth 0 only, on boards with the bit set.  The root's
+ *                  children are c = 0..K-1 with counts n_c = N_c + k_c (k_c the in-flight count, 0 without leaf batching), n_p = N_root +
+ *                  k_root (what selection takes as the parent's count) and T = n_p - 1.  Child c is FORCED when n_c >= 1 and
+ *                  (double)n_c < sqrt(((double)k * (double)P_c) * (double)T), P_c the prior as stored (after any root noise).  With the solver
+ *                  a child proven WIN is not forced whenever the arg-max skips WIN children.  If at least one child is forced the selected
+ *                  child is the forced child with the lowest index (counted in sz_forced_stats out[0]); otherwise selection is Node.select
+ *                  exactly as without the option.  Below the root nothing changes.  A NaN or negative product forces nothing.
+ *   pruning        in sz_play, on boards with the bit set, after the zero-visit check (which stays on the counted visits).  T = N_root - 1,
+ *                  sq = (float)sqrt((double)N_root), c* = the first maximum of N_c in action order, best = get_ucb(N*, W*, P*, sq, c_puct).
+ *                  For every other child with N_c >= 1: m_c = min(N_c, (int)floor(sqrt(((double)k*(double)P_c)*(double)T))) (0 when the root
+ *                  is NaN); q_c = the q term of get_ucb at the counted N_c, W_c, held fixed; n' = N_c; at most m_c times: cand = n' - 1,
+ *                  u = (((1.0f/(float)(cand+1)) * sq) * c_puct) * P_c, if q_c + u < best then n' = cand, else stop.  Afterwards, if n' < N_c
+ *                  and n' <= 1, n' = 0.  Children with N_c = 0 and c* keep their counts.  sz_forced_stats out[1] grows by the sum of N_c - n'.
+ *   the pruned counts  are what the record holds (sz_fetch_ply visits), and what sz_play samples or arg-maxes from, with the same sequential
+ *                  f64 arithmetic and total' = the sum of n'.  Forced visits are exploration the search ordered, not evidence.  The
+ *                  solver's WIN-root rule stays on top.  sz_root_children, sz_debug_tree and the subtree kept by reuse_subtree show the
+ *                  counted visits, unchanged.
+ * Held bit for bit to the host restatement tests/forcedref.py by tests/test_gpu_forced_playouts.py.  Its effect on playing strength is unmeasured. */
+int sz_set_forced_playouts(sz_engine* e, float k, const uint8_t* boards, void* stream);
+/* forced-playout counters, all boards, cumulative since the option was first switched on (synchronises): out[0] root selections decided by a
+ * forced child, out[1] visits that pruning took out of the records.  sz_stats is unchanged. */
+int sz_forced_stats(sz_engine* e, uint64_t out[2], void* stream);
+/* test: the DEVICE code of forced selection and of pruning (the functions the option's k_search_step and k_play call) on caller-supplied
+ * children, one wavefront per case, in the manner of sz_debug_select.  Case c owns children offsets[c]..offsets[c+1] (<= SZ_MAX_MOVES each) of
+ * vc (N), inflight (k), value_sum (f64), prior (f32) and proven (codes of sz_root_proven; NULL = the instantiations without the solver);
+ * parent_visits[c] (n_p), c_puct[c], forced_k[c]; virtual_loss is one number for all cases.  Writes per case the selected child and whether a
+ * forced child decided it, and, for the case read as a finished search with N_root = parent_visits[c] (in-flight counts ignored), every child's
+ * pruned count and c*.  All device pointers. */
+int sz_debug_forced(const int32_t* offsets_dev, const int32_t* vc_dev, const int32_t* inflight_dev, const double* value_sum_dev, const float* prior_dev,
+                    const int8_t* proven_dev, const int32_t* parent_visits_dev, const float* c_dev, const float* forced_k_dev, float virtual_loss,
+                    int32_t* selected_out_dev, int32_t* forced_out_dev, int32_t* pruned_out_dev, int32_t* cstar_out_dev, int32_t n_cases, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

@@ -57,6 +57,9 @@ EXPORTS = {
     "sz_root_proven": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sz_debug_tree_proven": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_solver_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_set_forced_playouts": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "sz_forced_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_debug_forced": (C.c_int, [C.c_void_p] * 9 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_set_visit_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

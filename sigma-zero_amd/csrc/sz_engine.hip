@@ -45,7 +45,8 @@ struct alignas(16) EdgeMeta { int first; int node; unsigned short n; unsigned sh
 enum { PR_UNKNOWN = 0, PR_WIN = 1, PR_DRAW = 2, PR_LOSS = 3, PR_MASK = 3, PR_COMPLETE = 4 };
 
 enum { ST_ACTIVE = 1, ST_PENDING = 2, ST_DONE = 4, ST_GAMEOVER = 8, ST_ERROR = 16, ST_SEARCHING = 32,
-       ST_QUIET = 64 };         // this search's root gets no root noise (sz_set_search_root_noise's quiet[b]); set by k_search_begin, gone after k_play
+       ST_QUIET = 64,           // this search's root gets no root noise (sz_set_search_root_noise's quiet[b]); set by k_search_begin, gone after k_play
+       ST_FORCED = 128 };       // this search's root forces playouts and its record is pruned (sz_set_forced_playouts' boards[b]); set by k_search_begin, gone after k_play
 
 struct alignas(16) Ctl {
     int status, n_nodes, n_edges, sims_done;
@@ -116,12 +117,19 @@ __device__ __forceinline__ u64 view_to_squares(u64 m, int white) {
 // Node.get_ucb (mctsnode.py:33-37) in torch's float32 operation order; see oracle/oc_mcts.c:oc_ucb.
 // Compiled with -ffp-contract=off: each operator is one IEEE rounding.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ucb_value(int vc, double wsum, float prior, float sqrt_parent, float c) {
+// its two terms, each on its own for sz_set_forced_playouts' pruning, which holds q fixed while it lowers the visit count under u
+__device__ __forceinline__ float ucb_q(int vc, double wsum) {
     float vsum = (float)wsum;
     float t1 = (float)vc + 1e-6f;
-    float q = 1.0f - ((vsum / t1) + 1.0f) / 2.0f;
+    return 1.0f - ((vsum / t1) + 1.0f) / 2.0f;
+}
+__device__ __forceinline__ float ucb_u(int vc, float prior, float sqrt_parent, float c) {
     float r = 1.0f / (float)(vc + 1);
-    float u = ((r * sqrt_parent) * c) * prior;
+    return ((r * sqrt_parent) * c) * prior;
+}
+__device__ __forceinline__ float ucb_value(int vc, double wsum, float prior, float sqrt_parent, float c) {
+    float q = ucb_q(vc, wsum);
+    float u = ucb_u(vc, prior, sqrt_parent, c);
     return q + u;
 }
 
@@ -156,6 +164,93 @@ __device__ __forceinline__ int wave_select_child(const EdgeStat* ch, const EdgeM
         if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
     }
     return uni(bi);
+}
+
+// NON-REFERENCE option (sz_set_forced_playouts): what the FORCED instantiations take on top of View, an argument of their own like BeginOpts
+struct ForcedOpts {
+    float k;                    // the forced constant of the searches begun since the last sz_search_begin
+    const uint8_t* boards;      // [B] != 0: the board's next search is forced and pruned; k_search_begin latches it into ST_FORCED
+    unsigned long long* stat;   // [B][2] root selections decided by a forced child, visits pruning took out of the records
+};
+// The FORCED instantiation of a kernel is the one that takes a ForcedOpts as one more, last argument: k_search_step<VL, SOLVE, ForcedOpts>
+// against k_search_step<VL, SOLVE>, whose argument list, and with it every line of its code, is what it was before the option existed
+template <typename... FO> constexpr bool is_forced = sizeof...(FO) > 0;
+__device__ __forceinline__ const ForcedOpts& forced_opts(const ForcedOpts& fo) { return fo; }
+
+// forced playouts at a root (sz_set_forced_playouts): child c with n_c = N_c + k_c >= 1 visits is forced while n_c < sqrt((k * P_c) * T) in f64,
+// T = parentVC - 1.  Returns the forced child with the lowest index, -1 when none is forced.  Lanes = children as in wave_select_child; with
+// SOLVE a child proven WIN is not forced whenever the arg-max skips WIN children.  A NaN or negative product forces nothing.
+template <bool VL, bool SOLVE>
+__device__ __forceinline__ int wave_forced_child(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float fk) {
+    const int lane = lane_id();
+    bool skip_wins = false;
+    if constexpr (SOLVE) {
+        bool open = false;
+        for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
+        skip_wins = __ballot(open) != 0;
+    }
+    const double T = (double)(parentVC - 1);
+    int fi = 0x7fffffff;
+    for (int c = lane; c < n && fi == 0x7fffffff; c += 64) {
+        if constexpr (SOLVE) { if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue; }
+        const EdgeStat s = ch[c];
+        int nc = s.N;
+        if constexpr (VL) nc += k[c];
+        if (nc >= 1 && (double)nc < sqrt(((double)fk * (double)s.P) * T)) fi = c;
+    }
+    for (int off = 32; off >= 1; off >>= 1) { const int oi = __shfl_xor(fi, off); if (oi < fi) fi = oi; }
+    fi = uni(fi);
+    return fi == 0x7fffffff ? -1 : fi;
+}
+
+// selection at the root of a forced board: the lowest forced child if there is one (*forced = true), else wave_select_child as everywhere
+template <bool VL, bool SOLVE>
+__device__ __forceinline__ int wave_select_root_forced(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam, float fk,
+                                                       bool* forced) {
+    int bi = wave_forced_child<VL, SOLVE>(ch, cm, k, n, parentVC, fk);
+    *forced = bi >= 0;
+    if (bi < 0) bi = wave_select_child<VL, SOLVE>(ch, cm, k, n, parentVC, c_puct, lam, nullptr);
+    return bi;
+}
+
+// policy-target pruning of a finished search (sz_set_forced_playouts): vis[0..n) holds the root children's counted visits N_c on entry and the
+// pruned counts n' on return (LDS, lanes = children).  c* = the first maximum of N_c keeps its count; every other visited child loses visits one
+// at a time, at most m_c = min(N_c, floor(sqrt((k * P_c) * (rootN - 1)))) of them, while its PUCT value with q held at the counted N_c, W_c stays
+// below c*'s; a child left with one visit loses that too.  Returns the visits taken out (uniform); *cstar_out (optional) = c*.
+__device__ __forceinline__ int wave_prune(const EdgeStat* ch, int n, int rootN, float c_puct, float fk, int* vis, int* cstar_out) {
+    const int lane = lane_id();
+    int bn = -1, bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) { const int nc = vis[c]; if (nc > bn) { bn = nc; bi = c; } }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
+        if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+    }
+    const int cs = uni(bi);
+    const float sq = (float)sqrt((double)rootN);
+    const EdgeStat top = ch[cs];
+    const float best = ucb_value(vis[cs], top.W, top.P, sq, c_puct);
+    const double T = (double)(rootN - 1);
+    int cut = 0;
+    for (int c = lane; c < n; c += 64) {
+        const int nc = vis[c];
+        if (c == cs || nc < 1) continue;
+        const EdgeStat s = ch[c];
+        const double lim = sqrt(((double)fk * (double)s.P) * T);
+        int m = 0;                                                          // NaN (a NaN prior, a negative product): nothing is pruned
+        if (lim >= (double)nc) m = nc; else if (lim >= 0.0) m = (int)floor(lim);
+        const float q = ucb_q(nc, s.W);
+        int np = nc;
+        for (int i = 0; i < m; i++) {
+            const int cand = np - 1;
+            if (q + ucb_u(cand, s.P, sq, c_puct) < best) np = cand; else break;
+        }
+        if (np < nc && np <= 1) np = 0;
+        vis[c] = np;
+        cut += nc - np;
+    }
+    for (int off = 32; off >= 1; off >>= 1) cut += __shfl_xor(cut, off);
+    if (cstar_out && lane == 0) *cstar_out = cs;
+    return uni(cut);
 }
 
 // solver update after a backup whose last node path[d] has just become proven: walk towards the root; the parent of a newly proven node is
@@ -513,8 +608,10 @@ __global__ void k_after_upload(View v, int b, int ply) {
 // VL: leaf batching on (sz_set_leaf_batching): the root is pending leaf 0 (leaf_ptrs), its network input goes to row slot(b)*L
 // SOLVE: proven results on (sz_set_solver): a terminal root is labelled like any terminal position
 // Both (sz_set_search_options) and either with reuse_subtree: the same code; a kept subtree carries its labels and has no descent in flight
-template <bool VL, bool SOLVE>
-__global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb, BeginOpts o) {
+// FO = ForcedOpts (sz_set_forced_playouts): the board's bit of fo.boards is latched into its status word beside ST_QUIET
+template <bool VL, bool SOLVE, typename... FO>
+__global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb, BeginOpts o, FO... fo) {
+    constexpr bool FORCED = is_forced<FO...>;
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -533,6 +630,8 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
     }
     const int root_ply = uni(bp.ctl->game_ply);
     const int qbit = (o.quiet && uni((int)o.quiet[b])) ? ST_QUIET : 0;
+    int fbit = 0;
+    if constexpr (FORCED) fbit = uni((int)forced_opts(fo...).boards[b]) ? ST_FORCED : 0;
     SzPos X = load_pos(bp.ring + (root_ply & (SZ_RING - 1)));
     path[0] = 0;
     if (v.reuse && uni(bp.ctl->reuse_ready) && uni(bp.ctl->n_nodes) <= v.S && 2 * (long long)uni(bp.ctl->n_edges) <= v.e_cap && v.S > 0) {
@@ -554,7 +653,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
             bp.npos[0] = X;
             Ctl* c = bp.ctl;
             if (o.target) o.goal[b] = goal;
-            c->status = (status & ST_ACTIVE) | ST_SEARCHING | qbit | (goal == 0 ? ST_DONE : 0); c->sims_done = 0; c->pend_node = -1; c->pend_depth = 0; c->reuse_ready = 0;
+            c->status = (status & ST_ACTIVE) | ST_SEARCHING | qbit | fbit | (goal == 0 ? ST_DONE : 0); c->sims_done = 0; c->pend_node = -1; c->pend_depth = 0; c->reuse_ready = 0;
             if constexpr (VL) c->n_pend = 0;                    // no root evaluation in flight: every in-flight count of the kept tree is 0, k[0] included
             if (v.rec_colour) v.rec_colour[b] = (uint8_t)szm_turn(X.meta);
         }
@@ -571,7 +670,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
         bp.em[0] = m;
         bp.gpath[0] = 0;
     }
-    int st = (status & ST_ACTIVE) | ST_SEARCHING | qbit;
+    int st = (status & ST_ACTIVE) | ST_SEARCHING | qbit | fbit;
     const int budget = o.target ? uni(o.target[b]) : board_budget(v, b);     // a fresh root: the visit target is a budget
     if (o.target && lane == 0) o.goal[b] = budget;
     if (szm_term(X.meta) || budget <= 0) {
@@ -620,8 +719,11 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // VL && SOLVE (sz_set_search_options): both at once; a proven stop puts nothing in flight and the gather goes on, a pending leaf is unknown.
 // One body for the four: selection is wave_select_child<VL, SOLVE>, a pending leaf's path / mask / depth / network row come from
 // leaf_ptrs<VL>; only the in-flight counts, n_pend, the collision break and "gather on" against "one leaf, stop" sit under if constexpr (VL).
-template <bool VL, bool SOLVE>
-__global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb) {
+// FO = ForcedOpts (sz_set_forced_playouts): on a board with ST_FORCED the selection at depth 0 is wave_select_root_forced; below the root
+// nothing changes.
+template <bool VL, bool SOLVE, typename... FO>
+__global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb, FO... fo) {
+    constexpr bool FORCED = is_forced<FO...>;
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -636,6 +738,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     if ((status & ST_PENDING) && !policy) return;             // descent-only launch (sz_search_begin with reuse): boards that already wait for the network sit it out
     unsigned long long n_expand = 0, n_term = 0, sum_depth = 0, sum_k = 0;
     unsigned long long n_stop = 0, n_proved = 0;                // solver: simulations ended on a proven non-terminal node, nodes proven by the update
+    unsigned long long n_forced = 0;                            // forced playouts: root selections decided by a forced child
     int err = 0;
     STEP_STAMP(0);
 
@@ -756,7 +859,16 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         int proven = PR_UNKNOWN;                                        // solver: result of the first proven node on the way, the root included
         if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
         while (mn > 0 && !proven) {                                     // Node.select
-            const int bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
+            int bi;
+            if constexpr (FORCED) {
+                bool forced = false;
+                if (d == 0 && (status & ST_FORCED))
+                    bi = wave_select_root_forced<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, forced_opts(fo...).k, &forced);
+                else
+                    bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
+                n_forced += forced ? 1 : 0;
+            } else
+            bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
             cur = m.first + bi;
             d++;
             if (d >= v.p_cap) { err = SZ_ERR_CAPACITY; break; }
@@ -840,6 +952,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if (err && !c->err) c->err = err;
         if constexpr (VL) c->n_pend = n_pend;
         if constexpr (SOLVE) { v.sstat[(size_t)b * 2] += n_stop; v.sstat[(size_t)b * 2 + 1] += n_proved; }
+        if constexpr (FORCED) forced_opts(fo...).stat[(size_t)b * 2] += n_forced;
     }
 }
 
@@ -895,8 +1008,11 @@ __global__ __launch_bounds__(64) void k_root_proven(View v, int8_t* root, int8_t
 // kernel: sample + play (sim.py:63-76) and game-over test (sim.py:46, 86-97)
 // ------------------------------------------------------------------------------------------------
 // SOLVE (sz_set_solver): on a root proven WIN the move played is the first child proven LOSS, whatever the uniform
-template <bool SOLVE>
-__global__ __launch_bounds__(64) void k_play(View v, const double* uniforms) {
+// FO = ForcedOpts (sz_set_forced_playouts): on a board with ST_FORCED the record and the move choice use the pruned counts of wave_prune; the
+// tree, and with it the subtree kept below, keeps the counted visits
+template <bool SOLVE, typename... FO>
+__global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO... fo) {
+    constexpr bool FORCED = is_forced<FO...>;
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     int* vis_lds = path + 8;
@@ -920,6 +1036,15 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms) {
     if (n == 0 || total == 0) {                                          // ZeroDivisionError in the reference (mcts.py:118-120)
         if (lane == 0) { bp.ctl->status = status | ST_ERROR; if (!bp.ctl->err) bp.ctl->err = SZ_ERR_ZERO_VISITS; }
         return;
+    }
+    if constexpr (FORCED) {
+        if (status & ST_FORCED) {                                        // the zero-visit check above stays on the counted visits
+            const int cut = wave_prune(bp.es + first, n, uni(bp.es[0].N), v.c_puct, forced_opts(fo...).k, vis_lds, nullptr);
+            __syncthreads();
+            total -= cut;
+            if (v.rec_action) for (int c = lane; c < n; c += 64) v.rec_visits[(size_t)b * SZ_MAX_CHILDREN + c] = vis_lds[c];
+            if (lane == 0) forced_opts(fo...).stat[(size_t)b * 2 + 1] += (unsigned long long)cut;
+        }
     }
     // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; idx = searchsorted(cdf, u, 'right')   (sequential f64, like numpy)
     int chosen = 0;
@@ -1019,6 +1144,34 @@ __global__ __launch_bounds__(64) void k_debug_select(const int* offsets, const i
     if (lane_id() == 0) argmax_out[cs] = bi;
 }
 
+// test hook (sz_debug_forced): wave_select_root_forced and wave_prune, the functions k_search_step<.., ForcedOpts> and k_play<.., ForcedOpts> call, on
+// caller-supplied children, one wave per case.  proven == NULL: the instantiations without the solver
+__global__ __launch_bounds__(64) void k_debug_forced(const int* offsets, const int* vc, const int* inflight, const double* wsum, const float* prior,
+                                                     const int8_t* proven, const int* parent_visits, const float* c_puct, const float* fk, float lam,
+                                                     int* selected_out, int* forced_out, int* pruned_out, int* cstar_out) {
+    extern __shared__ u64 lds64[];
+    EdgeStat* ch = (EdgeStat*)lds64;
+    EdgeMeta* cm = (EdgeMeta*)(ch + SZ_MAX_CHILDREN);
+    int* kk = (int*)(cm + SZ_MAX_CHILDREN);
+    int* vis = kk + SZ_MAX_CHILDREN;
+    const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
+    if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) { selected_out[cs] = -1; forced_out[cs] = 0; cstar_out[cs] = -1; } return; }
+    for (int c = lane; c < n; c += 64) {
+        EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s;
+        EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = 0; m.term = 0; m.tval = 0; m.pad = (unsigned short)(proven ? (proven[lo + c] & PR_MASK) : 0); cm[c] = m;
+        kk[c] = inflight[lo + c]; vis[c] = s.N;
+    }
+    __syncthreads();
+    const int pv = parent_visits[cs];
+    bool forced;
+    const int bi = proven ? wave_select_root_forced<true, true>(ch, cm, kk, n, pv, c_puct[cs], lam, fk[cs], &forced)
+                          : wave_select_root_forced<true, false>(ch, cm, kk, n, pv, c_puct[cs], lam, fk[cs], &forced);
+    if (lane == 0) { selected_out[cs] = bi; forced_out[cs] = forced ? 1 : 0; }
+    wave_prune(ch, n, pv, c_puct[cs], fk[cs], vis, cstar_out + cs);       // the case read as a finished search: the parent count is the root's N
+    __syncthreads();
+    for (int c = lane; c < n; c += 64) pruned_out[lo + c] = vis[c];
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
@@ -1040,7 +1193,9 @@ struct sz_engine {
     std::vector<void*> vb_allocs;
     int solver;                     // sz_set_solver: the SOLVE instantiations of begin / step / play run
     unsigned long long* d_sstat;    // its counters [n_boards][2], allocated by the first enabling call
-};
+    float forced_k;                 // sz_set_forced_playouts: the constant the next sz_search_begin takes up (0 = off)
+    ForcedOpts fo;                  // ... and what the searches begun since run with: fo.k > 0 selects the FORCED instantiations.  fo.boards
+};                                  //     [n_boards] and fo.stat [n_boards][2] are allocated by the first enabling call
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
 
@@ -1062,11 +1217,13 @@ template <typename T> static int dalloc(sz_engine* e, T** p, size_t count) {
     return SZ_OK;
 }
 
-// the one place that maps the options in force to a kernel instantiation: f(VL, SOLVE) is called with two std::bool_constants,
-// VL = leaf batching on (vb.L > 1), SOLVE = the solver on.  Instantiations without batching take an empty Batch.
+// the one place that maps the options in force to a kernel instantiation: f(VL, SOLVE, FORCED) is called with three std::bool_constants,
+// VL = leaf batching on (vb.L > 1), SOLVE = the solver on, FORCED = forced playouts on in the searches begun last (fo.k > 0).
+// Instantiations without batching take an empty Batch.
 template <typename F> static void with_search_options(const sz_engine* e, F&& f) {
-    if (e->vb.L > 1) { if (e->solver) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
-    else             { if (e->solver) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
+    auto g = [&](auto vl, auto solve) { if (e->fo.k > 0.0f) f(vl, solve, std::true_type{}); else f(vl, solve, std::false_type{}); };
+    if (e->vb.L > 1) { if (e->solver) g(std::true_type{}, std::true_type{}); else g(std::true_type{}, std::false_type{}); }
+    else             { if (e->solver) g(std::false_type{}, std::true_type{}); else g(std::false_type{}, std::false_type{}); }
 }
 
 extern "C" {
@@ -1358,18 +1515,25 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
 
 // the k_search_step instantiation of the options in force; policy == NULL: the descent-only launch of sz_search_begin
 static void launch_step(sz_engine* e, const float* policy, const float* value, void* planes, hipStream_t s) {
-    with_search_options(e, [&](auto vl, auto solve) {
+    with_search_options(e, [&](auto vl, auto solve, auto forced) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
-        hipLaunchKernelGGL((k_search_step<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{});
+        if constexpr (decltype(forced)::value)
+            hipLaunchKernelGGL((k_search_step<VL, SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fo);
+        else
+            hipLaunchKernelGGL((k_search_step<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{});
     });
 }
 
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    with_search_options(e, [&](auto vl, auto solve) {
+    e->fo.k = e->forced_k;                                                  // sz_set_forced_playouts takes effect here
+    with_search_options(e, [&](auto vl, auto solve, auto forced) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
-        hipLaunchKernelGGL((k_search_begin<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo);
+        if constexpr (decltype(forced)::value)
+            hipLaunchKernelGGL((k_search_begin<VL, SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo, e->fo);
+        else
+            hipLaunchKernelGGL((k_search_begin<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo);
     });
     HIPCHK(hipGetLastError());
     if (e->v.reuse && planes_dev) {
@@ -1495,6 +1659,45 @@ int sz_solver_stats(sz_engine* e, uint64_t out[2], void* stream) {
     return SZ_OK;
 }
 
+int sz_set_forced_playouts(sz_engine* e, float k, const uint8_t* boards, void* stream) {
+    if (!e || !(k >= 0.0f) || !std::isfinite(k)) return SZ_ERR_INVALID;
+    if (k > 0.0f && !e->v.learning) return SZ_ERR_INVALID;                  // an exploration option of self-play, like root noise
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if (k > 0.0f) {
+        const size_t B = e->v.B;
+        if (!e->fo.stat) {                                                  // the first enabling call: the boards' bits and the counters
+            uint8_t* fb = nullptr; unsigned long long* st = nullptr;
+            if ((rc = dalloc(e, &fb, B)) || (rc = dalloc(e, &st, B * 2))) return rc;
+            HIPCHK(hipMemsetAsync(st, 0, B * 2 * sizeof(unsigned long long), s));
+            e->fo.boards = fb; e->fo.stat = st;
+        }
+        std::vector<uint8_t> h(B, 1);
+        if (boards) for (size_t b = 0; b < B; b++) h[b] = boards[b] ? 1 : 0;
+        HIPCHK(hipMemcpyAsync((void*)e->fo.boards, h.data(), B, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                                    // the staging array goes out of scope
+    }
+    e->forced_k = k;
+    return SZ_OK;
+}
+
+int sz_forced_stats(sz_engine* e, uint64_t out[2], void* stream) {
+    if (!e || !out) return SZ_ERR_INVALID;
+    out[0] = out[1] = 0;
+    if (!e->fo.stat) return SZ_OK;                                          // the option was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<unsigned long long> h((size_t)e->v.B * 2);
+    HIPCHK(hipMemcpyAsync(h.data(), e->fo.stat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < (size_t)e->v.B; b++) { out[0] += h[2 * b]; out[1] += h[2 * b + 1]; }
+    return SZ_OK;
+}
+
 int sz_pending_boards(sz_engine* e, int32_t* n_out, void* stream) {
     if (!e || !n_out) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
@@ -1538,8 +1741,11 @@ int sz_root_children(sz_engine* e, int32_t* action_dev, int32_t* visits_dev, int
 int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    with_search_options(e, [&](auto, auto solve) {
-        hipLaunchKernelGGL(k_play<decltype(solve)::value>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
+    with_search_options(e, [&](auto, auto solve, auto forced) {
+        if constexpr (decltype(forced)::value)
+            hipLaunchKernelGGL((k_play<decltype(solve)::value, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->fo);
+        else
+            hipLaunchKernelGGL(k_play<decltype(solve)::value>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
     });
     HIPCHK(hipGetLastError());
     return SZ_OK;
@@ -1660,6 +1866,18 @@ int sz_debug_select(const int32_t* offsets_dev, const int32_t* vc_dev, const dou
     if (!offsets_dev || !vc_dev || !value_sum_dev || !prior_dev || !parent_visits_dev || !c_dev || !ucb_out_dev || !argmax_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
     hipLaunchKernelGGL(k_debug_select, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * sizeof(EdgeStat), (hipStream_t)stream, offsets_dev, vc_dev, value_sum_dev,
                        prior_dev, parent_visits_dev, c_dev, ucb_out_dev, argmax_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_forced(const int32_t* offsets_dev, const int32_t* vc_dev, const int32_t* inflight_dev, const double* value_sum_dev, const float* prior_dev,
+                    const int8_t* proven_dev, const int32_t* parent_visits_dev, const float* c_dev, const float* forced_k_dev, float virtual_loss,
+                    int32_t* selected_out_dev, int32_t* forced_out_dev, int32_t* pruned_out_dev, int32_t* cstar_out_dev, int32_t n_cases, void* stream) {
+    if (!offsets_dev || !vc_dev || !inflight_dev || !value_sum_dev || !prior_dev || !parent_visits_dev || !c_dev || !forced_k_dev || !selected_out_dev ||
+        !forced_out_dev || !pruned_out_dev || !cstar_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_forced, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(EdgeMeta) + 2 * sizeof(int)), (hipStream_t)stream,
+                       offsets_dev, vc_dev, inflight_dev, value_sum_dev, prior_dev, proven_dev, parent_visits_dev, c_dev, forced_k_dev, virtual_loss,
+                       selected_out_dev, forced_out_dev, pruned_out_dev, cstar_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

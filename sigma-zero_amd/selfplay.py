@@ -127,6 +127,21 @@ def visit_target_options_of(args):
     return bool(vt), bool(quiet)
 
 
+def forced_playout_options_of(args):
+    """The forced-playout constant of args, checked: k, or None when the option is off.  NON-REFERENCE, default off.
+
+    args["forced_playouts"] = k > 0 (KataGo uses 2) switches on forced playouts and policy-target pruning (sz_set_forced_playouts): at the root
+    every child with n >= 1 visits is selected while n < sqrt(k * P * (N_root - 1)), whatever PUCT says, so a noised move gets enough visits
+    to show what it is worth; play() then takes out of the recorded visit counts, and of the counts it samples from, the visits PUCT alone
+    would not have made.  The tree keeps the counted visits.  Needs learning = True.  Its effect on playing strength is unmeasured."""
+    k = args.get("forced_playouts")
+    if k is None:
+        return None
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, float, np.integer, np.floating)) or not (math.isfinite(k) and k > 0):      # NaN fails the comparison
+        raise ValueError("args['forced_playouts'] must be a finite number > 0, got %r" % (k,))
+    return float(k)
+
+
 def raise_if_overflowed(model):
     """ValueError when `model` keeps a range flag (FastPolicyNet / SplitPolicyNet: overflowed()) and a forward since the last look returned inf / NaN:
     with f16 operands a stored activation of 65520 or more is inf, the heads make NaN of it, and the search keeps a NaN prior without complaint.
@@ -166,6 +181,10 @@ class SelfPlayEngine:
         # NON-REFERENCE option (default off): reuse_subtree as a self-play configuration, see visit_target_options_of
         self.visit_targets, self.quiet_fast_plies = visit_target_options_of(self.args)
         self.targets = None           # host copy of the visit targets in force (set_visit_targets)
+        # NON-REFERENCE option (default off): forced playouts and policy-target pruning, see forced_playout_options_of
+        self.forced_k = forced_playout_options_of(self.args)
+        if self.forced_k is not None and not learning:
+            raise ValueError("args['forced_playouts'] needs learning=True: it is an exploration option of self-play, like root noise")
         self.quiet = None             # boards whose next searches get no root noise (set_quiet; visit_targets mode)
         self.last_goals = None        # visit_targets mode: search_goals() of the last search()
         self._compact_on = False      # the mapping chosen by the last compact() call
@@ -213,6 +232,8 @@ class SelfPlayEngine:
         self.next_gamma = None        # [B, SZ_MAX_MOVES] draws for the next begin() in place of torch's generator (play_games' root_gamma)
         if self.visit_targets:        # every board's target is num_searches until set_visit_targets says otherwise
             self.set_visit_targets(np.full(self.B, self.S, np.int32))
+        if self.forced_k is not None:  # every board is forced until set_forced_playouts says otherwise
+            self.set_forced_playouts(self.forced_k)
 
     def close(self):
         if self._e:
@@ -306,6 +327,22 @@ class SelfPlayEngine:
             raise ValueError("set_search_root_noise: %d quiet flags for %d boards" % (q.shape[0], self.B))
         N.check(N.lib().sz_set_search_root_noise(self._e, _ptr(self._gamma), None if q is None else q.ctypes.data_as(C.c_void_p), self._stream()),
                 "sz_set_search_root_noise")
+
+    def set_forced_playouts(self, k, boards=None):
+        """Forced playouts and policy-target pruning (sz_set_forced_playouts, a NON-REFERENCE option) from the next begin() on, until changed:
+        k > 0 for the boards with boards[b] != 0 (None: all of them), k = 0 switches the option off.  Between searches only; kept subtrees
+        are not dropped."""
+        m = None if boards is None else np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1)
+        if m is not None and m.shape[0] != self.B:
+            raise ValueError("set_forced_playouts: %d flags for %d boards" % (m.shape[0], self.B))
+        N.check(N.lib().sz_set_forced_playouts(self._e, float(k), None if m is None else m.ctypes.data_as(C.c_void_p), self._stream()), "sz_set_forced_playouts")
+        self.forced_k = float(k) if k else None
+
+    def forced_stats(self):
+        """(root selections decided by a forced child, visits pruning took out of the records), all boards, cumulative (sz_forced_stats)"""
+        out = (C.c_uint64 * 2)()
+        N.check(N.lib().sz_forced_stats(self._e, out, self._stream()), "sz_forced_stats")
+        return int(out[0]), int(out[1])
 
     def set_quiet(self, quiet):
         """visit_targets mode with root_dirichlet_alpha: the boards whose searches get no root noise from the next begin() on (None: none)"""

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -89,7 +89,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     max_plies: a game still running after that many plies is cut (result None, rewards 0); one number or one per game.
     stats: optional dict, receives 'sims', 'nn_rows', 'plies' (work done; sims = new simulations, nn_rows = network rows evaluated), 'full_plies' / 'fast_plies' (game
       plies searched with the full / the fast budget), 'searches_without_network' (lock-step searches that made no network call: args["visit_targets"]) and 'host_seconds' (the host's wall time per phase of the ply loop: enqueue_search returns before the GPU is done,
-      wait_search is the wait for it).
+      wait_search is the wait for it), 'forced_selections' / 'pruned_visits' (sz_forced_stats; 0 without args["forced_playouts"]).
 
     NON-REFERENCE option, off by default (the reference searches every ply with args['num_searches'] and records every ply, sim.py:46-76):
     args["playout_cap"] = {"fast": n_fast, "p_full": p}, playout-cap randomisation (KataGo).  Per ply every running game is searched with the
@@ -101,6 +101,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     args["reuse_subtree"].  The per-ply numbers np.where(sampled, num_searches, n_fast) are then root visit TARGETS: the visits of the kept
     subtree count, stats['sims'] are the new simulations actually made, and the root is noised at every ply.  With
     args["quiet_fast_plies"] = True fast plies are searched without root noise; the sampling temperature is not touched.  Strength effect unmeasured.
+    args["forced_playouts"] = k (NON-REFERENCE, selfplay.forced_playout_options_of): forced playouts at the root and policy-target pruning of the
+    record ('actions' are the pruned visit fractions; the move is sampled from them).  With args["playout_cap"] only full-search plies are forced
+    (fast plies are not recorded, and KataGo leaves them un-forced); without it every ply is.  Needs learning.  Strength effect unmeasured.
     full_search(game, ply) -> bool: the full / fast decision, like `uniforms`.  Default: a numpy Generator of its own, drawn per ply for every
       running game in game order — never the global numpy or `random` state, whose draw order the callers above depend on.
     root_gamma(game, ply) -> 218 floats: the Gamma(alpha, 1) draws of args["root_dirichlet_alpha"] for that game's root at that ply, like
@@ -108,6 +111,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     import random
     pcap = playout_cap_of(args)                             # validated before anything is created
     vt, quiet_fast = visit_target_options_of(args)
+    forced_k = forced_playout_options_of(args)
+    if forced_k is not None and not learning:
+        raise ValueError("args['forced_playouts'] needs learning=True")
     if full_search is not None and pcap is None:
         raise ValueError("full_search needs args['playout_cap']")
     if root_gamma is not None and args.get("root_dirichlet_alpha") is None:
@@ -136,7 +142,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     slot_game = np.full(B, -1, dtype=np.int64)            # game running on each board slot, -1 = none
     plies = np.zeros(n_games, dtype=np.int64)             # plies played so far per game
     next_game = 0
-    work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0, searches_without_network=0)
+    work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0, searches_without_network=0, forced_selections=0, pruned_visits=0)
 
     def refill(slots):
         """start the next waiting games on these slots (ChessTensor.__init__/start_board for each); the rest go dark"""
@@ -203,6 +209,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
                     eng.set_quiet(~sampled)
             else:
                 eng.set_budgets(np.where(sampled, S, pcap[0]))
+            if forced_k is not None:
+                eng.set_forced_playouts(forced_k, sampled)         # full-search plies only
         if root_gamma is not None:
             gam = np.zeros((B, 218), dtype=np.float32)
             for s_ in running:
@@ -246,6 +254,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     for g in range(n_games):
         reward = {"1-0": 1, "0-1": -1}.get(games[g]["result"], 0)
         games[g]["rewards"] = [reward if ply % 2 == 0 else -reward for ply in games[g]["sample_plies"]]   # sim.py:94-97: the sign alternates with the ply the sample was taken at
+    if forced_k is not None:
+        work["forced_selections"], work["pruned_visits"] = eng.forced_stats()
     eng.close()
     if stats is not None:
         stats.update(work)

@@ -508,6 +508,9 @@ def main(argv=None):
     ap.add_argument("--quiet-fast-plies", action="store_true",
                     help="NON-REFERENCE: fast plies are searched without root noise (needs --visit-targets, --playout-cap-fast and --root-dirichlet-alpha); the "
                          "sampling temperature is not touched; strength effect unmeasured")
+    ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
+                    help="NON-REFERENCE: forced playouts at the root, n < sqrt(K * P * (N_root - 1)), and policy-target pruning of the recorded visits "
+                         "(KataGo: K = 2; 0 = off); with --playout-cap-fast on full-search plies only (args['forced_playouts']); strength effect unmeasured")
     a = ap.parse_args(argv)
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     gpr = [int(x) for x in str(a.games_per_rank).split(",")]
@@ -551,6 +554,8 @@ def main(argv=None):
             args["combine_options"] = True
     if a.quiet_fast_plies:
         args["quiet_fast_plies"] = True
+    if a.forced_playouts:
+        args["forced_playouts"] = a.forced_playouts
     import random
     random.seed(1000 + rank)
     np.random.seed(1000 + rank)
@@ -581,6 +586,8 @@ def main(argv=None):
                                         "fast_plies": sp_stats.get("fast_plies"), "network_rows": sp_stats.get("nn_rows"), "simulations": sp_stats.get("sims"),
                                         "playout_cap": args.get("playout_cap"), "visit_targets": bool(args.get("visit_targets", False)),
                                         "quiet_fast_plies": bool(args.get("quiet_fast_plies", False)),
+                                        "forced_playouts": args.get("forced_playouts"), "forced_selections": sp_stats.get("forced_selections"),
+                                        "pruned_visits": sp_stats.get("pruned_visits"),
                                         "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"

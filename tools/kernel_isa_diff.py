@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Did a source change alter the network kernels' code?  usage: kernel_isa_diff.py TREE_A TREE_B [KEEP_DIR]
+"""Did a source change alter the kernels' code?  usage: kernel_isa_diff.py [--sources=a.hip,b.hip] TREE_A TREE_B [KEEP_DIR]
 
-Compiles csrc/sz_nn.hip and csrc/sz_nn_split.hip of two checkouts for the device only (each tree's own build.py FLAGS plus
+Compiles csrc/sz_nn.hip and csrc/sz_nn_split.hip (the network kernels; --sources=sz_engine.hip: the tree kernels) of two checkouts for the device only (each tree's own build.py FLAGS plus
 --cuda-device-only -S; no GPU needed) and prints one line per kernel: SAME when the instruction text, the .amdhsa_kernel descriptor and the register figures are
 identical after stripping comments and numbering the .L labels by first appearance, else DIFF, with both trees' register, scratch and LDS
 figures (ONLY-A / ONLY-B: the kernel exists in one tree).  Kernels are matched by demangled name without the parameter list.
@@ -60,13 +60,15 @@ def kernels(lines, filt):
 
 
 def main():
-    tree_a, tree_b = sys.argv[1], sys.argv[2]
-    keep = sys.argv[3] if len(sys.argv) > 3 else None
+    argv = [a for a in sys.argv[1:] if not a.startswith("--sources=")]
+    sources = [a[len("--sources="):].split(",") for a in sys.argv[1:] if a.startswith("--sources=")]
+    tree_a, tree_b = argv[0], argv[1]
+    keep = argv[2] if len(argv) > 2 else None
     work = keep or tempfile.mkdtemp()
     os.makedirs(work, exist_ok=True)
     filt = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")          # without one, kernels are matched by mangled name
     n_diff = 0
-    for src in SOURCES:
+    for src in (sources[-1] if sources else SOURCES):
         ka, kb = (kernels(compile_s(t, src, os.path.join(work, "%s_%s.s" % (tag, src))), filt) for tag, t in (("a", tree_a), ("b", tree_b)))
         for k in sorted(set(ka) | set(kb)):
             if k not in ka or k not in kb:
