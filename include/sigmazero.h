@@ -375,6 +375,63 @@ int sz_debug_forced(const int32_t* offsets_dev, const int32_t* vc_dev, const int
                     const int8_t* proven_dev, const int32_t* parent_visits_dev, const float* c_dev, const float* forced_k_dev, float virtual_loss,
                     int32_t* selected_out_dev, int32_t* forced_out_dev, int32_t* pruned_out_dev, int32_t* cstar_out_dev, int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, off by default: RESIGNATION and ADJUDICATED GAME ENDINGS (AlphaZero, lc0, KataGo).  A self-play cycle lasts as long
+ * as its longest game, and a game the rules have not ended yet is cut by the host without a result.  With the option on, sz_play ends a
+ * board's game INSTEAD of playing a move when the finished search says the game is decided: the mover's most visited move has looked lost for
+ * resign_patience of the mover's searches in a row, both sides have looked level for draw_patience searches in a row, or (proven, with the
+ * solver on) the root is proven.  Boards flagged in `holdout` play on and only remember the first ply a rule would have ended them at, so the
+ * thresholds can be checked against games that were played out.  Never switched on, every kernel that runs today runs unchanged: the option
+ * is an instantiation of k_play of its own (k_play<SOLVE, [ForcedOpts,] EndOpts>); k_search_begin and k_search_step have none.
+ * The rule, per board that passes sz_play's early return (searching, done, no error, game not over) and its zero-visit check, both first and
+ * both on the counted visits.  All arithmetic is f64, every operator one IEEE rounding (-ffp-contract=off):
+ *   inputs   colour = the side to move at the root (1 white, 0 black, sz_fetch_ply's colour); c* = the first maximum of the counted N_c over
+ *            the root's children in action order (the tree's visits, before any policy-target pruning); m = -(W_c* / (double)N_c*), the
+ *            mover's expected outcome of its most visited move (a child's W is stored from the child's side to move).
+ *   state    per board: rs[2] (resign streak per colour), ds (draw streak, shared), would_ply (-1 = none), would_kind, would_colour.  Streaks
+ *            saturate at 65535.  The array is allocated by the first call with opt != NULL; it is reset for exactly the boards sz_new_games
+ *            starts and for the board sz_upload_game fills, never by sz_set_active or by this setter.  While the option is off nothing updates it.
+ *   1 proven    if opt.proven != 0, the solver is on and the root's proven code R is not UNKNOWN, the game ends with kind SZ_END_PROVEN: WIN =
+ *            the mover wins, LOSS = the mover loses, DRAW = a draw.  Holdout boards too (a proof is not a guess).  Streaks are not touched.
+ *   2 streaks   if m <= (double)resign_value then rs[colour]++ else rs[colour] = 0; if fabs(m) <= (double)draw_value then ds++ else ds = 0.  A
+ *            NaN m fails both comparisons: both streaks reset.
+ *   3 fire      fire_resign = resign_patience > 0 && rs[colour] >= resign_patience && root_ply >= resign_min_ply; fire_draw likewise with ds,
+ *            draw_patience, draw_min_ply.  Resign wins over draw.  Every sz_play of the board counts, whatever budget or visit target (a
+ *            goal-0 ply on kept visits included) its search had.
+ *   4 holdout   on a board with holdout[b] != 0 a firing rule ends nothing: if would_ply < 0 it records would_ply = root_ply, would_kind,
+ *            would_colour (counted in sz_ending_stats out[3]); the ply is played exactly as without the option; streaks go on counting.
+ *   5 ending    on any other board the game ends instead of a move: no move is played, the ring, the position and game_ply are unchanged, no
+ *            subtree is kept, the board is game-over with result +1 / -1 (white / black wins; a resigning mover loses) or 0.  The ply's
+ *            record is written as always (planes, actions, visits: pruned if the board is forced) with chosen = -1, game_over = 1 and the
+ *            result.  The board's uniform is not read.
+ * The solver's WIN-root move rule and policy-target pruning are untouched where no ending fires.  Composes with sz_set_search_options (any L,
+ * solver on or off), sz_set_forced_playouts, reuse_subtree, budgets, visit targets, sz_compact and sz_compact_searching.
+ * Held bit for bit to the host restatement tests/endingref.py by tests/test_gpu_endings.py.  Its effect on playing strength is unmeasured. */
+enum { SZ_END_NONE = 0, SZ_END_RESIGN = 1, SZ_END_DRAW = 2, SZ_END_PROVEN = 3 };
+typedef struct sz_ending_options {
+    float resign_value;  int32_t resign_patience, resign_min_ply;   /* value in [-1, 1]; patience 0 = rule off, else 1..65535; min_ply >= 0 */
+    float draw_value;    int32_t draw_patience,   draw_min_ply;     /* value in [0, 1] */
+    int32_t proven;                                                  /* ignored while the solver is off */
+} sz_ending_options;
+/* opt == NULL switches the option off (holdout is ignored; state and counters stay); otherwise on, for every board, with `holdout` a HOST array
+ * [n_boards] (NULL = no holdout board).  SZ_ERR_INVALID: a value outside its range or not finite, a patience outside 0..65535, a negative
+ * min_ply.  SZ_ERR_STATE during a search (the rule of sz_set_search_budgets; nothing is changed then).  Takes effect at the next sz_play and
+ * holds until changed.  Never drops kept subtrees and never resets streaks or marks: a host calls it at every refill with a new `holdout`. */
+int sz_set_endings(sz_engine* e, const sz_ending_options* opt, const uint8_t* holdout, void* stream);
+/* HOST arrays [n_boards], any may be NULL; synchronises.  kind[b] (SZ_END_*) and mover_value[b] (m) describe the last sz_play: 0 and NaN for a
+ * board that did not play in it, and for every board while the option is off; kind is 0 for a game the rules ended or that goes on.
+ * would_ply / would_kind / would_colour are the board's sticky holdout mark for its current game (-1 / 0 / 0 = none). */
+int sz_fetch_endings(sz_engine* e, uint8_t* kind, double* mover_value, int32_t* would_ply, uint8_t* would_kind, uint8_t* would_colour, void* stream);
+/* ending counters, all boards, cumulative since the option was first switched on (synchronises): out[0] resignations, out[1] adjudicated
+ * draws, out[2] proven endings, out[3] holdout marks.  sz_stats is unchanged. */
+int sz_ending_stats(sz_engine* e, uint64_t out[4], void* stream);
+/* test: the DEVICE code of the ending decision (the function the option's k_play calls) on caller-supplied cases, one wavefront per case, in
+ * the manner of sz_debug_forced.  Case c owns children offsets[c]..offsets[c+1] (1..SZ_MAX_MOVES each) of vc (N) and value_sum (f64);
+ * root_proven[c] (codes of sz_root_proven), colour[c], ply[c], holdout[c], state_in[c*6..] = rs[0], rs[1], ds, would_ply, would_kind,
+ * would_colour, opts[c].  Writes kind_out[c], m_out[c] and state_out[c*6..].  All device pointers. */
+int sz_debug_endings(const int32_t* offsets_dev, const int32_t* vc_dev, const double* value_sum_dev, const int8_t* root_proven_dev, const uint8_t* colour_dev,
+                     const int32_t* ply_dev, const uint8_t* holdout_dev, const int32_t* state_in_dev, const sz_ending_options* opts_dev,
+                     int32_t* kind_out_dev, double* m_out_dev, int32_t* state_out_dev, int32_t n_cases, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

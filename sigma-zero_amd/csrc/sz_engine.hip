@@ -174,8 +174,26 @@ struct ForcedOpts {
 };
 // The FORCED instantiation of a kernel is the one that takes a ForcedOpts as one more, last argument: k_search_step<VL, SOLVE, ForcedOpts>
 // against k_search_step<VL, SOLVE>, whose argument list, and with it every line of its code, is what it was before the option existed
-template <typename... FO> constexpr bool is_forced = sizeof...(FO) > 0;
+template <typename... FO> constexpr bool is_forced = (std::is_same_v<FO, ForcedOpts> || ...);
+
+// NON-REFERENCE option (sz_set_endings): the per-board state of the ending rules, reset when a game starts on the board ...
+struct EndState { int rs[2]; int ds; int would_ply; int would_kind; int would_colour; };     // resign streak per colour, draw streak, the holdout mark (would_ply -1 = none)
+enum { END_STREAK_MAX = 65535 };                                                             // streaks saturate here: the largest patience
+// ... and what k_play's ENDING instantiations take on top of View, and of ForcedOpts when both options are on: k_play<SOLVE, EndOpts>,
+// k_play<SOLVE, ForcedOpts, EndOpts>.  k_search_begin and k_search_step have no ending variant: the option lives in sz_play alone.
+struct EndOpts {
+    sz_ending_options o;        // o.proven is already 0 when the solver is off
+    EndState* state;            // [B]
+    const uint8_t* holdout;     // [B] != 0: a firing rule marks the board and ends nothing
+    uint8_t* kind;              // [B] SZ_END_* of the last sz_play (0 for a board that did not play in it) ...
+    double* mval;               // [B] ... and the mover's value m it saw (NaN likewise)
+    unsigned long long* stat;   // [B][4] resignations, adjudicated draws, proven endings, holdout marks
+};
+template <typename... FO> constexpr bool is_ending = (std::is_same_v<FO, EndOpts> || ...);
 __device__ __forceinline__ const ForcedOpts& forced_opts(const ForcedOpts& fo) { return fo; }
+__device__ __forceinline__ const ForcedOpts& forced_opts(const ForcedOpts& fo, const EndOpts&) { return fo; }
+__device__ __forceinline__ const EndOpts& end_opts(const EndOpts& eo) { return eo; }
+__device__ __forceinline__ const EndOpts& end_opts(const ForcedOpts&, const EndOpts& eo) { return eo; }
 
 // forced playouts at a root (sz_set_forced_playouts): child c with n_c = N_c + k_c >= 1 visits is forced while n_c < sqrt((k * P_c) * T) in f64,
 // T = parentVC - 1.  Returns the forced child with the lowest index, -1 when none is forced.  Lanes = children as in wave_select_child; with
@@ -251,6 +269,45 @@ __device__ __forceinline__ int wave_prune(const EdgeStat* ch, int n, int rootN, 
     for (int off = 32; off >= 1; off >>= 1) cut += __shfl_xor(cut, off);
     if (cstar_out && lane == 0) *cstar_out = cs;
     return uni(cut);
+}
+
+// the ending rules of sz_set_endings on a finished search (sz_play): ch[0..n) the root's children with their counted visits (lanes = children),
+// code the root's proven code (PR_UNKNOWN without the solver), colour the side to move (1 white), ply the root's ply.  c* = the first maximum
+// of N_c, m = -(W_c* / N_c*) in f64.  Order: proven root (o.proven; streaks untouched, holdout ignored), then the streaks are advanced, then
+// resign before draw.  On a holdout board a firing rule records the board's first mark (*marked = true) and ends nothing.  Returns the kind
+// that ends the game (SZ_END_NONE: the ply is played); st is advanced in place, *m_out = m.  Every lane returns the same.
+__device__ __forceinline__ int wave_ending(const EdgeStat* ch, int n, int code, int colour, int ply, EndState& st, const sz_ending_options& o, bool holdout,
+                                           double* m_out, bool* marked) {
+    const int lane = lane_id();
+    int bn = -1, bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) { const int nc = ch[c].N; if (nc > bn) { bn = nc; bi = c; } }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
+        if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+    }
+    const EdgeStat top = ch[uni(bi)];
+    const double m = -(top.W / (double)top.N);
+    *m_out = m;
+    *marked = false;
+    if (o.proven && code != PR_UNKNOWN) return SZ_END_PROVEN;
+    const int col = colour ? 1 : 0;
+    if (m <= (double)o.resign_value) { if (st.rs[col] < END_STREAK_MAX) st.rs[col]++; } else st.rs[col] = 0;
+    if (fabs(m) <= (double)o.draw_value) { if (st.ds < END_STREAK_MAX) st.ds++; } else st.ds = 0;
+    const bool fire_resign = o.resign_patience > 0 && st.rs[col] >= o.resign_patience && ply >= o.resign_min_ply;
+    const bool fire_draw = o.draw_patience > 0 && st.ds >= o.draw_patience && ply >= o.draw_min_ply;
+    int kind = fire_resign ? SZ_END_RESIGN : (fire_draw ? SZ_END_DRAW : SZ_END_NONE);
+    if (kind != SZ_END_NONE && holdout) {
+        if (st.would_ply < 0) { st.would_ply = ply; st.would_kind = kind; st.would_colour = col; *marked = true; }
+        kind = SZ_END_NONE;
+    }
+    return kind;
+}
+// the result of a game ended by `kind`: +1 white wins, -1 black wins, 0 draw
+__device__ __forceinline__ int ending_result(int kind, int code, int colour) {
+    const int mover = colour ? 1 : -1;
+    if (kind == SZ_END_RESIGN) return -mover;
+    if (kind == SZ_END_PROVEN) return code == PR_WIN ? mover : (code == PR_LOSS ? -mover : 0);
+    return 0;
 }
 
 // solver update after a backup whose last node path[d] has just become proven: walk towards the root; the parent of a newly proven node is
@@ -600,6 +657,16 @@ __global__ void k_after_upload(View v, int b, int ply) {
     Ctl z = *c;                                           // cumulative counters kept, per-game fields reset
     z.status = ST_ACTIVE; z.n_nodes = z.n_edges = z.sims_done = 0; z.pend_node = z.pend_depth = z.err = 0; z.game_result = 0; z.game_ply = ply; z.reuse_ready = 0;
     *c = z;
+}
+
+// sz_set_endings' per-board state starts again with a game: the boards sz_new_games starts (board < 0; active == NULL: all), or the one board
+// sz_upload_game fills.  Launched only while the array exists.
+__global__ void k_reset_endings(EndState* st, const uint8_t* active, int B, int board) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (board >= 0 ? b != board : (active && !active[b])) return;
+    EndState z; z.rs[0] = z.rs[1] = z.ds = 0; z.would_ply = -1; z.would_kind = z.would_colour = 0;
+    st[b] = z;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1010,15 +1077,20 @@ __global__ __launch_bounds__(64) void k_root_proven(View v, int8_t* root, int8_t
 // SOLVE (sz_set_solver): on a root proven WIN the move played is the first child proven LOSS, whatever the uniform
 // FO = ForcedOpts (sz_set_forced_playouts): on a board with ST_FORCED the record and the move choice use the pruned counts of wave_prune; the
 // tree, and with it the subtree kept below, keeps the counted visits
+// FO ends in EndOpts (sz_set_endings): wave_ending decides on the counted visits whether the game ends here instead of a move
 template <bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO... fo) {
     constexpr bool FORCED = is_forced<FO...>;
+    constexpr bool ENDING = is_ending<FO...>;
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     int* vis_lds = path + 8;
     const int b = blockIdx.x, lane = lane_id();
     BoardPtrs bp = board_ptrs(v, b);
     int status = uni(bp.ctl->status);
+    if constexpr (ENDING) {                                              // a board that does not play in this sz_play: kind 0, m NaN
+        if (lane == 0) { end_opts(fo...).kind[b] = SZ_END_NONE; end_opts(fo...).mval[b] = __longlong_as_double(0x7ff8000000000000LL); }
+    }
     if (!(status & ST_SEARCHING) || !(status & ST_DONE) || (status & (ST_ERROR | ST_GAMEOVER))) return;
     EdgeMeta rm = bp.em[0];
     const int n = uni((int)rm.n), first = uni(rm.first);
@@ -1037,6 +1109,22 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
         if (lane == 0) { bp.ctl->status = status | ST_ERROR; if (!bp.ctl->err) bp.ctl->err = SZ_ERR_ZERO_VISITS; }
         return;
     }
+    int end_kind = SZ_END_NONE, end_result = 0;
+    if constexpr (ENDING) {                                              // on the counted visits, before any pruning
+        const EndOpts& eo = end_opts(fo...);
+        int code = PR_UNKNOWN;
+        if constexpr (SOLVE) code = rm.pad & PR_MASK;
+        const int colour = uni((int)szm_turn(bp.npos[0].meta));
+        EndState st = eo.state[b];
+        double m; bool marked;
+        end_kind = wave_ending(bp.es + first, n, code, colour, root_ply, st, eo.o, uni((int)eo.holdout[b]) != 0, &m, &marked);
+        end_result = ending_result(end_kind, code, colour);
+        if (lane == 0) {
+            eo.state[b] = st; eo.kind[b] = (uint8_t)end_kind; eo.mval[b] = m;
+            if (end_kind != SZ_END_NONE) eo.stat[(size_t)b * 4 + end_kind - 1] += 1;
+            if (marked) eo.stat[(size_t)b * 4 + 3] += 1;
+        }
+    }
     if constexpr (FORCED) {
         if (status & ST_FORCED) {                                        // the zero-visit check above stays on the counted visits
             const int cut = wave_prune(bp.es + first, n, uni(bp.es[0].N), v.c_puct, forced_opts(fo...).k, vis_lds, nullptr);
@@ -1044,6 +1132,17 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
             total -= cut;
             if (v.rec_action) for (int c = lane; c < n; c += 64) v.rec_visits[(size_t)b * SZ_MAX_CHILDREN + c] = vis_lds[c];
             if (lane == 0) forced_opts(fo...).stat[(size_t)b * 2 + 1] += (unsigned long long)cut;
+        }
+    }
+    if constexpr (ENDING) {
+        if (end_kind != SZ_END_NONE) {                                   // the game ends instead of a move: ring, game_ply and the root stay, no subtree is kept,
+            if (lane == 0) {                                             // the board's uniform is not read
+                Ctl* c = bp.ctl;
+                c->status = (status & ST_ACTIVE) | ST_GAMEOVER;
+                c->game_result = end_result;
+                if (v.rec_nchild) { v.rec_nchild[b] = n; v.rec_chosen[b] = -1; v.rec_over[b] = 1; v.rec_result[b] = (int8_t)end_result; v.rec_active[b] = 1; }
+            }
+            return;
         }
     }
     // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; idx = searchsorted(cdf, u, 'right')   (sequential f64, like numpy)
@@ -1172,6 +1271,27 @@ __global__ __launch_bounds__(64) void k_debug_forced(const int* offsets, const i
     for (int c = lane; c < n; c += 64) pruned_out[lo + c] = vis[c];
 }
 
+// test hook (sz_debug_endings): wave_ending, the function k_play<.., EndOpts> calls, on caller-supplied cases, one wave per case
+__global__ __launch_bounds__(64) void k_debug_endings(const int* offsets, const int* vc, const double* wsum, const int8_t* root_proven, const uint8_t* colour,
+                                                      const int* ply, const uint8_t* holdout, const int* state_in, const sz_ending_options* opts,
+                                                      int* kind_out, double* m_out, int* state_out) {
+    extern __shared__ u64 lds64[];
+    EdgeStat* ch = (EdgeStat*)lds64;
+    const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
+    if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) kind_out[cs] = -1; return; }
+    for (int c = lane; c < n; c += 64) { EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = 0.0f; ch[c] = s; }
+    __syncthreads();
+    const int* si = state_in + (size_t)cs * 6;
+    EndState st; st.rs[0] = si[0]; st.rs[1] = si[1]; st.ds = si[2]; st.would_ply = si[3]; st.would_kind = si[4]; st.would_colour = si[5];
+    double m; bool marked;
+    const int kind = wave_ending(ch, n, root_proven[cs] & PR_MASK, colour[cs], ply[cs], st, opts[cs], holdout[cs] != 0, &m, &marked);
+    if (lane == 0) {
+        int* so = state_out + (size_t)cs * 6;
+        kind_out[cs] = kind; m_out[cs] = m;
+        so[0] = st.rs[0]; so[1] = st.rs[1]; so[2] = st.ds; so[3] = st.would_ply; so[4] = st.would_kind; so[5] = st.would_colour;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
@@ -1195,7 +1315,10 @@ struct sz_engine {
     unsigned long long* d_sstat;    // its counters [n_boards][2], allocated by the first enabling call
     float forced_k;                 // sz_set_forced_playouts: the constant the next sz_search_begin takes up (0 = off)
     ForcedOpts fo;                  // ... and what the searches begun since run with: fo.k > 0 selects the FORCED instantiations.  fo.boards
-};                                  //     [n_boards] and fo.stat [n_boards][2] are allocated by the first enabling call
+                                    //     [n_boards] and fo.stat [n_boards][2] are allocated by the first enabling call
+    int end_on;                     // sz_set_endings: sz_play runs the ENDING instantiations of k_play
+    EndOpts eo;                     // ... with these; its arrays are allocated by the first enabling call (eo.state != NULL from then on)
+};
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
 
@@ -1325,6 +1448,8 @@ int sz_new_games(sz_engine* e, const int32_t* scharnagl, const uint8_t* active, 
     if (active) HIPCHK(hipMemcpyAsync(e->d_active, active, B, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));                    // host staging buffers go out of scope
     hipLaunchKernelGGL(k_new_games, dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, e->d_scharnagl, active ? e->d_active : nullptr);
+    if (e->eo.state)                                    // sz_set_endings: streaks and marks start again with the game
+        hipLaunchKernelGGL(k_reset_endings, dim3((e->v.B + 255) / 256), dim3(256), 0, s, e->eo.state, active ? e->d_active : nullptr, e->v.B, -1);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
@@ -1509,6 +1634,8 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
     HIPCHK(hipMemcpyAsync(e->v.ring + (size_t)board * SZ_RING, ring, SZ_RING * sizeof(SzPos), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     hipLaunchKernelGGL(k_after_upload, dim3(1), dim3(1), 0, s, e->v, board, ply);
+    if (e->eo.state)                                    // sz_set_endings: streaks and marks start again with the game
+        hipLaunchKernelGGL(k_reset_endings, dim3((e->v.B + 255) / 256), dim3(256), 0, s, e->eo.state, (const uint8_t*)nullptr, e->v.B, board);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
@@ -1698,6 +1825,80 @@ int sz_forced_stats(sz_engine* e, uint64_t out[2], void* stream) {
     return SZ_OK;
 }
 
+int sz_set_endings(sz_engine* e, const sz_ending_options* opt, const uint8_t* holdout, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (opt) {
+        if (!std::isfinite(opt->resign_value) || opt->resign_value < -1.0f || opt->resign_value > 1.0f) return SZ_ERR_INVALID;
+        if (!std::isfinite(opt->draw_value) || opt->draw_value < 0.0f || opt->draw_value > 1.0f) return SZ_ERR_INVALID;
+        if (opt->resign_patience < 0 || opt->resign_patience > END_STREAK_MAX || opt->draw_patience < 0 || opt->draw_patience > END_STREAK_MAX) return SZ_ERR_INVALID;
+        if (opt->resign_min_ply < 0 || opt->draw_min_ply < 0) return SZ_ERR_INVALID;
+    }
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if (!opt) { e->end_on = 0; return SZ_OK; }
+    const size_t B = e->v.B;
+    if (!e->eo.state) {                                                     // the first enabling call: state, flags, last-play readouts, counters
+        EndState* st = nullptr; uint8_t* ho = nullptr; uint8_t* kd = nullptr; double* mv = nullptr; unsigned long long* ct = nullptr;
+        if ((rc = dalloc(e, &st, B)) || (rc = dalloc(e, &ho, B)) || (rc = dalloc(e, &kd, B)) || (rc = dalloc(e, &mv, B)) || (rc = dalloc(e, &ct, B * 4))) return rc;
+        HIPCHK(hipMemsetAsync(ct, 0, B * 4 * sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(k_reset_endings, dim3((e->v.B + 255) / 256), dim3(256), 0, s, st, (const uint8_t*)nullptr, e->v.B, -1);
+        HIPCHK(hipGetLastError());
+        e->eo.holdout = ho; e->eo.kind = kd; e->eo.mval = mv; e->eo.stat = ct; e->eo.state = st;
+    }
+    if (!e->end_on) {                                                       // off -> on: no sz_play of the option to describe yet
+        HIPCHK(hipMemsetAsync(e->eo.kind, 0, B, s));
+        HIPCHK(hipMemsetAsync(e->eo.mval, 0xff, B * sizeof(double), s));    // all ones: a NaN
+    }
+    std::vector<uint8_t> h(B, 0);
+    if (holdout) for (size_t b = 0; b < B; b++) h[b] = holdout[b] ? 1 : 0;
+    HIPCHK(hipMemcpyAsync((void*)e->eo.holdout, h.data(), B, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));                                        // the staging array goes out of scope
+    e->eo.o = *opt;
+    e->end_on = 1;
+    return SZ_OK;
+}
+
+int sz_fetch_endings(sz_engine* e, uint8_t* kind, double* mover_value, int32_t* would_ply, uint8_t* would_kind, uint8_t* would_colour, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = e->v.B;
+    std::vector<EndState> st;
+    if (e->eo.state) {
+        st.resize(B);
+        HIPCHK(hipMemcpyAsync(st.data(), e->eo.state, B * sizeof(EndState), hipMemcpyDeviceToHost, s));
+    }
+    if (e->end_on) {
+        if (kind) HIPCHK(hipMemcpyAsync(kind, e->eo.kind, B, hipMemcpyDeviceToHost, s));
+        if (mover_value) HIPCHK(hipMemcpyAsync(mover_value, e->eo.mval, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < B; b++) {
+        if (!e->end_on) { if (kind) kind[b] = SZ_END_NONE; if (mover_value) mover_value[b] = std::nan(""); }
+        if (would_ply) would_ply[b] = st.empty() ? -1 : st[b].would_ply;
+        if (would_kind) would_kind[b] = (uint8_t)(st.empty() ? 0 : st[b].would_kind);
+        if (would_colour) would_colour[b] = (uint8_t)(st.empty() ? 0 : st[b].would_colour);
+    }
+    return SZ_OK;
+}
+
+int sz_ending_stats(sz_engine* e, uint64_t out[4], void* stream) {
+    if (!e || !out) return SZ_ERR_INVALID;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!e->eo.stat) return SZ_OK;                                          // the option was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<unsigned long long> h((size_t)e->v.B * 4);
+    HIPCHK(hipMemcpyAsync(h.data(), e->eo.stat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < (size_t)e->v.B; b++) for (int k = 0; k < 4; k++) out[k] += h[4 * b + k];
+    return SZ_OK;
+}
+
 int sz_pending_boards(sz_engine* e, int32_t* n_out, void* stream) {
     if (!e || !n_out) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
@@ -1742,10 +1943,18 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     with_search_options(e, [&](auto, auto solve, auto forced) {
-        if constexpr (decltype(forced)::value)
-            hipLaunchKernelGGL((k_play<decltype(solve)::value, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->fo);
+        constexpr bool SOLVE = decltype(solve)::value;
+        if (e->end_on) {                                                    // sz_set_endings: the ENDING instantiations
+            EndOpts eo = e->eo;
+            if (!SOLVE) eo.o.proven = 0;                                    // ignored while the solver is off
+            if constexpr (decltype(forced)::value)
+                hipLaunchKernelGGL((k_play<SOLVE, ForcedOpts, EndOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->fo, eo);
+            else
+                hipLaunchKernelGGL((k_play<SOLVE, EndOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, eo);
+        } else if constexpr (decltype(forced)::value)
+            hipLaunchKernelGGL((k_play<SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->fo);
         else
-            hipLaunchKernelGGL(k_play<decltype(solve)::value>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
+            hipLaunchKernelGGL(k_play<SOLVE>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
     });
     HIPCHK(hipGetLastError());
     return SZ_OK;
@@ -1878,6 +2087,18 @@ int sz_debug_forced(const int32_t* offsets_dev, const int32_t* vc_dev, const int
     hipLaunchKernelGGL(k_debug_forced, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(EdgeMeta) + 2 * sizeof(int)), (hipStream_t)stream,
                        offsets_dev, vc_dev, inflight_dev, value_sum_dev, prior_dev, proven_dev, parent_visits_dev, c_dev, forced_k_dev, virtual_loss,
                        selected_out_dev, forced_out_dev, pruned_out_dev, cstar_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_endings(const int32_t* offsets_dev, const int32_t* vc_dev, const double* value_sum_dev, const int8_t* root_proven_dev, const uint8_t* colour_dev,
+                     const int32_t* ply_dev, const uint8_t* holdout_dev, const int32_t* state_in_dev, const sz_ending_options* opts_dev,
+                     int32_t* kind_out_dev, double* m_out_dev, int32_t* state_out_dev, int32_t n_cases, void* stream) {
+    if (!offsets_dev || !vc_dev || !value_sum_dev || !root_proven_dev || !colour_dev || !ply_dev || !holdout_dev || !state_in_dev || !opts_dev ||
+        !kind_out_dev || !m_out_dev || !state_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_endings, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * sizeof(EdgeStat), (hipStream_t)stream,
+                       offsets_dev, vc_dev, value_sum_dev, root_proven_dev, colour_dev, ply_dev, holdout_dev, state_in_dev, opts_dev,
+                       kind_out_dev, m_out_dev, state_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

@@ -142,6 +142,51 @@ def forced_playout_options_of(args):
     return float(k)
 
 
+ENDING_KEYS = ("resign_value", "resign_patience", "resign_min_ply", "draw_value", "draw_patience", "draw_min_ply", "proven", "holdout")
+ENDING_KINDS = {N.SZ_END_RESIGN: "resign", N.SZ_END_DRAW: "draw_adjudicated", N.SZ_END_PROVEN: "proven"}
+
+
+def ending_options_of(args):
+    """The ending options of args, checked: a dict with every key of ENDING_KEYS, or None when the option is off.  NON-REFERENCE, default off.
+
+    args["endings"] = {"resign_value": v, "resign_patience": n, "resign_min_ply": p, "draw_value": d, "draw_patience": n, "draw_min_ply": p,
+    "proven": bool, "holdout": q} switches on resignation and adjudicated game endings (sz_set_endings): play() ends a game instead of a move
+    when the mover's most visited move had an expected outcome m <= v in n of the mover's searches in a row (from ply p on), when |m| <= d in n
+    searches in a row, or when the root is proven (needs args["solver"]).  Absent keys mean that rule is off (patience 0); a patience > 0 needs
+    its value.  holdout in [0, 1]: the probability with which play_games plays a game out and only marks where a rule would have ended it
+    (sim.ending_report counts how often the mark was wrong).  Its effect on playing strength is unmeasured."""
+    opt = args.get("endings")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(ENDING_KEYS):
+        raise ValueError("args['endings'] must be a dict with keys from %s, got %r" % (ENDING_KEYS, opt))
+    number = lambda x: not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating))
+    out = {}
+    for rule, lo in (("resign", -1.0), ("draw", 0.0)):
+        v, n, p = opt.get(rule + "_value"), opt.get(rule + "_patience", 0), opt.get(rule + "_min_ply", 0)
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 65535:
+            raise ValueError("args['endings']['%s_patience'] must be an integer in 0..65535, got %r" % (rule, n))
+        if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, np.integer)) or not 0 <= p <= 2 ** 31 - 1:
+            raise ValueError("args['endings']['%s_min_ply'] must be an integer >= 0, got %r" % (rule, p))
+        if v is None:
+            if n > 0:
+                raise ValueError("args['endings']['%s_patience'] = %d needs '%s_value'" % (rule, n, rule))
+            v = 0.0
+        if not number(v) or not (math.isfinite(v) and lo <= float(np.float32(v)) <= 1.0):       # NaN fails the comparison
+            raise ValueError("args['endings']['%s_value'] must be a number in [%g, 1], got %r" % (rule, lo, v))
+        out[rule + "_value"], out[rule + "_patience"], out[rule + "_min_ply"] = float(np.float32(v)), int(n), int(p)
+    proven = opt.get("proven", False)
+    if not isinstance(proven, (bool, np.bool_)):
+        raise ValueError("args['endings']['proven'] must be True or False, got %r" % (proven,))
+    if proven and not args.get("solver", False):
+        raise ValueError("args['endings']['proven'] needs args['solver']: only the solver proves a root")
+    h = opt.get("holdout", 0.0)
+    if not number(h) or not 0.0 <= h <= 1.0:                     # NaN fails both comparisons
+        raise ValueError("args['endings']['holdout'] must be a probability in [0, 1], got %r" % (h,))
+    out["proven"], out["holdout"] = bool(proven), float(h)
+    return out
+
+
 def raise_if_overflowed(model):
     """ValueError when `model` keeps a range flag (FastPolicyNet / SplitPolicyNet: overflowed()) and a forward since the last look returned inf / NaN:
     with f16 operands a stored activation of 65520 or more is inf, the heads make NaN of it, and the search keeps a NaN prior without complaint.
@@ -185,6 +230,8 @@ class SelfPlayEngine:
         self.forced_k = forced_playout_options_of(self.args)
         if self.forced_k is not None and not learning:
             raise ValueError("args['forced_playouts'] needs learning=True: it is an exploration option of self-play, like root noise")
+        # NON-REFERENCE option (default off): resignation and adjudicated game endings, see ending_options_of
+        self.endings = ending_options_of(self.args)
         self.quiet = None             # boards whose next searches get no root noise (set_quiet; visit_targets mode)
         self.last_goals = None        # visit_targets mode: search_goals() of the last search()
         self._compact_on = False      # the mapping chosen by the last compact() call
@@ -234,6 +281,8 @@ class SelfPlayEngine:
             self.set_visit_targets(np.full(self.B, self.S, np.int32))
         if self.forced_k is not None:  # every board is forced until set_forced_playouts says otherwise
             self.set_forced_playouts(self.forced_k)
+        if self.endings is not None:   # no holdout board until set_endings says otherwise
+            self.set_endings(self.endings)
 
     def close(self):
         if self._e:
@@ -343,6 +392,40 @@ class SelfPlayEngine:
         out = (C.c_uint64 * 2)()
         N.check(N.lib().sz_forced_stats(self._e, out, self._stream()), "sz_forced_stats")
         return int(out[0]), int(out[1])
+
+    def set_endings(self, opts, holdout=None):
+        """Resignation and adjudicated game endings (sz_set_endings, a NON-REFERENCE option) from the next play() on, until changed.  opts: a
+        dict with keys of ENDING_KEYS (absent: that rule off; 'holdout' is play_games' business and ignored here), or None = off.  holdout:
+        the boards [B] that play on and only mark where a rule would have ended them (None: none).  Between searches only; kept subtrees,
+        streaks and marks are not touched."""
+        h = None if holdout is None else np.ascontiguousarray(holdout, dtype=np.uint8).reshape(-1)
+        if h is not None and h.shape[0] != self.B:
+            raise ValueError("set_endings: %d flags for %d boards" % (h.shape[0], self.B))
+        o = None
+        if opts is not None:
+            o = N.sz_ending_options(float(opts.get("resign_value", 0.0)), int(opts.get("resign_patience", 0)), int(opts.get("resign_min_ply", 0)),
+                                    float(opts.get("draw_value", 0.0)), int(opts.get("draw_patience", 0)), int(opts.get("draw_min_ply", 0)),
+                                    int(bool(opts.get("proven", False))))
+        N.check(N.lib().sz_set_endings(self._e, None if o is None else C.byref(o), None if h is None else h.ctypes.data_as(C.c_void_p), self._stream()),
+                "sz_set_endings")
+        self.endings = None if opts is None else dict(opts)
+
+    def fetch_endings(self):
+        """sz_fetch_endings: dict of [B] arrays: kind (SZ_END_*) and mover_value (m) of the last play(), and the boards' sticky holdout marks
+        would_ply (-1: none), would_kind, would_colour"""
+        B = self.B
+        out = dict(kind=np.zeros(B, np.uint8), mover_value=np.zeros(B, np.float64), would_ply=np.zeros(B, np.int32),
+                   would_kind=np.zeros(B, np.uint8), would_colour=np.zeros(B, np.uint8))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        N.check(N.lib().sz_fetch_endings(self._e, p(out["kind"]), p(out["mover_value"]), p(out["would_ply"]), p(out["would_kind"]), p(out["would_colour"]),
+                                         self._stream()), "sz_fetch_endings")
+        return out
+
+    def ending_stats(self):
+        """(resignations, adjudicated draws, proven endings, holdout marks), all boards, cumulative (sz_ending_stats)"""
+        out = (C.c_uint64 * 4)()
+        N.check(N.lib().sz_ending_stats(self._e, out, self._stream()), "sz_ending_stats")
+        return tuple(int(x) for x in out)
 
     def set_quiet(self, quiet):
         """visit_targets mode with root_dirichlet_alpha: the boards whose searches get no root noise from the next begin() on (None: none)"""

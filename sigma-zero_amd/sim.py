@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, ENDING_KINDS
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -71,7 +71,7 @@ def playout_cap_of(args):
 
 
 def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, learning=True, planes_dtype=None, max_plies=100000,
-               verbose=False, n_boards=None, compact=True, stats=None, full_search=None, root_gamma=None):
+               verbose=False, n_boards=None, compact=True, stats=None, full_search=None, root_gamma=None, holdout=None):
     """Plays n_games games to the end and returns a list of per-game history dicts (sim.py:38-43 layout), game g at index g.
 
     The games run concurrently on `n_boards` board slots of one engine (default: one slot per game).  A slot whose game ends is
@@ -89,7 +89,10 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     max_plies: a game still running after that many plies is cut (result None, rewards 0); one number or one per game.
     stats: optional dict, receives 'sims', 'nn_rows', 'plies' (work done; sims = new simulations, nn_rows = network rows evaluated), 'full_plies' / 'fast_plies' (game
       plies searched with the full / the fast budget), 'searches_without_network' (lock-step searches that made no network call: args["visit_targets"]) and 'host_seconds' (the host's wall time per phase of the ply loop: enqueue_search returns before the GPU is done,
-      wait_search is the wait for it), 'forced_selections' / 'pruned_visits' (sz_forced_stats; 0 without args["forced_playouts"]).
+      wait_search is the wait for it), 'forced_selections' / 'pruned_visits' (sz_forced_stats; 0 without args["forced_playouts"]), 'resigned' /
+      'adjudicated_draws' / 'adjudicated_proven' / 'holdout_marks' (sz_ending_stats) and 'holdout_games' (0 without args["endings"]).
+    Every game dict has 'termination', one of "rules" | "resign" | "draw_adjudicated" | "proven" | "max_plies", 'holdout' (the game was a holdout
+      game) and 'would_end', None or {"kind", "ply", "colour"}: the first ply at which a rule would have ended a holdout game.
 
     NON-REFERENCE option, off by default (the reference searches every ply with args['num_searches'] and records every ply, sim.py:46-76):
     args["playout_cap"] = {"fast": n_fast, "p_full": p}, playout-cap randomisation (KataGo).  Per ply every running game is searched with the
@@ -104,6 +107,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     args["forced_playouts"] = k (NON-REFERENCE, selfplay.forced_playout_options_of): forced playouts at the root and policy-target pruning of the
     record ('actions' are the pruned visit fractions; the move is sampled from them).  With args["playout_cap"] only full-search plies are forced
     (fast plies are not recorded, and KataGo leaves them un-forced); without it every ply is.  Needs learning.  Strength effect unmeasured.
+    args["endings"] = {...} (NON-REFERENCE, selfplay.ending_options_of): resignation and adjudicated game endings (sz_set_endings).  A game a rule
+    ends gets its result without a move: the ending ply is a training sample like any other recorded ply (with args["playout_cap"] only if it
+    was a full-search ply), 'chosen_actions' gets no entry for it, and 'rewards' follow from 'result' as always.  A refill hands the engine the
+    holdout flags of the games it starts.  The extra per-ply host copy (sz_fetch_endings) happens in this mode only.  Strength effect unmeasured.
+    holdout(game) -> bool: whether a game is a holdout game, like `uniforms`.  Default: a numpy Generator of its own, one draw per game in game
+      order when the game starts, true with probability args["endings"]["holdout"].
     full_search(game, ply) -> bool: the full / fast decision, like `uniforms`.  Default: a numpy Generator of its own, drawn per ply for every
       running game in game order — never the global numpy or `random` state, whose draw order the callers above depend on.
     root_gamma(game, ply) -> 218 floats: the Gamma(alpha, 1) draws of args["root_dirichlet_alpha"] for that game's root at that ply, like
@@ -114,6 +123,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     forced_k = forced_playout_options_of(args)
     if forced_k is not None and not learning:
         raise ValueError("args['forced_playouts'] needs learning=True")
+    end_opts = ending_options_of(args)
+    if holdout is not None and end_opts is None:
+        raise ValueError("holdout needs args['endings']")
     if full_search is not None and pcap is None:
         raise ValueError("full_search needs args['playout_cap']")
     if root_gamma is not None and args.get("root_dirichlet_alpha") is None:
@@ -137,12 +149,15 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     B = max(1, min(int(n_games), int(n_boards) if n_boards else int(n_games)))
     S = int(args["num_searches"])
     eng = SelfPlayEngine(model, args, B, chess960=c960, learning=learning, planes_dtype=planes_dtype, device=dev)
-    games = [dict(states=[], actions=[], rewards=[], colours=[], result=None, packed_states=[], sample_plies=[], chosen_actions=[]) for _ in range(n_games)]   # packed_states: the (119,8) uint8 form (train_RL.py:42)
+    games = [dict(states=[], actions=[], rewards=[], colours=[], result=None, packed_states=[], sample_plies=[], chosen_actions=[], termination=None, holdout=False, would_end=None) for _ in range(n_games)]   # packed_states: the (119,8) uint8 form (train_RL.py:42)
     cap_rng = np.random.default_rng() if pcap is not None and full_search is None else None
+    holdout_rng = np.random.default_rng() if end_opts is not None and holdout is None else None
+    slot_holdout = np.zeros(B, dtype=np.uint8)            # the holdout flag of the game on each board slot
     slot_game = np.full(B, -1, dtype=np.int64)            # game running on each board slot, -1 = none
     plies = np.zeros(n_games, dtype=np.int64)             # plies played so far per game
     next_game = 0
-    work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0, searches_without_network=0, forced_selections=0, pruned_visits=0)
+    work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0, searches_without_network=0, forced_selections=0, pruned_visits=0,
+                resigned=0, adjudicated_draws=0, adjudicated_proven=0, holdout_games=0, holdout_marks=0)
 
     def refill(slots):
         """start the next waiting games on these slots (ChessTensor.__init__/start_board for each); the rest go dark"""
@@ -152,18 +167,26 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             if next_game < n_games:
                 slot_game[s_] = next_game
                 sch[s_], act[s_] = scharnagl[next_game], 1
+                if end_opts is not None:
+                    slot_holdout[s_] = bool(holdout(next_game)) if holdout is not None else bool(holdout_rng.random() < end_opts["holdout"])
+                    games[next_game]["holdout"] = bool(slot_holdout[s_])
+                    work["holdout_games"] += int(slot_holdout[s_])
                 next_game += 1
             else:
                 slot_game[s_] = -1
+                slot_holdout[s_] = 0
         if act.any():
             eng.new_games(sch, act)
+            if end_opts is not None:
+                eng.set_endings(end_opts, slot_holdout)    # the new games' holdout flags; streaks and marks of the games that go on stay
         eng.set_active((slot_game >= 0).astype(np.uint8))
 
     def absorb(rec, game_of_slot, sampled, ply_of_slot):
         """host-side bookkeeping of one ply's records (sim.py:71-73); runs while the GPU searches the next ply"""
         slots = np.nonzero((game_of_slot >= 0) & rec["active"].astype(bool))[0]
         for s_ in slots.tolist():                          # the move played, sample or not: chosen_actions has one action index per ply of the game
-            games[int(game_of_slot[s_])]["chosen_actions"].append(int(rec["chosen"][s_]))
+            if rec["chosen"][s_] >= 0:                     # -1: a rule ended the game instead of a move (args["endings"])
+                games[int(game_of_slot[s_])]["chosen_actions"].append(int(rec["chosen"][s_]))
         for s_ in slots[~sampled[slots]].tolist():         # playout cap: a fast-search ply leaves no sample, only the game's outcome
             if rec["game_over"][s_]:
                 games[int(game_of_slot[s_])]["result"] = {1: "1-0", -1: "0-1", 0: "1/2-1/2"}[int(rec["result"][s_])]
@@ -230,6 +253,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             u[s_] = uniforms(g, int(plies[g])) if uniforms is not None else np.random.random_sample()
         eng.play(u)
         rec = eng.fetch_ply()
+        ends = eng.fetch_endings() if end_opts is not None else None
         if eng.stats()["boards_error"]:
             eng.check_errors()
         t0 = lap("play_fetch", t0)
@@ -244,6 +268,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         work["full_plies"] += n_full; work["fast_plies"] += len(running) - n_full
         plies[slot_game[running]] += 1
         done = [int(s_) for s_ in running if (rec["game_over"][s_] and rec["active"][s_]) or plies[slot_game[s_]] >= cap[slot_game[s_]]]
+        for s_ in done:
+            g = games[int(slot_game[s_])]
+            over = bool(rec["game_over"][s_] and rec["active"][s_])
+            g["termination"] = "max_plies" if not over else ("rules" if ends is None else ENDING_KINDS.get(int(ends["kind"][s_]), "rules"))
+            if ends is not None and ends["would_ply"][s_] >= 0:
+                g["would_end"] = {"kind": ENDING_KINDS[int(ends["would_kind"][s_])], "ply": int(ends["would_ply"][s_]), "colour": int(ends["would_colour"][s_])}
         if done:
             refill(done)
         lap("refill", t0)
@@ -256,11 +286,36 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         games[g]["rewards"] = [reward if ply % 2 == 0 else -reward for ply in games[g]["sample_plies"]]   # sim.py:94-97: the sign alternates with the ply the sample was taken at
     if forced_k is not None:
         work["forced_selections"], work["pruned_visits"] = eng.forced_stats()
+    if end_opts is not None:
+        work["resigned"], work["adjudicated_draws"], work["adjudicated_proven"], work["holdout_marks"] = eng.ending_stats()
     eng.close()
     if stats is not None:
         stats.update(work)
         stats["host_seconds"] = host
     return games
+
+
+def ending_report(games):
+    """What args["endings"] did to the games of play_games: the number of games each way of ending took, and over the holdout games that got a
+    mark the false positives: a resign mark whose colour did not lose the game played out, a draw mark whose game ended decisively.  (A game
+    cut at max_plies has no result: it counts as not lost and as not decisive.)"""
+    r = dict(games=len(games), resigned=0, adjudicated_draws=0, adjudicated_proven=0, rules=0, max_plies=0, holdout_games=0, holdout_marks=0,
+             resign_marks=0, resign_false_positives=0, draw_marks=0, draw_false_positives=0)
+    key = {"resign": "resigned", "draw_adjudicated": "adjudicated_draws", "proven": "adjudicated_proven", "rules": "rules", "max_plies": "max_plies"}
+    for g in games:
+        r[key[g["termination"]]] += 1
+        r["holdout_games"] += bool(g.get("holdout"))
+        w = g.get("would_end")
+        if w is None:
+            continue
+        r["holdout_marks"] += 1
+        if w["kind"] == "resign":
+            r["resign_marks"] += 1
+            r["resign_false_positives"] += g["result"] != ("0-1" if w["colour"] else "1-0")
+        elif w["kind"] == "draw_adjudicated":
+            r["draw_marks"] += 1
+            r["draw_false_positives"] += g["result"] in ("1-0", "0-1")
+    return r
 
 
 def play_game(model, args, c960=False):

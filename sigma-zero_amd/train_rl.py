@@ -511,6 +511,18 @@ def main(argv=None):
     ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
                     help="NON-REFERENCE: forced playouts at the root, n < sqrt(K * P * (N_root - 1)), and policy-target pruning of the recorded visits "
                          "(KataGo: K = 2; 0 = off); with --playout-cap-fast on full-search plies only (args['forced_playouts']); strength effect unmeasured")
+    ap.add_argument("--resign-value", type=float, default=None, metavar="V",
+                    help="NON-REFERENCE: a game is resigned when the mover's most visited move had an expected outcome <= V (in [-1, 1]) in "
+                         "--resign-patience of the mover's searches in a row (args['endings'], sz_set_endings); strength effect unmeasured")
+    ap.add_argument("--resign-patience", type=int, default=0, help="searches in a row for --resign-value (0 = no resignation)")
+    ap.add_argument("--resign-min-ply", type=int, default=0, help="no resignation before this ply")
+    ap.add_argument("--draw-value", type=float, default=None, metavar="D",
+                    help="NON-REFERENCE: a game is adjudicated drawn when that outcome was within [-D, D] (D in [0, 1]) in --draw-patience searches in a row")
+    ap.add_argument("--draw-patience", type=int, default=0, help="searches in a row for --draw-value (0 = no draw adjudication)")
+    ap.add_argument("--draw-min-ply", type=int, default=0, help="no draw adjudication before this ply")
+    ap.add_argument("--adjudicate-proven", action="store_true", help="NON-REFERENCE: a game whose root the solver has proven ends with that result (needs --solver)")
+    ap.add_argument("--ending-holdout", type=float, default=0.0, metavar="Q",
+                    help="share of the games that are played out and only marked where a rule would have ended them; the cycle log counts how often the mark was wrong")
     a = ap.parse_args(argv)
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     gpr = [int(x) for x in str(a.games_per_rank).split(",")]
@@ -556,6 +568,14 @@ def main(argv=None):
         args["quiet_fast_plies"] = True
     if a.forced_playouts:
         args["forced_playouts"] = a.forced_playouts
+    if a.resign_patience or a.draw_patience or a.adjudicate_proven:
+        end = {"resign_patience": a.resign_patience, "resign_min_ply": a.resign_min_ply, "draw_patience": a.draw_patience, "draw_min_ply": a.draw_min_ply,
+               "proven": bool(a.adjudicate_proven), "holdout": a.ending_holdout}
+        if a.resign_value is not None:
+            end["resign_value"] = a.resign_value
+        if a.draw_value is not None:
+            end["draw_value"] = a.draw_value
+        args["endings"] = end
     import random
     random.seed(1000 + rank)
     np.random.seed(1000 + rank)
@@ -581,6 +601,7 @@ def main(argv=None):
             if a.log_dir:
                 write_step_log(os.path.join(a.log_dir, "RL_train.jsonl"), epoch, hist, sched)
                 import json
+                from .sim import ending_report
                 with open(os.path.join(a.log_dir, "RL_cycles.jsonl"), "a") as f:        # one record per cycle: what self-play cost and what it yielded (rank 0's share)
                     f.write(json.dumps({"epoch": epoch, "games": a.games_per_rank, "samples": n_samples, "full_plies": sp_stats.get("full_plies"),
                                         "fast_plies": sp_stats.get("fast_plies"), "network_rows": sp_stats.get("nn_rows"), "simulations": sp_stats.get("sims"),
@@ -588,6 +609,7 @@ def main(argv=None):
                                         "quiet_fast_plies": bool(args.get("quiet_fast_plies", False)),
                                         "forced_playouts": args.get("forced_playouts"), "forced_selections": sp_stats.get("forced_selections"),
                                         "pruned_visits": sp_stats.get("pruned_visits"),
+                                        "endings": args.get("endings"), "ending_report": ending_report(games) if args.get("endings") else None,
                                         "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"
