@@ -9,7 +9,11 @@
  * device memory; tensors handed in by pointer stay owned by the caller; all device work is enqueued
  * on the caller's stream (pass torch.cuda.current_stream().cuda_stream), which must belong to the
  * engine's device (sz_config.device); every call makes that device current for its duration and
- * restores the caller's current device; one engine per GPU per process; not thread-safe.
+ * restores the caller's current device; not thread-safe.  One engine per GPU per process is the usual
+ * arrangement (self-play fills the card with one), a usage note and not a constraint: the library keeps no
+ * process-global state, and several engines may live side by side on one device (arena.play_options_match
+ * holds two).  Give each an explicit edges_per_board then: the default sizes the first one to half of the
+ * free HBM.
  */
 #ifndef SIGMAZERO_H
 #define SIGMAZERO_H
@@ -136,6 +140,38 @@ int sz_root_children(sz_engine* e, int32_t* action_dev, int32_t* visits_dev, int
  * board.is_game_over() (sim.py:46).  A negative uniform selects the most visited child instead
  * (max(action_probs, key=...) of eval.py:92-94 / play.py:40-41: first maximum in action-index order). */
 int sz_play(sz_engine* e, const double* uniforms_dev, void* stream);
+
+/* Play GIVEN moves, one per board: an opponent engine's, a book's, a person's (the role of the reference's play.py, which pushes the
+ * human's move into the game: ChessTensor.move, chess_tensor.py:88-95).  actions_dev: device array [n_boards] int32; -1 leaves the board
+ * alone, any other value is an action index 0..SZ_ACTIONS-1 to play on that board.  One launch, one wavefront per board, no
+ * synchronisation.  SZ_ERR_INVALID: e or actions_dev NULL.  Per board, in this order:
+ *   actions[b] < 0     nothing is touched: the record's `active` flag and a kept subtree stay as they are;
+ *   game over, or a sticky error: nothing is touched;
+ *   inside an unfinished search (between sz_search_begin and the search's last step): the board is flagged SZ_ERR_STATE, sticky, the
+ *                      way sz_search_begin flags a board without a row.  Whether the board is active (sz_set_active) is NOT consulted and
+ *                      is preserved: a caller may park the boards an engine does not search as inactive and still move on them;
+ *   legality           the root position is the ring entry of the game's ply (what sz_search_begin takes).  The action must be a bit of the
+ *                      legal-move mask move generation makes for it; it is not looked up among the root's children, because expansion drops
+ *                      legal moves whose renormalised prior is exactly 0.  An illegal action, or one >= SZ_ACTIONS, flags the board
+ *                      SZ_ERR_INVALID, sticky (ValueError("Invalid move"), chess_tensor.py:91-92); nothing else on the board changes;
+ *   the move           is played as sz_play plays the one it chose: the new position goes to the ring slot of ply + 1, the game's ply
+ *                      advances, the game-over test runs and sets the game's result.  The 80-byte position record and the ring are
+ *                      byte-identical to what sz_play writes when it plays the same action.  The board's status keeps its active bit
+ *                      alone (plus game over): a finished search is consumed, as by sz_play;
+ *   the record         a given move is not a training sample: active[b] = 0.  chosen[b], game_over[b] and result[b] are written, so
+ *                      sz_fetch_ply reports the game's end; visits, actions, n_child, colour and planes are left as they are;
+ *   not touched        sz_play's uniforms, the ending streaks and marks of sz_set_endings, the counters of sz_forced_stats,
+ *                      sz_solver_stats, sz_ending_stats and sz_get_stats: a given move is not a search of the mover;
+ *   reuse_subtree      the board has a tree when a search has finished on it and was not yet consumed, or when an earlier sz_play /
+ *                      sz_play_moves kept a subtree that no search has continued yet.  If the root child with this action exists, was
+ *                      visited and has children, its subtree is kept with sz_play's own in-place compaction (solver labels and `complete`
+ *                      bits travel with their edges) and the next sz_search_begin continues on it, under the three fresh-start conditions
+ *                      of sz_config.reuse_subtree evaluated on what is kept now.  Otherwise nothing is kept and the next search starts
+ *                      fresh: no tree, no such child (a move expansion dropped), an unvisited child, a leaf, a game that has ended.  So
+ *                      sz_play followed by one sz_play_moves is a two-ply re-rooting: the next search continues on the grandchild's
+ *                      subtree, which holds the engine's thinking about the reply.
+ * Held to a host restatement by tests/test_gpu_play_moves.py (tests/playmovesref.py). */
+int sz_play_moves(sz_engine* e, const int32_t* actions_dev, void* stream);
 
 /* Copy this ply's training records to host arrays (synchronises; any pointer may be NULL):
  *  packed_planes [n_boards,119,8] uint8   root get_representation(), bit j of byte = column j

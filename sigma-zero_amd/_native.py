@@ -78,6 +78,7 @@ EXPORTS = {
     "sz_get_stats": (C.c_int, [C.c_void_p, C.POINTER(sz_stats), C.c_void_p]),
     "sz_root_children": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]),
     "sz_play": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sz_play_moves": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "sz_fetch_ply": (C.c_int, [C.c_void_p] + [C.c_void_p] * 9 + [C.c_void_p]),
     "sz_debug_pending": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]),
     "sz_debug_position": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

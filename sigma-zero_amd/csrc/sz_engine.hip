@@ -1072,6 +1072,56 @@ __global__ __launch_bounds__(64) void k_root_proven(View v, int8_t* root, int8_t
 }
 
 // ------------------------------------------------------------------------------------------------
+// NON-REFERENCE option (sz_config.reuse_subtree): re-root the board's tree at edge e_c, a child of the root, in place.  What k_play does
+// with the move it chose and k_play_moves with the move it was given.  reuse_ready is set when a subtree was kept and left as it is
+// otherwise (never visited, or a leaf: nothing to keep): it is 0 on entry (k_search_begin's, or k_play_moves' own write).
+// ------------------------------------------------------------------------------------------------
+__device__ void wave_keep_subtree(const View& v, const BoardPtrs& bp, int b, int e_c) {
+    const int lane = lane_id();
+    // Spans are bump-allocated in node-creation order and a node is created after its parent, so walking the nodes in id order visits the kept
+    // spans in ascending address order: every span moves DOWN (destination <= source), in place, no second buffer.  nmap[nid] = new index of the
+    // edge that owns node nid (-1 = not in the kept subtree); the chosen child becomes edge 0 / node 0.
+    const int n_nodes = uni(bp.ctl->n_nodes);
+    const EdgeMeta cm = bp.em[e_c];
+    const int nid_c = uni(cm.node), n_c = uni((int)cm.n);
+    if (nid_c < 0 || n_c == 0) return;                               // never visited, or a leaf: nothing to keep (reuse_ready stays 0)
+    int* nmap = v.nmap + (size_t)b * v.n_cap;
+    for (int i = lane; i < n_nodes; i += 64) nmap[i] = -1;
+    const EdgeStat cs = bp.es[e_c];
+    __threadfence_block();
+    if (lane == 0) { bp.es[0] = cs; bp.em[0] = cm; nmap[nid_c] = 0; }
+    __threadfence_block();
+    int cursor = 1, new_nid = 0;
+    for (int nid = nid_c; nid < n_nodes; nid++) {
+        const int e_new = uni(nmap[nid]);
+        if (e_new < 0) continue;
+        EdgeMeta m = bp.em[e_new];                                   // already moved; `first` still points at the old span, which no copy has reached yet
+        const int ofirst = uni(m.first), on = uni((int)m.n);
+        for (int base = 0; base < on; base += 64) {
+            const int k = base + lane;
+            EdgeStat s2; EdgeMeta m2;
+            if (k < on) { s2 = bp.es[ofirst + k]; m2 = bp.em[ofirst + k]; }
+            __threadfence_block();
+            if (k < on) {
+                bp.es[cursor + k] = s2; bp.em[cursor + k] = m2;
+                if (m2.node >= 0) nmap[m2.node] = cursor + k;
+            }
+            __threadfence_block();
+        }
+        if (lane == 0) {
+            SzPos pz = bp.npos[nid];
+            bp.npos[new_nid] = pz;
+            bp.em[e_new].first = on > 0 ? cursor : -1;
+            bp.em[e_new].node = new_nid;
+        }
+        __threadfence_block();
+        cursor += on;
+        new_nid++;
+    }
+    if (lane == 0) { Ctl* c = bp.ctl; c->n_nodes = new_nid; c->n_edges = cursor; c->reuse_ready = 1; }
+}
+
+// ------------------------------------------------------------------------------------------------
 // kernel: sample + play (sim.py:63-76) and game-over test (sim.py:46, 86-97)
 // ------------------------------------------------------------------------------------------------
 // SOLVE (sz_set_solver): on a root proven WIN the move played is the first child proven LOSS, whatever the uniform
@@ -1184,48 +1234,74 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     }
     if (!v.reuse || over) return;
     // ---- NON-REFERENCE option: keep the subtree of the move just played (the reference builds a fresh tree per ply, sim.py:53) ------------
-    // Spans are bump-allocated in node-creation order and a node is created after its parent, so walking the nodes in id order visits the kept
-    // spans in ascending address order: every span moves DOWN (destination <= source), in place, no second buffer.  nmap[nid] = new index of the
-    // edge that owns node nid (-1 = not in the kept subtree); the chosen child becomes edge 0 / node 0.
     __syncthreads();
-    const int n_nodes = uni(bp.ctl->n_nodes);
-    const EdgeMeta cm = bp.em[first + chosen];
-    const int nid_c = uni(cm.node), n_c = uni((int)cm.n);
-    if (nid_c < 0 || n_c == 0) return;                               // never visited, or a leaf: nothing to keep (reuse_ready stays 0)
-    int* nmap = v.nmap + (size_t)b * v.n_cap;
-    for (int i = lane; i < n_nodes; i += 64) nmap[i] = -1;
-    const EdgeStat cs = bp.es[first + chosen];
-    __threadfence_block();
-    if (lane == 0) { bp.es[0] = cs; bp.em[0] = cm; nmap[nid_c] = 0; }
-    __threadfence_block();
-    int cursor = 1, new_nid = 0;
-    for (int nid = nid_c; nid < n_nodes; nid++) {
-        const int e_new = uni(nmap[nid]);
-        if (e_new < 0) continue;
-        EdgeMeta m = bp.em[e_new];                                   // already moved; `first` still points at the old span, which no copy has reached yet
-        const int ofirst = uni(m.first), on = uni((int)m.n);
-        for (int base = 0; base < on; base += 64) {
-            const int k = base + lane;
-            EdgeStat s2; EdgeMeta m2;
-            if (k < on) { s2 = bp.es[ofirst + k]; m2 = bp.em[ofirst + k]; }
-            __threadfence_block();
-            if (k < on) {
-                bp.es[cursor + k] = s2; bp.em[cursor + k] = m2;
-                if (m2.node >= 0) nmap[m2.node] = cursor + k;
-            }
-            __threadfence_block();
-        }
-        if (lane == 0) {
-            SzPos pz = bp.npos[nid];
-            bp.npos[new_nid] = pz;
-            bp.em[e_new].first = on > 0 ? cursor : -1;
-            bp.em[e_new].node = new_nid;
-        }
-        __threadfence_block();
-        cursor += on;
-        new_nid++;
+    wave_keep_subtree(v, bp, b, first + chosen);
+}
+
+// ------------------------------------------------------------------------------------------------
+// kernel: play a GIVEN move (sz_play_moves): an opponent engine's, a book's, a person's.  One wave per board, no option state read.
+// ------------------------------------------------------------------------------------------------
+// The root position is the ring entry of the game's ply (as k_search_begin takes it; npos[0] is the root only right after a search).  Legality
+// is the action's bit in wave_movegen's mask, never a look-up among the root's children: expansion drops legal moves whose renormalised prior
+// is exactly 0.  The move itself is what k_play does after its choice; the record says the board played no search move (rec_active = 0) and
+// still reports the game's end.  With reuse_subtree the board's tree (a finished search's, or the one an earlier sz_play / sz_play_moves kept)
+// is re-rooted at the given move by wave_keep_subtree, so sz_play followed by sz_play_moves keeps the grandchild's subtree.
+__global__ __launch_bounds__(64) void k_play_moves(View v, const int* actions) {
+    extern __shared__ u64 lds64[];
+    u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
+    const int b = blockIdx.x, lane = lane_id();
+    const int action = uni(actions[b]);
+    if (action < 0) return;                                              // -1: the board is left alone, its record and kept subtree included
+    BoardPtrs bp = board_ptrs(v, b);
+    const int status = uni(bp.ctl->status);
+    if (status & (ST_ERROR | ST_GAMEOVER)) return;
+    if ((status & ST_SEARCHING) && !(status & ST_DONE)) {                // inside an unfinished search: refused loudly, like a board without a row
+        if (lane == 0) { bp.ctl->status = status | ST_ERROR; if (!bp.ctl->err) bp.ctl->err = SZ_ERR_STATE; }
+        return;
     }
-    if (lane == 0) { Ctl* c = bp.ctl; c->n_nodes = new_nid; c->n_edges = cursor; c->reuse_ready = 1; }
+    const int root_ply = uni(bp.ctl->game_ply);
+    const SzPos R = load_pos(bp.ring + (root_ply & (SZ_RING - 1)));
+    int legal = 0;
+    if (action < SZ_ACTIONS) {
+        int n_legal, ep_legal; u64 checkers;
+        wave_movegen(R, v.chess960, mask, n_legal, ep_legal, checkers);
+        __syncthreads();
+        legal = (int)((mask[action >> 6] >> (action & 63)) & 1);
+        __syncthreads();                                                 // wave_create_position fills the same mask words
+    }
+    if (!uni(legal)) {                                                   // ValueError("Invalid move"), chess_tensor.py:91-92
+        if (lane == 0) { bp.ctl->status = status | ST_ERROR; if (!bp.ctl->err) bp.ctl->err = SZ_ERR_INVALID; }
+        return;
+    }
+    // the new position at depth 0 of a tree rooted one ply on: every ancestor is a ring entry, the root's included, so no tree is read
+    path[0] = 0;
+    SzPos X = wave_create_position(bp, R, action, v.chess960, path, 0, root_ply + 1, mask);
+    const int over = szm_term(X.meta);
+    int result = 0;
+    if (over && szm_loss(X.meta)) result = szm_turn(X.meta) ? -1 : 1;      // side to move is mated
+    const bool tree = ((status & ST_SEARCHING) && (status & ST_DONE)) || uni(bp.ctl->reuse_ready) != 0;
+    if (lane == 0) {
+        bp.ring[(root_ply + 1) & (SZ_RING - 1)] = X;
+        Ctl* c = bp.ctl;
+        c->game_ply = root_ply + 1;
+        c->status = (status & ST_ACTIVE) | (over ? ST_GAMEOVER : 0);
+        c->game_result = result;
+        c->reuse_ready = 0;
+        if (v.rec_nchild) { v.rec_chosen[b] = action; v.rec_over[b] = (uint8_t)over; v.rec_result[b] = (int8_t)result; v.rec_active[b] = 0; }
+    }
+    if (!v.reuse || over || !tree) return;
+    __syncthreads();
+    const EdgeMeta rm = bp.em[0];
+    const int n = uni((int)rm.n), first = uni(rm.first);
+    u64 hit = 0;
+    int at = -1;
+    for (int base = 0; base < n && at < 0; base += 64) {                 // the root child with this action; none: a move expansion dropped
+        const int c = base + lane;
+        hit = __ballot(c < n && (int)bp.em[first + c].action == action);
+        if (hit) at = base + __builtin_ctzll(hit);
+    }
+    if (at < 0) return;
+    wave_keep_subtree(v, bp, b, first + at);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1956,6 +2032,14 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
         else
             hipLaunchKernelGGL(k_play<SOLVE>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
     });
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_play_moves(sz_engine* e, const int32_t* actions_dev, void* stream) {
+    if (!e || !actions_dev) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipLaunchKernelGGL(k_play_moves, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, actions_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

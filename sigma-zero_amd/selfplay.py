@@ -262,6 +262,7 @@ class SelfPlayEngine:
             if self.solver:
                 N.check(N.lib().sz_set_solver(self._e, 1, self._stream()), "sz_set_solver")
         self.uniforms = torch.zeros(self.B, dtype=torch.float64, device=dev)
+        self._moves = None            # play_moves' device buffer [B] int32, allocated on first use
         self.root_action = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
         self.root_visits = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.int32, device=dev)
         self.root_nchild = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -567,6 +568,19 @@ class SelfPlayEngine:
         """sim.py:68-76 for every board: sample with the given uniforms (one per board), play, test game over."""
         self.uniforms.copy_(torch.as_tensor(np.asarray(uniforms, dtype=np.float64)))
         N.check(N.lib().sz_play(self._e, _ptr(self.uniforms), self._stream()), "sz_play")
+
+    def play_moves(self, actions):
+        """Play given moves (sz_play_moves): actions is an integer array [n_boards], -1 = leave the board alone, else the action index to
+        play there: another engine's move, a book move, a person's.  Legality is checked on the device (an illegal move flags the board,
+        check_errors() raises); with reuse_subtree the board's tree is re-rooted at the move.  No training record; fetch_ply() reports
+        chosen, game_over and result."""
+        a = np.ascontiguousarray(actions, dtype=np.int32).reshape(-1)
+        if a.shape[0] != self.B:
+            raise ValueError("play_moves: %d actions for %d boards" % (a.shape[0], self.B))
+        if self._moves is None:
+            self._moves = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self._moves.copy_(torch.from_numpy(a))
+        N.check(N.lib().sz_play_moves(self._e, _ptr(self._moves), self._stream()), "sz_play_moves")
 
     def fetch_ply(self):
         B = self.B
