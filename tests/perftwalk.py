@@ -54,6 +54,20 @@ def positions_at_depth(root, depth, path=()):
         yield from positions_at_depth(ch, depth - 1, tuple(path) + (a,))
 
 
+def children_that_take_a_right(root):
+    """(action, child) for the children of `root` reached by a castling (the king moves onto its own rook) or by the capture of a rook
+    that carried a castling right, read off the host mirror's record"""
+    rec = dict(zip(RECORD_WORDS, root.board.bitboards()))
+    for a in root.legal_action_indices():
+        m = root.move_from_index(a)
+        f, t = 1 << m.from_square, 1 << m.to_square
+        same_colour = bool(rec["white"] & f) == bool(rec["white"] & t)
+        if (rec["kings"] & f and rec["rooks"] & t and same_colour) or (rec["castling"] & rec["rooks"] & t and not same_colour):
+            ch = root.copy()
+            ch.push_action(a)
+            yield a, ch
+
+
 def chunks(it, n_max, weight=lambda x: 1):
     buf, w = [], 0
     for x in it:
@@ -204,10 +218,12 @@ class WalkResult:
             setattr(self, k, getattr(self, k) + getattr(o, k))
 
 
-def device_walk(tag, roots, chess960, compare=True):
+def device_walk(tag, roots, chess960, compare=True, scharnagl=None):
     """Upload `roots` ((path, ChessTensor) pairs, ring included) to one engine and run the walk.  Counts come from the DEVICE's masks and
     tree only; with `compare` every root and every device-created child is held to the host mirror (legal mask, 119 planes, terminal or not,
-    loss or draw), exact equality.  Asserts per board that exactly its K children were seen, each once: pending at depth 1, or terminal."""
+    loss or draw), exact equality.  Asserts per board that exactly its K children were seen, each once: pending at depth 1, or terminal.
+    With `scharnagl` (one start-position number per root) nothing is uploaded: the device creates the roots itself (new_games), and
+    `roots` are the host mirror's games for the same numbers."""
     import torch
     from sigma_zero_amd.selfplay import SelfPlayEngine
     H = HostLevel(roots, children=compare)
@@ -215,8 +231,12 @@ def device_walk(tag, roots, chess960, compare=True):
     S = int(K.max()) + 1
     eng = SelfPlayEngine(None, {"C": WALK_C, "num_searches": S}, B, chess960=chess960, learning=False)
     try:
-        for b, g in enumerate(H.games):
-            eng.upload_game(b, g)
+        if scharnagl is not None:
+            assert len(scharnagl) == B
+            eng.new_games(scharnagl)
+        else:
+            for b, g in enumerate(H.games):
+                eng.upload_game(b, g)
         policy = torch.full((B, N.SZ_ACTIONS), float(UNIFORM_P), dtype=torch.float32, device=eng.device)
         value = torch.zeros(B, dtype=torch.float32, device=eng.device)
         res = WalkResult()
