@@ -411,6 +411,60 @@ int sz_debug_forced(const int32_t* offsets_dev, const int32_t* vc_dev, const int
                     const int8_t* proven_dev, const int32_t* parent_visits_dev, const float* c_dev, const float* forced_k_dev, float virtual_loss,
                     int32_t* selected_out_dev, int32_t* forced_out_dev, int32_t* pruned_out_dev, int32_t* cstar_out_dev, int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, off by default: FIRST-PLAY URGENCY for unvisited children (lc0, KataGo).  Node.get_ucb scores a child that was never
+ * tried as 1 - ((0 / 1e-6) + 1) / 2 = 0.5, a dead draw, at every node: where the mover is losing every untried move then looks better than
+ * everything tried and the search goes wide, where the mover is winning untried moves are handicapped for no reason.  With the option on an
+ * unvisited child is scored from a first-play value v0 that is a constant or follows the parent's value, with one setting for the board's
+ * root and one for every node below it (lc0's self-play uses a different one at the root, so that root noise gets looked at).  Never switched
+ * on, every kernel that runs today runs unchanged: the option is an instantiation of k_search_step of its own, with one more trailing argument
+ * beside ForcedOpts (k_search_step<VL, SOLVE, [ForcedOpts,] FpuOpts>).  k_search_begin selects nothing and k_play reads visited children only:
+ * neither has an FPU variant.
+ * The rule, wherever a child is selected (sz_search_step and the descent-only launch of sz_search_begin) for a parent p with children
+ * c = 0..K-1.  All arithmetic is f32, every operator one IEEE rounding (-ffp-contract=off):
+ *   counts     n_c = N_c + k_c (k_c the in-flight count, 0 without leaf batching); a child is VISITED when n_c >= 1.  n_p = N_p + k_p and
+ *              sq = (float)sqrt((double)n_p), as without the option.
+ *   visited    a visited child is scored exactly as without the option: get_ucb on n_c and W_c + lam*k_c.
+ *   mode       the mode and value in force are the root's at depth 0 of a descent (the board's root, of a fresh and of a continued search
+ *              alike) and the tree's elsewhere.  With SZ_FPU_REFERENCE an unvisited child is scored exactly as without the option.
+ *   unvisited  otherwise an unvisited child scores q0 + u, u = (((1.0f / (float)(0 + 1)) * sq) * c_puct) * P_c (get_ucb's second term at a
+ *              count of 0) and q0 = (v0 + 1.0f) / 2.0f, with
+ *                ABSOLUTE   v0 = value
+ *                REDUCTION  v0 = vp - (value * (float)sqrt((double)mass)), where vp = (float)W_p / ((float)N_p + 1e-6f) is taken from the
+ *                           parent's own stored edge (the root is edge 0; no in-flight terms; a fresh root's N_p carries the reference's
+ *                           extra 1 of mcts.py:46, which is not corrected) and mass is the sum of P_c over the visited children in a fixed
+ *                           order: lane l adds children l, l+64, ... ascending, skipping unvisited ones, then an xor butterfly (offsets 32
+ *                           down to 1).  A child's proven label does not matter for mass.
+ *              then the clamp: if (!(v0 >= -1.0f)) v0 = -1.0f; if (v0 > 1.0f) v0 = 1.0f.  vp and mass are computed once per parent.
+ *   arg-max    the arg-max, its first-maximum tie-break and the solver's skipping of WIN children (all children when every child is WIN) are
+ *              unchanged.  On a forced board (sz_set_forced_playouts) the forced child decides first, as without the option; it only ever
+ *              looks at children with n_c >= 1.  Policy-target pruning and the ending rules read visited children only and are untouched.
+ * ABSOLUTE with value 0 gives q0 = 0.5f, exactly what get_ucb yields for an unvisited child: an engine set to ABSOLUTE 0 at both sites builds
+ * the same trees as one with the option off, bit for bit, through different kernels.
+ * Works with learning 0 and 1.  Only selection changes and the tree is never modified, so changing the option does not drop kept subtrees.
+ * Orthogonal to sz_set_search_options (any L, solver on or off), budgets, visit targets, root noise, forced playouts, endings, sz_compact,
+ * sz_compact_searching and sz_play_moves, on engines with and without reuse_subtree.
+ * Held bit for bit to the host restatement tests/fpuref.py by tests/test_gpu_fpu.py.  Its effect on playing strength is unmeasured. */
+enum { SZ_FPU_REFERENCE = 0, SZ_FPU_ABSOLUTE = 1, SZ_FPU_REDUCTION = 2 };
+typedef struct sz_fpu_options {
+    int32_t tree_mode;  float tree_value;     /* every node below the root */
+    int32_t root_mode;  float root_value;     /* the board's root (depth 0 of a descent), fresh or continued search */
+} sz_fpu_options;                             /* 16 bytes */
+/* opt == NULL, or both modes SZ_FPU_REFERENCE, switches the option off: the kernels that run without it then run.  SZ_ERR_INVALID: a mode
+ * outside 0..2, an ABSOLUTE value that is not finite or outside [-1, 1], a REDUCTION value that is not finite, negative or above 2 (the
+ * value of a REFERENCE site is ignored).  SZ_ERR_STATE during a search (the rule of sz_set_search_budgets; nothing is changed then).  Takes
+ * effect at the next sz_search_begin and holds until changed. */
+int sz_set_fpu(sz_engine* e, const sz_fpu_options* opt, void* stream);
+/* test: the DEVICE code of selection under the option (the function the option's k_search_step calls) on caller-supplied children, one
+ * wavefront per case, in the manner of sz_debug_select and sz_debug_forced.  Case c owns children offsets[c]..offsets[c+1] (1..SZ_MAX_MOVES
+ * each) of vc (N), inflight (k), value_sum (f64), prior (f32) and proven (codes of sz_root_proven; NULL = the instantiations without the
+ * solver); parent_visits[c] (n_p), the parent's stored parent_n[c] (N_p) and parent_w[c] (W_p, f64), c_puct[c], is_root[c] (!= 0: the
+ * root's mode and value apply) and opts[c]; virtual_loss is one number for all cases.  Writes every child's score (a WIN child the arg-max
+ * skips included) and per case the selected child.  opts are not checked.  All device pointers. */
+int sz_debug_select_fpu(const int32_t* offsets_dev, const int32_t* vc_dev, const int32_t* inflight_dev, const double* value_sum_dev, const float* prior_dev,
+                        const int8_t* proven_dev, const int32_t* parent_visits_dev, const int32_t* parent_n_dev, const double* parent_w_dev, const float* c_dev,
+                        const int32_t* is_root_dev, const sz_fpu_options* opts_dev, float virtual_loss, float* ucb_out_dev, int32_t* selected_out_dev,
+                        int32_t n_cases, void* stream);
+
 /* NON-REFERENCE option, off by default: RESIGNATION and ADJUDICATED GAME ENDINGS (AlphaZero, lc0, KataGo).  A self-play cycle lasts as long
  * as its longest game, and a game the rules have not ended yet is cut by the host without a result.  With the option on, sz_play ends a
  * board's game INSTEAD of playing a move when the finished search says the game is decided: the mover's most visited move has looked lost for

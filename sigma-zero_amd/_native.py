@@ -16,6 +16,7 @@ SZ_NN_TOWER_WGB1, SZ_NN_TOWER_WGB2 = 0x10000000, 0x20000000
 SZ_MAX_LEAVES_PER_STEP = 256
 SZ_PROVEN_UNKNOWN, SZ_PROVEN_WIN, SZ_PROVEN_DRAW, SZ_PROVEN_LOSS = 0, 1, 2, 3      # codes of sz_root_proven / sz_debug_tree_proven
 SZ_END_NONE, SZ_END_RESIGN, SZ_END_DRAW, SZ_END_PROVEN = 0, 1, 2, 3                # kinds of sz_fetch_endings (sz_set_endings)
+SZ_FPU_REFERENCE, SZ_FPU_ABSOLUTE, SZ_FPU_REDUCTION = 0, 1, 2                      # modes of sz_fpu_options (sz_set_fpu)
 
 
 class sz_config(C.Structure):
@@ -31,6 +32,10 @@ class sz_search_options(C.Structure):
 class sz_ending_options(C.Structure):
     _fields_ = [("resign_value", C.c_float), ("resign_patience", C.c_int32), ("resign_min_ply", C.c_int32),
                 ("draw_value", C.c_float), ("draw_patience", C.c_int32), ("draw_min_ply", C.c_int32), ("proven", C.c_int32)]
+
+
+class sz_fpu_options(C.Structure):
+    _fields_ = [("tree_mode", C.c_int32), ("tree_value", C.c_float), ("root_mode", C.c_int32), ("root_value", C.c_float)]
 
 
 class sz_stats(C.Structure):
@@ -66,6 +71,8 @@ EXPORTS = {
     "sz_set_forced_playouts": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "sz_forced_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "sz_debug_forced": (C.c_int, [C.c_void_p] * 9 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
+    "sz_set_fpu": (C.c_int, [C.c_void_p, C.POINTER(sz_fpu_options), C.c_void_p]),
+    "sz_debug_select_fpu": (C.c_int, [C.c_void_p] * 12 + [C.c_float] + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p]),
     "sz_set_endings": (C.c_int, [C.c_void_p, C.POINTER(sz_ending_options), C.c_void_p, C.c_void_p]),
     "sz_fetch_endings": (C.c_int, [C.c_void_p] * 7),
     "sz_ending_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

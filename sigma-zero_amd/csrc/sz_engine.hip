@@ -94,6 +94,7 @@ __device__ __forceinline__ u64 uni64(u64 x) {
     u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)x), hi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(x >> 32));
     return ((u64)hi << 32) | lo;
 }
+__device__ __forceinline__ double uni_f64(double x) { return __longlong_as_double((long long)uni64((u64)__double_as_longlong(x))); }
 __device__ __forceinline__ SzPos load_pos(const SzPos* ptr) {
     SzPos p = *ptr;
     for (int k = 0; k < 6; k++) p.pc[k] = uni64(p.pc[k]);
@@ -229,6 +230,72 @@ __device__ __forceinline__ int wave_select_root_forced(const EdgeStat* ch, const
     *forced = bi >= 0;
     if (bi < 0) bi = wave_select_child<VL, SOLVE>(ch, cm, k, n, parentVC, c_puct, lam, nullptr);
     return bi;
+}
+
+// NON-REFERENCE option (sz_set_fpu): what the FPU instantiations of k_search_step take on top of View, and of ForcedOpts when both options are
+// on: k_search_step<VL, SOLVE, FpuOpts>, k_search_step<VL, SOLVE, ForcedOpts, FpuOpts>.  k_search_begin and k_play have no FPU variant.
+struct FpuOpts { sz_fpu_options o; };
+template <typename... FO> constexpr bool is_fpu = (std::is_same_v<FO, FpuOpts> || ...);
+__device__ __forceinline__ const ForcedOpts& forced_opts(const ForcedOpts& fo, const FpuOpts&) { return fo; }
+__device__ __forceinline__ const FpuOpts& fpu_opts(const FpuOpts& fp) { return fp; }
+__device__ __forceinline__ const FpuOpts& fpu_opts(const ForcedOpts&, const FpuOpts& fp) { return fp; }
+
+// Node.select under first-play urgency (sz_set_fpu; include/sigmazero.h is the rule): wave_select_child with the score of an unvisited
+// child (n_c = N_c + k_c == 0) replaced by q0 + ucb_u(0, P_c, sq, c_puct), q0 = (v0 + 1) / 2.  mode / value: the site's (the root's at depth 0,
+// the tree's below; uniform); pN / pW: the parent's own stored edge.  v0 and with it q0 are formed once per parent and are the same in every
+// lane: the xor butterfly leaves one sum in all 64 (f32 addition commutes), and it is read back through readfirstlane so that the compiler
+// knows.  A visited child, the arg-max, its tie-break and the solver's skipping of WIN children are wave_select_child's; mode ==
+// SZ_FPU_REFERENCE scores every child as it does.  ucb_out (optional, test hook) receives every child's value, skipped WIN children included.
+template <bool VL, bool SOLVE>
+__device__ __forceinline__ int wave_select_child_fpu(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam,
+                                                     int mode, float value, int pN, double pW, float* ucb_out) {
+    const int lane = lane_id();
+    const float sq = (float)sqrt((double)parentVC);
+    bool skip_wins = false;
+    if constexpr (SOLVE) {
+        bool open = false;
+        for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
+        skip_wins = __ballot(open) != 0;
+    }
+    float q0 = 0.5f;
+    if (mode != SZ_FPU_REFERENCE) {
+        float v0 = value;
+        if (mode == SZ_FPU_REDUCTION) {
+            float part = 0.f;                                            // the prior mass of the visited children, a label does not matter
+            for (int c = lane; c < n; c += 64) {
+                const EdgeStat s = ch[c];
+                int nc = s.N;
+                if constexpr (VL) nc += k[c];
+                if (nc >= 1) part = part + s.P;
+            }
+            const float mass = __int_as_float(uni(__float_as_int(wave_sum_butterfly(part))));
+            const float vp = (float)pW / ((float)pN + 1e-6f);
+            v0 = vp - (value * (float)sqrt((double)mass));
+        }
+        if (!(v0 >= -1.0f)) v0 = -1.0f;
+        if (v0 > 1.0f) v0 = 1.0f;
+        q0 = (v0 + 1.0f) / 2.0f;
+    }
+    float best = 0.f; int bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) {
+        const EdgeStat s = ch[c];
+        int kc = 0;
+        if constexpr (VL) kc = k[c];
+        const int nc = s.N + kc;
+        float u;
+        if (nc >= 1 || mode == SZ_FPU_REFERENCE) {
+            if constexpr (VL) u = ucb_value(nc, s.W + (double)lam * (double)kc, s.P, sq, c_puct);
+            else u = ucb_value(s.N, s.W, s.P, sq, c_puct);
+        } else u = q0 + ucb_u(0, s.P, sq, c_puct);
+        if (ucb_out) ucb_out[c] = u;
+        if constexpr (SOLVE) { if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue; }
+        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+    }
+    return uni(bi);
 }
 
 // policy-target pruning of a finished search (sz_set_forced_playouts): vis[0..n) holds the root children's counted visits N_c on entry and the
@@ -788,9 +855,11 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // leaf_ptrs<VL>; only the in-flight counts, n_pend, the collision break and "gather on" against "one leaf, stop" sit under if constexpr (VL).
 // FO = ForcedOpts (sz_set_forced_playouts): on a board with ST_FORCED the selection at depth 0 is wave_select_root_forced; below the root
 // nothing changes.
+// FO = [ForcedOpts,] FpuOpts (sz_set_fpu): every selection is wave_select_child_fpu, after wave_forced_child at the root of a forced board.
 template <bool VL, bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb, FO... fo) {
     constexpr bool FORCED = is_forced<FO...>;
+    constexpr bool FPU = is_fpu<FO...>;
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -927,7 +996,19 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
         while (mn > 0 && !proven) {                                     // Node.select
             int bi;
-            if constexpr (FORCED) {
+            if constexpr (FPU) {
+                // sz_set_fpu: the root's mode and value at depth 0, the tree's below; vp from the parent's own stored edge (cur; the root is edge 0)
+                const sz_fpu_options& fp = fpu_opts(fo...).o;
+                const EdgeStat ps = bp.es[cur];
+                bi = -1;
+                if constexpr (FORCED) {                                 // the forced child decides first, as without the option
+                    if (d == 0 && (status & ST_FORCED)) bi = wave_forced_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, forced_opts(fo...).k);
+                    n_forced += bi >= 0 ? 1 : 0;
+                }
+                if (bi < 0)
+                    bi = wave_select_child_fpu<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, d == 0 ? fp.root_mode : fp.tree_mode,
+                                                          d == 0 ? fp.root_value : fp.tree_value, uni(ps.N), uni_f64(ps.W), nullptr);
+            } else if constexpr (FORCED) {
                 bool forced = false;
                 if (d == 0 && (status & ST_FORCED))
                     bi = wave_select_root_forced<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, forced_opts(fo...).k, &forced);
@@ -1347,6 +1428,32 @@ __global__ __launch_bounds__(64) void k_debug_forced(const int* offsets, const i
     for (int c = lane; c < n; c += 64) pruned_out[lo + c] = vis[c];
 }
 
+// test hook (sz_debug_select_fpu): wave_select_child_fpu, the function k_search_step<.., FpuOpts> calls, on caller-supplied children, one wave per
+// case.  proven == NULL: the instantiations without the solver
+__global__ __launch_bounds__(64) void k_debug_select_fpu(const int* offsets, const int* vc, const int* inflight, const double* wsum, const float* prior,
+                                                         const int8_t* proven, const int* parent_visits, const int* parent_n, const double* parent_w,
+                                                         const float* c_puct, const int* is_root, const sz_fpu_options* opts, float lam, float* ucb_out, int* selected_out) {
+    extern __shared__ u64 lds64[];
+    EdgeStat* ch = (EdgeStat*)lds64;
+    EdgeMeta* cm = (EdgeMeta*)(ch + SZ_MAX_CHILDREN);
+    int* kk = (int*)(cm + SZ_MAX_CHILDREN);
+    const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
+    if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) selected_out[cs] = -1; return; }
+    for (int c = lane; c < n; c += 64) {
+        EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s;
+        EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = 0; m.term = 0; m.tval = 0; m.pad = (unsigned short)(proven ? (proven[lo + c] & PR_MASK) : 0); cm[c] = m;
+        kk[c] = inflight[lo + c];
+    }
+    __syncthreads();
+    const sz_fpu_options o = opts[cs];
+    const int root = uni(is_root[cs]);
+    const int mode = uni(root ? o.root_mode : o.tree_mode);
+    const float value = root ? o.root_value : o.tree_value;
+    const int bi = proven ? wave_select_child_fpu<true, true>(ch, cm, kk, n, parent_visits[cs], c_puct[cs], lam, mode, value, uni(parent_n[cs]), uni_f64(parent_w[cs]), ucb_out + lo)
+                          : wave_select_child_fpu<true, false>(ch, cm, kk, n, parent_visits[cs], c_puct[cs], lam, mode, value, uni(parent_n[cs]), uni_f64(parent_w[cs]), ucb_out + lo);
+    if (lane == 0) selected_out[cs] = bi;
+}
+
 // test hook (sz_debug_endings): wave_ending, the function k_play<.., EndOpts> calls, on caller-supplied cases, one wave per case
 __global__ __launch_bounds__(64) void k_debug_endings(const int* offsets, const int* vc, const double* wsum, const int8_t* root_proven, const uint8_t* colour,
                                                       const int* ply, const uint8_t* holdout, const int* state_in, const sz_ending_options* opts,
@@ -1392,6 +1499,8 @@ struct sz_engine {
     float forced_k;                 // sz_set_forced_playouts: the constant the next sz_search_begin takes up (0 = off)
     ForcedOpts fo;                  // ... and what the searches begun since run with: fo.k > 0 selects the FORCED instantiations.  fo.boards
                                     //     [n_boards] and fo.stat [n_boards][2] are allocated by the first enabling call
+    sz_fpu_options fpu_next;        // sz_set_fpu: what the next sz_search_begin takes up (all zero = off)
+    FpuOpts fp;                     // ... and what the searches begun since run with: a mode other than SZ_FPU_REFERENCE selects the FPU instantiations
     int end_on;                     // sz_set_endings: sz_play runs the ENDING instantiations of k_play
     EndOpts eo;                     // ... with these; its arrays are allocated by the first enabling call (eo.state != NULL from then on)
 };
@@ -1718,12 +1827,20 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
 
 // the k_search_step instantiation of the options in force; policy == NULL: the descent-only launch of sz_search_begin
 static void launch_step(sz_engine* e, const float* policy, const float* value, void* planes, hipStream_t s) {
+    const bool fpu = e->fp.o.tree_mode != SZ_FPU_REFERENCE || e->fp.o.root_mode != SZ_FPU_REFERENCE;          // sz_set_fpu
     with_search_options(e, [&](auto vl, auto solve, auto forced) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
-        if constexpr (decltype(forced)::value)
-            hipLaunchKernelGGL((k_search_step<VL, SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fo);
-        else
-            hipLaunchKernelGGL((k_search_step<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{});
+        if constexpr (decltype(forced)::value) {
+            if (fpu)
+                hipLaunchKernelGGL((k_search_step<VL, SOLVE, ForcedOpts, FpuOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fo, e->fp);
+            else
+                hipLaunchKernelGGL((k_search_step<VL, SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fo);
+        } else {
+            if (fpu)
+                hipLaunchKernelGGL((k_search_step<VL, SOLVE, FpuOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fp);
+            else
+                hipLaunchKernelGGL((k_search_step<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{});
+        }
     });
 }
 
@@ -1731,6 +1848,7 @@ int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     e->fo.k = e->forced_k;                                                  // sz_set_forced_playouts takes effect here
+    e->fp.o = e->fpu_next;                                                  // ... and sz_set_fpu
     with_search_options(e, [&](auto vl, auto solve, auto forced) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         if constexpr (decltype(forced)::value)
@@ -1885,6 +2003,30 @@ int sz_set_forced_playouts(sz_engine* e, float k, const uint8_t* boards, void* s
         HIPCHK(hipStreamSynchronize(s));                                    // the staging array goes out of scope
     }
     e->forced_k = k;
+    return SZ_OK;
+}
+
+static bool fpu_site_ok(int mode, float value) {
+    if (mode == SZ_FPU_REFERENCE) return true;                              // its value is ignored
+    if (!std::isfinite(value)) return false;
+    if (mode == SZ_FPU_ABSOLUTE) return value >= -1.0f && value <= 1.0f;
+    if (mode == SZ_FPU_REDUCTION) return value >= 0.0f && value <= 2.0f;
+    return false;
+}
+
+int sz_set_fpu(sz_engine* e, const sz_fpu_options* opt, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (opt && (!fpu_site_ok(opt->tree_mode, opt->tree_value) || !fpu_site_ok(opt->root_mode, opt->root_value))) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    bool busy = false;
+    int rc = search_in_progress(e, (hipStream_t)stream, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    sz_fpu_options o = {SZ_FPU_REFERENCE, 0.0f, SZ_FPU_REFERENCE, 0.0f};
+    if (opt) o = *opt;
+    if (o.tree_mode == SZ_FPU_REFERENCE) o.tree_value = 0.0f;
+    if (o.root_mode == SZ_FPU_REFERENCE) o.root_value = 0.0f;
+    e->fpu_next = o;
     return SZ_OK;
 }
 
@@ -2171,6 +2313,19 @@ int sz_debug_forced(const int32_t* offsets_dev, const int32_t* vc_dev, const int
     hipLaunchKernelGGL(k_debug_forced, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(EdgeMeta) + 2 * sizeof(int)), (hipStream_t)stream,
                        offsets_dev, vc_dev, inflight_dev, value_sum_dev, prior_dev, proven_dev, parent_visits_dev, c_dev, forced_k_dev, virtual_loss,
                        selected_out_dev, forced_out_dev, pruned_out_dev, cstar_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_select_fpu(const int32_t* offsets_dev, const int32_t* vc_dev, const int32_t* inflight_dev, const double* value_sum_dev, const float* prior_dev,
+                        const int8_t* proven_dev, const int32_t* parent_visits_dev, const int32_t* parent_n_dev, const double* parent_w_dev, const float* c_dev,
+                        const int32_t* is_root_dev, const sz_fpu_options* opts_dev, float virtual_loss, float* ucb_out_dev, int32_t* selected_out_dev,
+                        int32_t n_cases, void* stream) {
+    if (!offsets_dev || !vc_dev || !inflight_dev || !value_sum_dev || !prior_dev || !parent_visits_dev || !parent_n_dev || !parent_w_dev || !c_dev || !is_root_dev ||
+        !opts_dev || !ucb_out_dev || !selected_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_select_fpu, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(EdgeMeta) + sizeof(int)), (hipStream_t)stream,
+                       offsets_dev, vc_dev, inflight_dev, value_sum_dev, prior_dev, proven_dev, parent_visits_dev, parent_n_dev, parent_w_dev, c_dev, is_root_dev,
+                       opts_dev, virtual_loss, ucb_out_dev, selected_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

@@ -142,6 +142,46 @@ def forced_playout_options_of(args):
     return float(k)
 
 
+FPU_KEYS = ("mode", "value", "root_mode", "root_value")
+FPU_MODES = {"reference": N.SZ_FPU_REFERENCE, "absolute": N.SZ_FPU_ABSOLUTE, "reduction": N.SZ_FPU_REDUCTION}
+
+
+def fpu_options_of(args):
+    """The first-play-urgency options of args, checked: (tree_mode, tree_value, root_mode, root_value) with the modes as SZ_FPU_* codes and
+    the values rounded to f32, or None when the key is absent.  NON-REFERENCE, default off.
+
+    args["fpu"] = {"mode": "reference" | "absolute" | "reduction", "value": x, "root_mode": ..., "root_value": ...} sets what selection takes a
+    child without a visit to be worth (sz_set_fpu).  "reference": Node.get_ucb's 0.5, a dead draw.  "absolute": q0 = (x + 1) / 2, x in [-1, 1]
+    a value from the mover's side.  "reduction": x in [0, 2] is taken off the parent's own value, scaled by the square root of the prior mass
+    of the children already visited: v0 = vp - x * sqrt(mass), clamped to [-1, 1] (lc0, KataGo).  mode / value hold below the root, root_mode /
+    root_value at the root of every search; each of the root's defaults to the tree's.  A "reference" site needs no value.  Checked in this
+    order: the dict and its keys, mode, value, root_mode, root_value.  Its effect on playing strength is unmeasured."""
+    opt = args.get("fpu")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(FPU_KEYS):
+        raise ValueError("args['fpu'] must be a dict with keys from %s, got %r" % (FPU_KEYS, opt))
+    if "mode" not in opt:
+        raise ValueError("args['fpu'] needs 'mode'")
+    sites = [("mode", "value", opt["mode"], opt.get("value")),
+             ("root_mode", "root_value", opt.get("root_mode", opt["mode"]), opt.get("root_value", opt.get("value")))]
+    out = []
+    for mkey, vkey, mode, value in sites:
+        if not isinstance(mode, str) or mode not in FPU_MODES:
+            raise ValueError("args['fpu'][%r] must be one of 'reference', 'absolute', 'reduction', got %r" % (mkey, mode))
+        if mode == "reference":
+            out += [FPU_MODES[mode], 0.0]
+            continue
+        if value is None:
+            raise ValueError("args['fpu'][%r] = %r needs %r" % (mkey, mode, vkey))
+        lo, hi = (-1.0, 1.0) if mode == "absolute" else (0.0, 2.0)
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) or \
+                not (math.isfinite(value) and lo <= float(np.float32(value)) <= hi):            # NaN fails the comparison
+            raise ValueError("args['fpu'][%r] must be a number in [%g, %g] with %r, got %r" % (vkey, lo, hi, mode, value))
+        out += [FPU_MODES[mode], float(np.float32(value))]
+    return tuple(out)
+
+
 ENDING_KEYS = ("resign_value", "resign_patience", "resign_min_ply", "draw_value", "draw_patience", "draw_min_ply", "proven", "holdout")
 ENDING_KINDS = {N.SZ_END_RESIGN: "resign", N.SZ_END_DRAW: "draw_adjudicated", N.SZ_END_PROVEN: "proven"}
 
@@ -230,6 +270,8 @@ class SelfPlayEngine:
         self.forced_k = forced_playout_options_of(self.args)
         if self.forced_k is not None and not learning:
             raise ValueError("args['forced_playouts'] needs learning=True: it is an exploration option of self-play, like root noise")
+        # NON-REFERENCE option (default off): first-play urgency for unvisited children, see fpu_options_of
+        self.fpu = fpu_options_of(self.args)
         # NON-REFERENCE option (default off): resignation and adjudicated game endings, see ending_options_of
         self.endings = ending_options_of(self.args)
         self.quiet = None             # boards whose next searches get no root noise (set_quiet; visit_targets mode)
@@ -282,6 +324,8 @@ class SelfPlayEngine:
             self.set_visit_targets(np.full(self.B, self.S, np.int32))
         if self.forced_k is not None:  # every board is forced until set_forced_playouts says otherwise
             self.set_forced_playouts(self.forced_k)
+        if self.fpu is not None:
+            self.set_fpu(self.fpu)
         if self.endings is not None:   # no holdout board until set_endings says otherwise
             self.set_endings(self.endings)
 
@@ -393,6 +437,14 @@ class SelfPlayEngine:
         out = (C.c_uint64 * 2)()
         N.check(N.lib().sz_forced_stats(self._e, out, self._stream()), "sz_forced_stats")
         return int(out[0]), int(out[1])
+
+    def set_fpu(self, opts):
+        """First-play urgency (sz_set_fpu, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (tree_mode, tree_value,
+        root_mode, root_value) as fpu_options_of returns it (SZ_FPU_* codes), or None = off.  Between searches only; kept subtrees are not
+        dropped."""
+        o = None if opts is None else N.sz_fpu_options(int(opts[0]), float(opts[1]), int(opts[2]), float(opts[3]))
+        N.check(N.lib().sz_set_fpu(self._e, None if o is None else C.byref(o), self._stream()), "sz_set_fpu")
+        self.fpu = None if opts is None else tuple(opts)
 
     def set_endings(self, opts, holdout=None):
         """Resignation and adjudicated game endings (sz_set_endings, a NON-REFERENCE option) from the next play() on, until changed.  opts: a

@@ -111,6 +111,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     ends gets its result without a move: the ending ply is a training sample like any other recorded ply (with args["playout_cap"] only if it
     was a full-search ply), 'chosen_actions' gets no entry for it, and 'rewards' follow from 'result' as always.  A refill hands the engine the
     holdout flags of the games it starts.  The extra per-ply host copy (sz_fetch_endings) happens in this mode only.  Strength effect unmeasured.
+    args["fpu"] = {...} (NON-REFERENCE, selfplay.fpu_options_of): first-play urgency, what selection takes an unvisited child to be worth
+    (sz_set_fpu), one setting for the root and one below it, on fast and full plies alike; the engine applies it.  Strength effect unmeasured.
     holdout(game) -> bool: whether a game is a holdout game, like `uniforms`.  Default: a numpy Generator of its own, one draw per game in game
       order when the game starts, true with probability args["endings"]["holdout"].
     full_search(game, ply) -> bool: the full / fast decision, like `uniforms`.  Default: a numpy Generator of its own, drawn per ply for every
