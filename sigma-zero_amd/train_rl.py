@@ -460,11 +460,40 @@ def write_step_log(path, epoch, hist, lr_scheduler, append=True):
             f.write(json.dumps(rec) + "\n")
 
 
-def main(argv=None):
-    """`python -m torch.distributed.run --nproc-per-node N -m sigma_zero_amd.train_rl ...` (or plain python for one GPU):
-    every rank self-plays its own games on its own GPU (no communication), then all ranks train with averaged gradients."""
+def selfplay_args_of(a):
+    """the self-play `args` dict of main()'s parsed flags `a`; nothing is checked here: the engine's option readers (selfplay.search_options_of,
+    visit_target_options_of, forced_playout_options_of, ending_options_of, sim.playout_cap_of) refuse what does not go together"""
+    args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
+    if a.leaves_per_step != 1:
+        args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
+    if a.solver:
+        args["solver"] = True
+    if a.playout_cap_fast:
+        args["playout_cap"] = {"fast": a.playout_cap_fast, "p_full": a.playout_cap_full_prob}
+    if a.root_dirichlet_alpha:
+        args["root_dirichlet_alpha"] = a.root_dirichlet_alpha
+    if a.visit_targets:
+        args.update(reuse_subtree=True, visit_targets=True)
+        if a.leaves_per_step != 1 or a.solver:
+            args["combine_options"] = True
+    if a.quiet_fast_plies:
+        args["quiet_fast_plies"] = True
+    if a.forced_playouts:
+        args["forced_playouts"] = a.forced_playouts
+    if a.resign_patience or a.draw_patience or a.adjudicate_proven:
+        end = {"resign_patience": a.resign_patience, "resign_min_ply": a.resign_min_ply, "draw_patience": a.draw_patience, "draw_min_ply": a.draw_min_ply,
+               "proven": bool(a.adjudicate_proven), "holdout": a.ending_holdout}
+        if a.resign_value is not None:
+            end["resign_value"] = a.resign_value
+        if a.draw_value is not None:
+            end["draw_value"] = a.draw_value
+        args["endings"] = end
+    return args
+
+
+def flag_parser():
+    """main()'s command-line flags"""
     import argparse
-    import torch.distributed as dist
     ap = argparse.ArgumentParser(description="RL loop of train_RL.py on the MI355X engine")
     ap.add_argument("--epochs", type=int, default=1)                  # train_RL.py:174 num_epochs (cycles)
     ap.add_argument("--start-epoch", type=int, default=1)             # :175
@@ -523,7 +552,14 @@ def main(argv=None):
     ap.add_argument("--adjudicate-proven", action="store_true", help="NON-REFERENCE: a game whose root the solver has proven ends with that result (needs --solver)")
     ap.add_argument("--ending-holdout", type=float, default=0.0, metavar="Q",
                     help="share of the games that are played out and only marked where a rule would have ended them; the cycle log counts how often the mark was wrong")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    """`python -m torch.distributed.run --nproc-per-node N -m sigma_zero_amd.train_rl ...` (or plain python for one GPU):
+    every rank self-plays its own games on its own GPU (no communication), then all ranks train with averaged gradients."""
+    import torch.distributed as dist
+    a = flag_parser().parse_args(argv)
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     gpr = [int(x) for x in str(a.games_per_rank).split(",")]
     a.games_per_rank = gpr[rank] if len(gpr) > 1 else gpr[0]
@@ -551,31 +587,7 @@ def main(argv=None):
     sched = torch.optim.lr_scheduler.StepLR(optimiser, step_size=500, gamma=0.95)           # created after the resume, like train_RL.py:199
     sync_module_state(model, average_buffers=False)
     sync = GradSync(model) if world > 1 else None
-    args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
-    if a.leaves_per_step != 1:
-        args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
-    if a.solver:
-        args["solver"] = True
-    if a.playout_cap_fast:
-        args["playout_cap"] = {"fast": a.playout_cap_fast, "p_full": a.playout_cap_full_prob}
-    if a.root_dirichlet_alpha:
-        args["root_dirichlet_alpha"] = a.root_dirichlet_alpha
-    if a.visit_targets:
-        args.update(reuse_subtree=True, visit_targets=True)
-        if a.leaves_per_step != 1 or a.solver:
-            args["combine_options"] = True
-    if a.quiet_fast_plies:
-        args["quiet_fast_plies"] = True
-    if a.forced_playouts:
-        args["forced_playouts"] = a.forced_playouts
-    if a.resign_patience or a.draw_patience or a.adjudicate_proven:
-        end = {"resign_patience": a.resign_patience, "resign_min_ply": a.resign_min_ply, "draw_patience": a.draw_patience, "draw_min_ply": a.draw_min_ply,
-               "proven": bool(a.adjudicate_proven), "holdout": a.ending_holdout}
-        if a.resign_value is not None:
-            end["resign_value"] = a.resign_value
-        if a.draw_value is not None:
-            end["draw_value"] = a.draw_value
-        args["endings"] = end
+    args = selfplay_args_of(a)
     import random
     random.seed(1000 + rank)
     np.random.seed(1000 + rank)

@@ -210,8 +210,11 @@ def scenarios():
         Board("sp811/plays_on", start(811), "dyadic", 811, greedy, [F, 24, F, 9], [0] * 4, [0] * 4, 0, "plays_on"),
     ], [True] * 4, [2.0] * 4, False, [None, LATE, LATE, LATE]))
     # 3. proven roots (with the solver; without it `proven` is ignored and every board plays on): the 218-move position is WIN for the mover,
-    #    mated_in_2 LOSS, forced_draw DRAW; the WIN board is a holdout board, which a proof ignores
-    out.append(Scenario("proven_endings", 64, False, True, worst_case(64), 2, [
+    #    mated_in_2 LOSS, forced_draw DRAW; the WIN board is a holdout board, which a proof ignores.  A Chess960 engine (as forcedref's
+    #    wide_forced): the sp333 board spells castling king-takes-rook, and sz_upload_game hands the engine no flag, so on a standard engine
+    #    the two sides name a castling move differently once a search reaches one (under FPU's deeper trees it does, tests/fullref.py); the
+    #    FEN boards have no castling rights
+    out.append(Scenario("proven_endings", 64, True, True, worst_case(64), 2, [
         Board("moves_218/win/holdout", fen(WIDE_FEN), "dyadic", 1, greedy, [F] * 2, [0] * 2, [1] * 2, 1, "proven_win"),
         Board("mated_in_2/loss", fen(MATED_IN_2_FEN), "dyadic", 4, greedy, [F] * 2, [0] * 2, [1] * 2, 0, "proven_loss"),
         Board("forced_draw", fen(FORCED_DRAW_FEN), "dyadic", 3, greedy, [F] * 2, [0] * 2, [0] * 2, 0, "proven_draw"),
@@ -219,7 +222,7 @@ def scenarios():
     ], [True] * 2, [4.0, 2.0], True, [PROVE] * 2))
     # 4. the second engine: the same position with the option on and `proven` off plays the proving move as always; `proven` comes on for
     #    ply 1, where the kept root of the mated_in_2 board is WIN for the side to move
-    out.append(Scenario("proven_late", 64, False, True, worst_case(64), 2, [
+    out.append(Scenario("proven_late", 64, True, True, worst_case(64), 2, [
         Board("moves_218/plays_win_move", fen(WIDE_FEN), "dyadic", 1, greedy, [F] * 2, [0] * 2, [1] * 2, 0, "plays_win_move"),
         Board("mated_in_2/late_win", fen(MATED_IN_2_FEN), "dyadic", 4, greedy, [F] * 2, [0] * 2, [1] * 2, 0, "late_win"),
         Board("forced_draw/plays_on", fen(FORCED_DRAW_FEN), "dyadic", 3, greedy, [F] * 2, [0] * 2, [0] * 2, 0, "plays_on"),
