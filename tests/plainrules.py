@@ -5,7 +5,8 @@ It imports nothing of the project, uses no bitboards and shares no table with it
 a8 = 56; "." or a FEN piece letter), the side to move, the set of rook squares that still carry a castling right (the Shredder-FEN
 spelling) and the en-passant square.  Move generation is the textbook one: every pseudo-legal move is made on a copy and rejected if
 the mover's king is then attacked; attacks are found by looking outward from the square along rays, knight jumps and pawn captures.
-Repetition, the 75-move rule and insufficient material are not here (tests/rule_endings.py holds them).
+Repetition, the 75-move rule and insufficient material are not here: tests/plainendings.py states them on top of this module
+(tests/rule_endings.py holds ten constructed games with the oracle's expectations).
 
 Castling is stated as the FIDE Laws of Chess state it (FIDE Handbook E.01, edition in force from 1 January 2023):
 

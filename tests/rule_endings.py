@@ -1,6 +1,8 @@
 """Constructed games whose NEXT move ends the game or changes a counter class: the rule endings the perft tables do not contain.
 Each case is (name, FEN or None, uci moves, the move to look at, claim); the claim is checked on the oracle (oracle/oc_chess.c), so
-the expectations are the oracle's and not hand-written numbers.  Used on the CPU (host mirror against the oracle on every child and
+the expectations are the oracle's and not hand-written numbers.  The second, independent statement of these rules is
+tests/plainendings.py; tests/ending_lines.py places the same endings (and _long_game, _rook_snake below) at chosen depths inside the tree
+with the plain statement's expectations.  Used on the CPU (host mirror against the oracle on every child and
 grandchild, tests/test_perft_walk_driver.py) and on the device (tests/test_gpu_device_perft.py)."""
 import numpy as np
 
