@@ -465,6 +465,78 @@ int sz_debug_select_fpu(const int32_t* offsets_dev, const int32_t* vc_dev, const
                         const int32_t* is_root_dev, const sz_fpu_options* opts_dev, float virtual_loss, float* ucb_out_dev, int32_t* selected_out_dev,
                         int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, off by default: GUMBEL ROOT SEARCH (Danihelka et al., "Policy improvement by planning with Gumbel", ICLR 2022).  PUCT
+ * visit counts with root noise give no policy improvement at small simulation counts.  With the option on the root samples m moves without
+ * replacement by Gumbel-top-k, spends the search's simulations on them by sequential halving, sz_play plays the best of the most visited
+ * moves, and the training target is the completed-Q improved policy instead of the visit fractions.  A root-only rule, stateless per
+ * simulation, one wavefront per board.  Never switched on, every kernel that runs today runs unchanged: the option is an instantiation of its
+ * own, k_search_step<false, false, GumbelOpts[, FpuOpts]> (only depth 0 of a descent changes) and k_play<false, GumbelOpts>; k_search_begin
+ * has no variant, the root's network value is kept where the root is expanded.
+ * The rule.  All arithmetic is f64, every operator one IEEE rounding (-ffp-contract=off), sums run sequentially in ascending child order:
+ *   slog, sexp   libm's and the device's log / exp do not round alike, so the rule carries its own, written from + - * / and integer bit
+ *                operations only (csrc/sz_gumbel.h; tests/gumbelref.py repeats them operator for operator).
+ *                slog(x), x > 0 (a prior that is exactly 0 is dropped at expansion): x = 2^e * mant by bit operations with mant in
+ *                [sqrt(1/2), sqrt(2)) (mant >= 1.4142135623730951 is halved, e + 1), s = (mant - 1) / (mant + 1), s2 = s * s,
+ *                p = 1/19; p = p * s2 + 1/k for k = 17, 15, ..., 3, 1; slog = (2 * s) * p + (double)e * LN2, LN2 = 0.6931471805599453.  Ten terms:
+ *                the first one left out is s^20 / 21 < 2.3e-17 < 2^-53 over |s| <= 0.1716.
+ *                sexp(y), y <= 0: 0 when !(y >= -700) (the cutoff; every other result is a normal number); k = floor(y * 1.4426950408889634 +
+ *                0.5); r = (y - k * LN2_HI) - k * LN2_LO with LN2_HI = 0x3FE62E42FEE00000, LN2_LO = 0x3DEA39EF35793C76; p = 1/13!;
+ *                p = p * r + 1/j! for j = 12, 11, ..., 1, 0; the result is p with k added to its exponent bits.  Fourteen terms: the first one
+ *                left out is r^14 / 14! < 4.2e-18 < 2^-53 over |r| <= 0.3466.  Every constant 1/k, 1/j! is the correctly rounded quotient.
+ *   root         the root's children c = 0..K-1 with N_c, W_c, P_c as stored (on a learning engine the reference's constant noise mix stays
+ *                in P_c).  logit_c = slog((double)P_c).  q_c = 0.5 - 0.5 * (W_c / (double)N_c) for N_c >= 1, the mover's value of move c in
+ *                [0, 1] (a child's W is stored from the child's side to move).  vhat = the root's network value as sz_search_step reads it
+ *                when it expands the root (one float per board), v01 = 0.5 + 0.5 * (double)vhat.  maxN = max_c N_c.
+ *                sigma(x) = (((double)c_visit + (double)maxN) * (double)c_scale) * x.
+ *   schedule     goal = the new simulations of this search (sz_search_goals); n = goal - 1 root-child visits, the first simulation expands
+ *                the root.  m_eff = min(max_considered, K), L = max(1, ceil(log2 m_eff)).  Phases: the first has c = m_eff considered
+ *                children; a phase with c has r = max(1, floor(n / (L * c))) rounds of c visits each; then c <- max(2, floor(c / 2)); the
+ *                last phase is cut where n visits are scheduled; with m_eff = 1 every visit goes to that child.  The level l_t of root-child
+ *                visit t (0-based) = the rounds completed before the round t falls in, summed over the phases.  The device walks the phases.
+ *   selection    at root-child visit t: among the children with N_c == l_t the arg-max of s_c = (g_c + logit_c) + sigma(q_c), the sigma term
+ *                0.0 at N_c = 0, first maximum (wave_select_child's loop and tie-break).  The considered set is implicit: a child that is
+ *                not picked stays below the level and never matches again; level 0 picks the top m_eff by g + logit.  No child at the
+ *                level: the arg-max runs over all children; the schedule makes that impossible for a fresh root, sz_gumbel_stats counts it.
+ *                Terminal children are visited and counted like any other.  Below the root nothing changes.
+ *   sz_play      after the early return and the zero-visit check, both as without the option: the move is the arg-max of s_c over the
+ *                children with N_c == maxN, first maximum; the board's uniform is not read; the record's action and visits stay the counted
+ *                visits.
+ *   policy       sumN = sum of N_c.  v_mix = v01 when sumN is 0, else (v01 + (double)sumN * (sum over N_c >= 1 of (double)P_c * q_c /
+ *                sum over N_c >= 1 of (double)P_c)) / (1.0 + (double)sumN).  cq_c = q_c if N_c >= 1 else v_mix; z_c = logit_c + sigma(cq_c);
+ *                zmax = the maximum of z_c; e_c = sexp(z_c - zmax); policy_target[b][c] = (float)(e_c / sum of e) for c < K and 0 beyond.
+ * Not done, each a follow-up: the paper's deterministic completed-Q selection below the root; recording fast plies as training samples; and
+ * every combination refused below.
+ * Works with learning 0 and 1, budgets and visit targets on an engine without reuse_subtree (the rule reads the board's goal), sz_compact,
+ * sz_compact_searching, sz_play_moves and sz_set_fpu (below the root FPU acts as without the option; its root_mode is not consulted, Gumbel
+ * decides there).  Held bit for bit to the host restatement tests/gumbelref.py by tests/test_gpu_gumbel.py.  Strength effect unmeasured. */
+typedef struct sz_gumbel_options { int32_t max_considered; float c_visit; float c_scale; } sz_gumbel_options;   /* 12 bytes */
+/* opt == NULL switches the option off.  g_dev: device array [n_boards][SZ_MAX_MOVES] of f64 Gumbel(0,1) draws, indexed by root child in action
+ * order as gamma_dev is; NULL = all zeros, a deterministic search for match play.  It is read at every root selection and by sz_play: the
+ * caller keeps it unchanged from sz_search_begin to sz_play.  SZ_ERR_INVALID: max_considered outside 1..SZ_MAX_MOVES; c_visit or c_scale not
+ * finite or negative; a reuse_subtree engine, leaves_per_step > 1, the solver on, forced playouts on, endings on (and sz_set_leaf_batching,
+ * sz_set_solver, sz_set_search_options, sz_set_forced_playouts, sz_set_endings refuse to switch those on while Gumbel is on).  SZ_ERR_STATE:
+ * a call during a search (the rule of sz_set_search_budgets; nothing is changed then); root noise on (sz_set_root_noise or
+ * sz_set_search_root_noise with a gamma), and those two refuse a gamma with SZ_ERR_STATE while Gumbel is on: Gumbel is the root's
+ * exploration.  Takes effect at the next sz_search_begin and holds, for that search and its sz_play, until changed. */
+int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_dev, void* stream);
+/* after sz_play: the improved policy policy_target [n_boards][SZ_MAX_MOVES] f32 by root child as sz_fetch_ply's action, v_mix [n_boards] f64
+ * and the root's network value root_value [n_boards] f32.  HOST pointers, any may be NULL; rows are valid where sz_fetch_ply's active is 1.
+ * SZ_ERR_STATE on an engine the option was never switched on for.  Synchronises the stream. */
+int sz_fetch_gumbel(sz_engine* e, float* policy_target, double* v_mix, float* root_value, void* stream);
+/* cumulative over all boards: out[0] root selections made by the rule, out[1] those of them that found no child at the level (0 on fresh roots) */
+int sz_gumbel_stats(sz_engine* e, uint64_t out[2], void* stream);
+/* test: the DEVICE code of the option on caller-supplied cases, one wavefront per case, in the manner of sz_debug_forced.  Three parts, each
+ * skipped when its first array is NULL.  Maths: slog_out[c] = slog(x[c]), sexp_out[c] = sexp(x[c]).  Level: tnm[c] = (t, n, m_eff),
+ * level_out[c] = l_t, -1 unless 0 <= t < n and m_eff >= 1.  Children: case c owns children offsets[c]..offsets[c+1] (1..SZ_MAX_MOVES each) of
+ * vc (N), value_sum (f64), prior (f32) and g (f64, NULL = zeros); visit[c] (t), goal[c], root_value[c] (vhat) and opts[c] (not checked beyond
+ * max_considered >= 1 and 0 <= t < goal - 1, else -1s).  Writes the root selection at visit t and whether it fell back to all children, and of
+ * the case read as a finished search sz_play's move, every child's policy_target and v_mix.  All device pointers. */
+int sz_debug_gumbel(const double* x_dev, double* slog_out_dev, double* sexp_out_dev, const int32_t* tnm_dev, int32_t* level_out_dev,
+                    const int32_t* offsets_dev, const int32_t* vc_dev, const double* value_sum_dev, const float* prior_dev, const double* g_dev,
+                    const int32_t* visit_dev, const int32_t* goal_dev, const float* root_value_dev, const sz_gumbel_options* opts_dev,
+                    int32_t* selected_out_dev, int32_t* fallback_out_dev, int32_t* final_out_dev, float* policy_out_dev, double* v_mix_out_dev,
+                    int32_t n_cases, void* stream);
+
 /* NON-REFERENCE option, off by default: RESIGNATION and ADJUDICATED GAME ENDINGS (AlphaZero, lc0, KataGo).  A self-play cycle lasts as long
  * as its longest game, and a game the rules have not ended yet is cut by the host without a result.  With the option on, sz_play ends a
  * board's game INSTEAD of playing a move when the finished search says the game is decided: the mover's most visited move has looked lost for

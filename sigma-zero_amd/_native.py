@@ -38,6 +38,10 @@ class sz_fpu_options(C.Structure):
     _fields_ = [("tree_mode", C.c_int32), ("tree_value", C.c_float), ("root_mode", C.c_int32), ("root_value", C.c_float)]
 
 
+class sz_gumbel_options(C.Structure):
+    _fields_ = [("max_considered", C.c_int32), ("c_visit", C.c_float), ("c_scale", C.c_float)]
+
+
 class sz_stats(C.Structure):
     _fields_ = [("simulations", C.c_uint64), ("expansions", C.c_uint64), ("terminal_hits", C.c_uint64), ("sum_depth", C.c_uint64),
                 ("sum_children", C.c_uint64), ("max_edges_used", C.c_uint64), ("boards_pending", C.c_int32),
@@ -73,6 +77,10 @@ EXPORTS = {
     "sz_debug_forced": (C.c_int, [C.c_void_p] * 9 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "sz_set_fpu": (C.c_int, [C.c_void_p, C.POINTER(sz_fpu_options), C.c_void_p]),
     "sz_debug_select_fpu": (C.c_int, [C.c_void_p] * 12 + [C.c_float] + [C.c_void_p] * 2 + [C.c_int32, C.c_void_p]),
+    "sz_set_gumbel": (C.c_int, [C.c_void_p, C.POINTER(sz_gumbel_options), C.c_void_p, C.c_void_p]),
+    "sz_fetch_gumbel": (C.c_int, [C.c_void_p] * 5),
+    "sz_gumbel_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_debug_gumbel": (C.c_int, [C.c_void_p] * 19 + [C.c_int32, C.c_void_p]),
     "sz_set_endings": (C.c_int, [C.c_void_p, C.POINTER(sz_ending_options), C.c_void_p, C.c_void_p]),
     "sz_fetch_endings": (C.c_int, [C.c_void_p] * 7),
     "sz_ending_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <vector>
 #include "sz_chess.h"
+#include "sz_gumbel.h"
 #include "../../include/sigmazero.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -296,6 +297,117 @@ __device__ __forceinline__ int wave_select_child_fpu(const EdgeStat* ch, const E
         if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
     }
     return uni(bi);
+}
+
+// NON-REFERENCE option (sz_set_gumbel): what the GUMBEL instantiations take on top of View, before FpuOpts when both options are on:
+// k_search_step<false, false, GumbelOpts[, FpuOpts]> and k_play<false, GumbelOpts>.  k_search_begin has no variant: the root's network value is
+// kept where the root is expanded, in k_search_step.  Leaf batching, the solver, forced playouts and endings are refused with the option.
+struct GumbelOpts {
+    sz_gumbel_options o;
+    const double* g;            // [B][SZ_MAX_MOVES] Gumbel(0,1) draws by root child, NULL = all zeros
+    float* vhat;                // [B] the root's network value, written where the root is expanded
+    float* policy;              // [B][SZ_MAX_MOVES] the improved policy of the last sz_play
+    double* vmix;               // [B] ... and its v_mix
+    double* work;               // [B][SZ_MAX_MOVES] k_play's per-child terms, summed by one lane in child order
+    unsigned long long* stat;   // [B][2] root selections made by the rule, of them over all children because none was at the level
+};
+template <typename... FO> constexpr bool is_gumbel = (std::is_same_v<FO, GumbelOpts> || ...);
+__device__ __forceinline__ const GumbelOpts& gumbel_opts(const GumbelOpts& go) { return go; }
+__device__ __forceinline__ const GumbelOpts& gumbel_opts(const GumbelOpts& go, const FpuOpts&) { return go; }
+__device__ __forceinline__ const FpuOpts& fpu_opts(const GumbelOpts&, const FpuOpts& fp) { return fp; }
+
+// the mover's value of a visited root child in [0, 1] (a child's W is stored from the child's side to move) ...
+__device__ __forceinline__ double gumbel_q(const EdgeStat& s) { return 0.5 - 0.5 * (s.W / (double)s.N); }
+// ... and the factor of sigma(x) = (((double)c_visit + (double)maxN) * (double)c_scale) * x
+__device__ __forceinline__ double gumbel_sigma_factor(const sz_gumbel_options& o, int maxN) { return ((double)o.c_visit + (double)maxN) * (double)o.c_scale; }
+
+__device__ __forceinline__ int wave_max_visits(const EdgeStat* ch, int n) {
+    int mx = 0;
+    for (int c = lane_id(); c < n; c += 64) { const int nc = ch[c].N; if (nc > mx) mx = nc; }
+    for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(mx, off); if (o > mx) mx = o; }
+    return uni(mx);
+}
+
+// the arg-max of s_c = (g_c + slog(P_c)) + sigma(q_c) (the sigma term 0.0 at N_c = 0) over the children with N_c == level, over all of them with
+// level < 0; sf = gumbel_sigma_factor.  wave_select_child's loop, butterfly and first-maximum tie-break in f64.  -1: no child is at the level.
+__device__ __forceinline__ int wave_gumbel_best(const EdgeStat* ch, const double* g, int n, int level, double sf) {
+    const int lane = lane_id();
+    double best = 0.0; int bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) {
+        const EdgeStat s = ch[c];
+        if (level >= 0 && s.N != level) continue;
+        const double gl = (g ? g[c] : 0.0) + sz_slog((double)s.P);
+        double sig = 0.0;
+        if (s.N >= 1) sig = sf * gumbel_q(s);
+        const double sc = gl + sig;
+        if (bi == 0x7fffffff || sc > best) { best = sc; bi = c; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        double ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+    }
+    bi = uni(bi);
+    return bi == 0x7fffffff ? -1 : bi;
+}
+
+// root selection at root-child visit t of a search of `goal` simulations (sz_set_gumbel): the level of t by sequential halving over
+// m_eff = min(max_considered, n) children, then the best child at that level; *fallback = no child was there and all were considered
+__device__ __forceinline__ int wave_select_root_gumbel(const EdgeStat* ch, const double* g, int n, int t, int goal, const sz_gumbel_options& o, bool* fallback) {
+    const int m_eff = o.max_considered < n ? o.max_considered : n;
+    const int level = sz_gumbel_level(t, goal - 1, m_eff);
+    const double sf = gumbel_sigma_factor(o, wave_max_visits(ch, n));
+    int bi = wave_gumbel_best(ch, g, n, level, sf);
+    *fallback = bi < 0;
+    if (bi < 0) bi = wave_gumbel_best(ch, g, n, -1, sf);
+    return bi;
+}
+
+// sz_play on a Gumbel board: the move (the best child among the most visited) and the completed-Q improved policy of the root's children
+// ch[0..n), n >= 1.  work[0..n) (LDS or global) carries the per-child terms between the lanes that form them and lane 0, which adds them up
+// in ascending child order.  policy_out[0..SZ_MAX_MOVES) and *vmix_out are written; returns the move (uniform).
+__device__ __forceinline__ int wave_gumbel_play(const EdgeStat* ch, const double* g, int n, const sz_gumbel_options& o, float vhat, double* work,
+                                                float* policy_out, double* vmix_out) {
+    const int lane = lane_id();
+    const int maxN = wave_max_visits(ch, n);
+    const double sf = gumbel_sigma_factor(o, maxN);
+    const int move = wave_gumbel_best(ch, g, n, maxN, sf);
+    const double v01 = 0.5 + 0.5 * (double)vhat;
+    for (int c = lane; c < n; c += 64) { const EdgeStat s = ch[c]; work[c] = s.N >= 1 ? (double)s.P * gumbel_q(s) : 0.0; }
+    __threadfence_block();
+    __syncthreads();
+    double vmix = v01;
+    if (lane == 0) {
+        int sumN = 0; double pq = 0.0, pm = 0.0;
+        for (int c = 0; c < n; c++) {
+            const EdgeStat s = ch[c];
+            sumN += s.N;
+            if (s.N >= 1) { pq = pq + work[c]; pm = pm + (double)s.P; }
+        }
+        if (sumN != 0) vmix = (v01 + (double)sumN * (pq / pm)) / (1.0 + (double)sumN);
+    }
+    vmix = uni_f64(vmix);
+    __syncthreads();
+    double zmax = 0.0; bool any = false;
+    for (int c = lane; c < n; c += 64) {
+        const EdgeStat s = ch[c];
+        const double z = sz_slog((double)s.P) + sf * (s.N >= 1 ? gumbel_q(s) : vmix);
+        work[c] = z;
+        if (!any || z > zmax) { zmax = z; any = true; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double oz = __shfl_xor(zmax, off); const int oa = __shfl_xor((int)any, off);
+        if (oa && (!any || oz > zmax)) { zmax = oz; any = true; }
+    }
+    zmax = uni_f64(zmax);
+    for (int c = lane; c < n; c += 64) work[c] = sz_sexp(work[c] - zmax);      // a lane reads back what it wrote itself
+    __threadfence_block();
+    __syncthreads();
+    double se = 0.0;
+    if (lane == 0) for (int c = 0; c < n; c++) se = se + work[c];
+    se = uni_f64(se);
+    for (int c = lane; c < SZ_MAX_CHILDREN; c += 64) policy_out[c] = c < n ? (float)(work[c] / se) : 0.0f;
+    if (lane == 0) *vmix_out = vmix;
+    return move;
 }
 
 // policy-target pruning of a finished search (sz_set_forced_playouts): vis[0..n) holds the root children's counted visits N_c on entry and the
@@ -856,10 +968,14 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // FO = ForcedOpts (sz_set_forced_playouts): on a board with ST_FORCED the selection at depth 0 is wave_select_root_forced; below the root
 // nothing changes.
 // FO = [ForcedOpts,] FpuOpts (sz_set_fpu): every selection is wave_select_child_fpu, after wave_forced_child at the root of a forced board.
+// FO = GumbelOpts[, FpuOpts] (sz_set_gumbel, VL = SOLVE = false only): the selection at depth 0 is wave_select_root_gumbel and the root's network
+// value is kept when the root is expanded; below the root nothing changes (with FpuOpts: the tree's first-play value).
 template <bool VL, bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb, FO... fo) {
     constexpr bool FORCED = is_forced<FO...>;
     constexpr bool FPU = is_fpu<FO...>;
+    constexpr bool GUMBEL = is_gumbel<FO...>;
+    static_assert(!GUMBEL || (!VL && !SOLVE && !FORCED), "sz_set_gumbel refuses leaf batching, the solver and forced playouts");
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -875,6 +991,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     unsigned long long n_expand = 0, n_term = 0, sum_depth = 0, sum_k = 0;
     unsigned long long n_stop = 0, n_proved = 0;                // solver: simulations ended on a proven non-terminal node, nodes proven by the update
     unsigned long long n_forced = 0;                            // forced playouts: root selections decided by a forced child
+    unsigned long long n_gumbel = 0, n_fallback = 0;            // Gumbel: root selections made by the rule, of them over all children
     int err = 0;
     STEP_STAMP(0);
 
@@ -969,6 +1086,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             n_edges += kept;
             (void)node;
         const double val = (double)value[lf.row];                        // node.value = value.item()
+        if constexpr (GUMBEL) { if (d == 0 && lane == 0) gumbel_opts(fo...).vhat[b] = value[lf.row]; }     // sz_set_gumbel: the root's network value
         if constexpr (VL) {                                             // its descent is no longer in flight
             for (int j = lane; j <= d; j += 64) vb.vk[(size_t)b * v.e_cap + path[j]] -= 1;
         }
@@ -996,7 +1114,21 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
         while (mn > 0 && !proven) {                                     // Node.select
             int bi;
-            if constexpr (FPU) {
+            if constexpr (GUMBEL) {
+                // sz_set_gumbel: only depth 0 changes.  One leaf per step and nothing in flight: sims - 1 root-child visits were made before this one
+                if (d == 0) {
+                    const GumbelOpts& go = gumbel_opts(fo...);
+                    bool fallback;
+                    bi = wave_select_root_gumbel(bp.es + m.first, go.g ? go.g + (size_t)b * SZ_MAX_MOVES : nullptr, mn, sims - 1, budget, go.o, &fallback);
+                    n_gumbel++; n_fallback += fallback ? 1 : 0;
+                } else if constexpr (FPU) {                             // below the root FPU acts as without the option: the tree's mode and value
+                    const sz_fpu_options& fp = fpu_opts(fo...).o;
+                    const EdgeStat ps = bp.es[cur];
+                    bi = wave_select_child_fpu<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, fp.tree_mode, fp.tree_value,
+                                                          uni(ps.N), uni_f64(ps.W), nullptr);
+                } else
+                    bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
+            } else if constexpr (FPU) {
                 // sz_set_fpu: the root's mode and value at depth 0, the tree's below; vp from the parent's own stored edge (cur; the root is edge 0)
                 const sz_fpu_options& fp = fpu_opts(fo...).o;
                 const EdgeStat ps = bp.es[cur];
@@ -1101,6 +1233,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if constexpr (VL) c->n_pend = n_pend;
         if constexpr (SOLVE) { v.sstat[(size_t)b * 2] += n_stop; v.sstat[(size_t)b * 2 + 1] += n_proved; }
         if constexpr (FORCED) forced_opts(fo...).stat[(size_t)b * 2] += n_forced;
+        if constexpr (GUMBEL) { gumbel_opts(fo...).stat[(size_t)b * 2] += n_gumbel; gumbel_opts(fo...).stat[(size_t)b * 2 + 1] += n_fallback; }
     }
 }
 
@@ -1209,10 +1342,14 @@ __device__ void wave_keep_subtree(const View& v, const BoardPtrs& bp, int b, int
 // FO = ForcedOpts (sz_set_forced_playouts): on a board with ST_FORCED the record and the move choice use the pruned counts of wave_prune; the
 // tree, and with it the subtree kept below, keeps the counted visits
 // FO ends in EndOpts (sz_set_endings): wave_ending decides on the counted visits whether the game ends here instead of a move
+// FO = GumbelOpts (sz_set_gumbel, SOLVE = false only): the move is wave_gumbel_play's, the board's uniform is not read, and the improved policy,
+// v_mix and the root's network value are left for sz_fetch_gumbel; the record keeps the counted visits
 template <bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO... fo) {
     constexpr bool FORCED = is_forced<FO...>;
     constexpr bool ENDING = is_ending<FO...>;
+    constexpr bool GUMBEL = is_gumbel<FO...>;
+    static_assert(!GUMBEL || (!SOLVE && !FORCED && !ENDING), "sz_set_gumbel refuses the solver, forced playouts and endings");
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     int* vis_lds = path + 8;
@@ -1278,6 +1415,11 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     }
     // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; idx = searchsorted(cdf, u, 'right')   (sequential f64, like numpy)
     int chosen = 0;
+    if constexpr (GUMBEL) {
+        const GumbelOpts& go = gumbel_opts(fo...);
+        chosen = wave_gumbel_play(bp.es + first, go.g ? go.g + (size_t)b * SZ_MAX_MOVES : nullptr, n, go.o, go.vhat[b], go.work + (size_t)b * SZ_MAX_MOVES,
+                                  go.policy + (size_t)b * SZ_MAX_MOVES, go.vmix + b);
+    } else
     if (lane == 0) {
         const double u = uniforms[b];
         double acc = 0.0;
@@ -1454,6 +1596,39 @@ __global__ __launch_bounds__(64) void k_debug_select_fpu(const int* offsets, con
     if (lane == 0) selected_out[cs] = bi;
 }
 
+// test hook (sz_debug_gumbel): the device functions of sz_set_gumbel on caller-supplied cases, one wave per case.  Three parts, each skipped
+// when its first array is NULL: sz_slog / sz_sexp of x[cs]; sz_gumbel_level of tnm[cs] = (t, n, m_eff); wave_select_root_gumbel and
+// wave_gumbel_play, the functions k_search_step<.., GumbelOpts> and k_play<.., GumbelOpts> call, on the case's children
+__global__ __launch_bounds__(64) void k_debug_gumbel(const double* x, double* slog_out, double* sexp_out, const int* tnm, int* level_out,
+                                                     const int* offsets, const int* vc, const double* wsum, const float* prior, const double* g,
+                                                     const int* visit, const int* goal, const float* vhat, const sz_gumbel_options* opts,
+                                                     int* selected_out, int* fallback_out, int* final_out, float* policy_out, double* vmix_out) {
+    extern __shared__ u64 lds64[];
+    EdgeStat* ch = (EdgeStat*)lds64;
+    double* work = (double*)(ch + SZ_MAX_CHILDREN);
+    float* pol = (float*)(work + SZ_MAX_CHILDREN);
+    const int cs = blockIdx.x, lane = lane_id();
+    if (x && lane == 0) { slog_out[cs] = sz_slog(x[cs]); sexp_out[cs] = sz_sexp(x[cs]); }
+    if (tnm && lane == 0) {
+        const int t = tnm[cs * 3], n = tnm[cs * 3 + 1], m = tnm[cs * 3 + 2];
+        level_out[cs] = (t >= 0 && t < n && m >= 1) ? sz_gumbel_level(t, n, m) : -1;           // the rule knows visits 0..n-1 only
+    }
+    if (!offsets) return;
+    const int lo = offsets[cs], n = offsets[cs + 1] - lo;
+    const int t = uni(visit[cs]), gl = uni(goal[cs]);
+    const sz_gumbel_options o = opts[cs];
+    if (n <= 0 || n > SZ_MAX_CHILDREN || t < 0 || t >= gl - 1 || o.max_considered < 1) { if (lane == 0) { selected_out[cs] = -1; fallback_out[cs] = 0; final_out[cs] = -1; } return; }
+    for (int c = lane; c < n; c += 64) { EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s; }
+    __syncthreads();
+    bool fallback;
+    const int bi = wave_select_root_gumbel(ch, g ? g + lo : nullptr, n, t, gl, o, &fallback);
+    double vmix;
+    const int mv = wave_gumbel_play(ch, g ? g + lo : nullptr, n, o, vhat[cs], work, pol, &vmix);
+    __syncthreads();
+    for (int c = lane; c < n; c += 64) policy_out[lo + c] = pol[c];
+    if (lane == 0) { selected_out[cs] = bi; fallback_out[cs] = fallback ? 1 : 0; final_out[cs] = mv; vmix_out[cs] = vmix; }
+}
+
 // test hook (sz_debug_endings): wave_ending, the function k_play<.., EndOpts> calls, on caller-supplied cases, one wave per case
 __global__ __launch_bounds__(64) void k_debug_endings(const int* offsets, const int* vc, const double* wsum, const int8_t* root_proven, const uint8_t* colour,
                                                       const int* ply, const uint8_t* holdout, const int* state_in, const sz_ending_options* opts,
@@ -1501,6 +1676,10 @@ struct sz_engine {
                                     //     [n_boards] and fo.stat [n_boards][2] are allocated by the first enabling call
     sz_fpu_options fpu_next;        // sz_set_fpu: what the next sz_search_begin takes up (all zero = off)
     FpuOpts fp;                     // ... and what the searches begun since run with: a mode other than SZ_FPU_REFERENCE selects the FPU instantiations
+    int gumbel_next_on;             // sz_set_gumbel: what the next sz_search_begin takes up (0 = off) ...
+    sz_gumbel_options gumbel_next; const double* gumbel_next_g;
+    int gumbel_on;                  // ... and what the searches begun since and their sz_play run with: the GUMBEL instantiations when != 0
+    GumbelOpts go;                  //     its arrays are allocated by the first enabling call (go.stat != NULL from then on)
     int end_on;                     // sz_set_endings: sz_play runs the ENDING instantiations of k_play
     EndOpts eo;                     // ... with these; its arrays are allocated by the first enabling call (eo.state != NULL from then on)
 };
@@ -1771,6 +1950,7 @@ int sz_set_root_noise(sz_engine* e, const float* gamma_dev) {
     // a reused root (sz_config.reuse_subtree) was expanded as an inner node, on un-noised priors, and is never expanded again: root noise would silently
     // apply to the first ply of a game only.  The two non-reference options are therefore mutually exclusive.
     if (gamma_dev && e->v.reuse) return SZ_ERR_STATE;
+    if (gamma_dev && e->gumbel_next_on) return SZ_ERR_STATE;               // sz_set_gumbel: Gumbel is the root's exploration
     // ... and a reuse engine that runs sz_set_search_root_noise leaves that mode through the same setter, which drops the kept subtrees
     if (e->v.reuse && e->v.root_gamma) return SZ_ERR_STATE;
     e->v.root_gamma = gamma_dev;
@@ -1780,6 +1960,7 @@ int sz_set_root_noise(sz_engine* e, const float* gamma_dev) {
 
 int sz_set_search_root_noise(sz_engine* e, const float* gamma_dev, const uint8_t* quiet, void* stream) {
     if (!e) return SZ_ERR_INVALID;
+    if (gamma_dev && e->gumbel_next_on) return SZ_ERR_STATE;               // sz_set_gumbel: Gumbel is the root's exploration
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
     bool busy = false;
@@ -1828,6 +2009,13 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
 // the k_search_step instantiation of the options in force; policy == NULL: the descent-only launch of sz_search_begin
 static void launch_step(sz_engine* e, const float* policy, const float* value, void* planes, hipStream_t s) {
     const bool fpu = e->fp.o.tree_mode != SZ_FPU_REFERENCE || e->fp.o.root_mode != SZ_FPU_REFERENCE;          // sz_set_fpu
+    if (e->gumbel_on) {                                                     // sz_set_gumbel: its setter and the others' refusals leave VL = SOLVE = FORCED = false
+        if (fpu)
+            hipLaunchKernelGGL((k_search_step<false, false, GumbelOpts, FpuOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{}, e->go, e->fp);
+        else
+            hipLaunchKernelGGL((k_search_step<false, false, GumbelOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{}, e->go);
+        return;
+    }
     with_search_options(e, [&](auto vl, auto solve, auto forced) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         if constexpr (decltype(forced)::value) {
@@ -1849,6 +2037,7 @@ int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     ENGINE_GUARD(e);
     e->fo.k = e->forced_k;                                                  // sz_set_forced_playouts takes effect here
     e->fp.o = e->fpu_next;                                                  // ... and sz_set_fpu
+    e->gumbel_on = e->gumbel_next_on; e->go.o = e->gumbel_next; e->go.g = e->gumbel_next_g;      // ... and sz_set_gumbel
     with_search_options(e, [&](auto vl, auto solve, auto forced) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         if constexpr (decltype(forced)::value)
@@ -1933,6 +2122,7 @@ int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_lo
     if (!e || !batching_args_ok(leaves_per_step, virtual_loss)) return SZ_ERR_INVALID;
     if (leaves_per_step > 1 && e->v.reuse) return SZ_ERR_INVALID;          // combining the two non-reference options is not supported
     if (leaves_per_step > 1 && e->solver) return SZ_ERR_INVALID;           // nor leaf batching with the solver
+    if (leaves_per_step > 1 && e->gumbel_next_on) return SZ_ERR_INVALID;   // nor with the Gumbel root search (sz_set_gumbel)
     ENGINE_GUARD(e);
     return set_options(e, leaves_per_step, virtual_loss, e->solver, (hipStream_t)stream);
 }
@@ -1940,12 +2130,14 @@ int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_lo
 int sz_set_solver(sz_engine* e, int32_t enable, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     if (enable && (e->v.reuse || e->vb.L > 1)) return SZ_ERR_INVALID;      // not combined with subtree reuse or leaf batching
+    if (enable && e->gumbel_next_on) return SZ_ERR_INVALID;                // nor with the Gumbel root search (sz_set_gumbel)
     ENGINE_GUARD(e);
     return set_options(e, e->vb.L, e->vb.lam, enable ? 1 : 0, (hipStream_t)stream);
 }
 
 int sz_set_search_options(sz_engine* e, const sz_search_options* opt, void* stream) {
     if (!e || !opt || !batching_args_ok(opt->leaves_per_step, opt->virtual_loss)) return SZ_ERR_INVALID;
+    if ((opt->leaves_per_step > 1 || opt->solver) && e->gumbel_next_on) return SZ_ERR_INVALID;      // sz_set_gumbel: neither is combined with it
     ENGINE_GUARD(e);
     const int solver = opt->solver ? 1 : 0;
     // a kept subtree built under other settings has no `complete` bits, or its in-flight counts were never written: start fresh
@@ -1983,6 +2175,7 @@ int sz_solver_stats(sz_engine* e, uint64_t out[2], void* stream) {
 int sz_set_forced_playouts(sz_engine* e, float k, const uint8_t* boards, void* stream) {
     if (!e || !(k >= 0.0f) || !std::isfinite(k)) return SZ_ERR_INVALID;
     if (k > 0.0f && !e->v.learning) return SZ_ERR_INVALID;                  // an exploration option of self-play, like root noise
+    if (k > 0.0f && e->gumbel_next_on) return SZ_ERR_INVALID;               // not combined with the Gumbel root search (sz_set_gumbel)
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
     bool busy = false;
@@ -2030,6 +2223,65 @@ int sz_set_fpu(sz_engine* e, const sz_fpu_options* opt, void* stream) {
     return SZ_OK;
 }
 
+int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_dev, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (opt) {
+        if (opt->max_considered < 1 || opt->max_considered > SZ_MAX_MOVES) return SZ_ERR_INVALID;
+        if (!std::isfinite(opt->c_visit) || opt->c_visit < 0.0f || !std::isfinite(opt->c_scale) || opt->c_scale < 0.0f) return SZ_ERR_INVALID;
+        // each combination is a follow-up: a kept subtree's root was not expanded by this search, leaf batching has visits in flight, the
+        // solver and forced playouts select at the root themselves, the ending rules read the most visited move
+        if (e->v.reuse || e->vb.L > 1 || e->solver || e->forced_k > 0.0f || e->end_on) return SZ_ERR_INVALID;
+    }
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    bool busy = false;
+    int rc = search_in_progress(e, s, &busy);
+    if (rc) return rc;
+    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if (!opt) { e->gumbel_next_on = 0; e->gumbel_next_g = nullptr; return SZ_OK; }
+    if (e->v.root_gamma) return SZ_ERR_STATE;                               // root noise is on: Gumbel is the root's exploration
+    if (!e->go.stat) {                                                      // the first enabling call: the per-board outputs and the counters
+        const size_t B = e->v.B;
+        float* vh = nullptr; float* po = nullptr; double* vm = nullptr; double* wk = nullptr; unsigned long long* st = nullptr;
+        if ((rc = dalloc(e, &vh, B)) || (rc = dalloc(e, &po, B * SZ_MAX_MOVES)) || (rc = dalloc(e, &vm, B)) || (rc = dalloc(e, &wk, B * SZ_MAX_MOVES)) ||
+            (rc = dalloc(e, &st, B * 2))) return rc;
+        HIPCHK(hipMemsetAsync(vh, 0, B * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(po, 0, B * SZ_MAX_MOVES * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(vm, 0, B * sizeof(double), s));
+        HIPCHK(hipMemsetAsync(st, 0, B * 2 * sizeof(unsigned long long), s));
+        HIPCHK(hipStreamSynchronize(s));
+        e->go.vhat = vh; e->go.policy = po; e->go.vmix = vm; e->go.work = wk; e->go.stat = st;
+    }
+    e->gumbel_next = *opt; e->gumbel_next_g = g_dev; e->gumbel_next_on = 1;
+    return SZ_OK;
+}
+
+int sz_fetch_gumbel(sz_engine* e, float* policy_target, double* v_mix, float* root_value, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (!e->go.stat) return SZ_ERR_STATE;                                   // the option was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = e->v.B;
+    if (policy_target) HIPCHK(hipMemcpyAsync(policy_target, e->go.policy, B * SZ_MAX_MOVES * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (v_mix) HIPCHK(hipMemcpyAsync(v_mix, e->go.vmix, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (root_value) HIPCHK(hipMemcpyAsync(root_value, e->go.vhat, B * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SZ_OK;
+}
+
+int sz_gumbel_stats(sz_engine* e, uint64_t out[2], void* stream) {
+    if (!e || !out) return SZ_ERR_INVALID;
+    out[0] = out[1] = 0;
+    if (!e->go.stat) return SZ_OK;                                          // the option was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<unsigned long long> h((size_t)e->v.B * 2);
+    HIPCHK(hipMemcpyAsync(h.data(), e->go.stat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < (size_t)e->v.B; b++) { out[0] += h[2 * b]; out[1] += h[2 * b + 1]; }
+    return SZ_OK;
+}
+
 int sz_forced_stats(sz_engine* e, uint64_t out[2], void* stream) {
     if (!e || !out) return SZ_ERR_INVALID;
     out[0] = out[1] = 0;
@@ -2050,6 +2302,7 @@ int sz_set_endings(sz_engine* e, const sz_ending_options* opt, const uint8_t* ho
         if (!std::isfinite(opt->draw_value) || opt->draw_value < 0.0f || opt->draw_value > 1.0f) return SZ_ERR_INVALID;
         if (opt->resign_patience < 0 || opt->resign_patience > END_STREAK_MAX || opt->draw_patience < 0 || opt->draw_patience > END_STREAK_MAX) return SZ_ERR_INVALID;
         if (opt->resign_min_ply < 0 || opt->draw_min_ply < 0) return SZ_ERR_INVALID;
+        if (e->gumbel_next_on) return SZ_ERR_INVALID;                       // not combined with the Gumbel root search (sz_set_gumbel)
     }
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
@@ -2160,6 +2413,11 @@ int sz_root_children(sz_engine* e, int32_t* action_dev, int32_t* visits_dev, int
 int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
+    if (e->gumbel_on) {                                                     // sz_set_gumbel: the search that ended ran under it
+        hipLaunchKernelGGL((k_play<false, GumbelOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->go);
+        HIPCHK(hipGetLastError());
+        return SZ_OK;
+    }
     with_search_options(e, [&](auto, auto solve, auto forced) {
         constexpr bool SOLVE = decltype(solve)::value;
         if (e->end_on) {                                                    // sz_set_endings: the ENDING instantiations
@@ -2326,6 +2584,23 @@ int sz_debug_select_fpu(const int32_t* offsets_dev, const int32_t* vc_dev, const
     hipLaunchKernelGGL(k_debug_select_fpu, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(EdgeMeta) + sizeof(int)), (hipStream_t)stream,
                        offsets_dev, vc_dev, inflight_dev, value_sum_dev, prior_dev, proven_dev, parent_visits_dev, parent_n_dev, parent_w_dev, c_dev, is_root_dev,
                        opts_dev, virtual_loss, ucb_out_dev, selected_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_gumbel(const double* x_dev, double* slog_out_dev, double* sexp_out_dev, const int32_t* tnm_dev, int32_t* level_out_dev,
+                    const int32_t* offsets_dev, const int32_t* vc_dev, const double* value_sum_dev, const float* prior_dev, const double* g_dev,
+                    const int32_t* visit_dev, const int32_t* goal_dev, const float* root_value_dev, const sz_gumbel_options* opts_dev,
+                    int32_t* selected_out_dev, int32_t* fallback_out_dev, int32_t* final_out_dev, float* policy_out_dev, double* v_mix_out_dev,
+                    int32_t n_cases, void* stream) {
+    if (n_cases <= 0 || (!x_dev && !tnm_dev && !offsets_dev)) return SZ_ERR_INVALID;
+    if (x_dev && (!slog_out_dev || !sexp_out_dev)) return SZ_ERR_INVALID;
+    if (tnm_dev && !level_out_dev) return SZ_ERR_INVALID;
+    if (offsets_dev && (!vc_dev || !value_sum_dev || !prior_dev || !visit_dev || !goal_dev || !root_value_dev || !opts_dev || !selected_out_dev || !fallback_out_dev ||
+                        !final_out_dev || !policy_out_dev || !v_mix_out_dev)) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_gumbel, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(double) + sizeof(float)), (hipStream_t)stream,
+                       x_dev, slog_out_dev, sexp_out_dev, tnm_dev, level_out_dev, offsets_dev, vc_dev, value_sum_dev, prior_dev, g_dev, visit_dev, goal_dev,
+                       root_value_dev, opts_dev, selected_out_dev, fallback_out_dev, final_out_dev, policy_out_dev, v_mix_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

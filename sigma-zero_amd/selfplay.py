@@ -182,6 +182,42 @@ def fpu_options_of(args):
     return tuple(out)
 
 
+GUMBEL_KEYS = ("m", "c_visit", "c_scale")
+
+
+def gumbel_options_of(args):
+    """The Gumbel root search options of args, checked: (m, c_visit, c_scale) with the constants rounded to f32, or None when the key is
+    absent.  NON-REFERENCE, default off.
+
+    args["gumbel"] = {"m": int, "c_visit": x, "c_scale": y} (defaults 16 / 50 / 1) switches the root of every search from PUCT with root noise
+    to Gumbel AlphaZero's rule (sz_set_gumbel): m root moves are sampled without replacement by Gumbel-top-k, the simulations are spent on
+    them by sequential halving, play() takes the best of the most visited moves, and the policy target is the completed-Q improved policy
+    (fetch_gumbel) instead of the visit fractions.  Below the root nothing changes.  Refused with a reuse_subtree engine, leaves_per_step > 1,
+    the solver, forced playouts, endings and root_dirichlet_alpha: each combination is a follow-up.  Checked in this order: the dict and its
+    keys, m, c_visit, c_scale, the combinations.  Its effect on playing strength is unmeasured."""
+    opt = args.get("gumbel")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(GUMBEL_KEYS):
+        raise ValueError("args['gumbel'] must be a dict with keys from %s, got %r" % (GUMBEL_KEYS, opt))
+    m = opt.get("m", 16)
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or not 1 <= m <= N.SZ_MAX_MOVES:
+        raise ValueError("args['gumbel']['m'] must be an integer in 1..%d, got %r" % (N.SZ_MAX_MOVES, m))
+    out = [int(m)]
+    for key, default in (("c_visit", 50.0), ("c_scale", 1.0)):
+        x = opt.get(key, default)
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or \
+                not (math.isfinite(x) and math.isfinite(float(np.float32(x))) and x >= 0):          # NaN fails the comparison
+            raise ValueError("args['gumbel'][%r] must be a finite number >= 0, got %r" % (key, x))
+        out.append(float(np.float32(x)))
+    for key, on in (("reuse_subtree", args.get("reuse_subtree", False)), ("leaves_per_step", args.get("leaves_per_step", 1) != 1),
+                    ("solver", args.get("solver", False)), ("forced_playouts", args.get("forced_playouts") is not None),
+                    ("endings", args.get("endings") is not None), ("root_dirichlet_alpha", args.get("root_dirichlet_alpha") is not None)):
+        if on:
+            raise ValueError("args['gumbel'] and args[%r] exclude each other" % key)
+    return tuple(out)
+
+
 ENDING_KEYS = ("resign_value", "resign_patience", "resign_min_ply", "draw_value", "draw_patience", "draw_min_ply", "proven", "holdout")
 ENDING_KINDS = {N.SZ_END_RESIGN: "resign", N.SZ_END_DRAW: "draw_adjudicated", N.SZ_END_PROVEN: "proven"}
 
@@ -272,6 +308,9 @@ class SelfPlayEngine:
             raise ValueError("args['forced_playouts'] needs learning=True: it is an exploration option of self-play, like root noise")
         # NON-REFERENCE option (default off): first-play urgency for unvisited children, see fpu_options_of
         self.fpu = fpu_options_of(self.args)
+        # NON-REFERENCE option (default off): Gumbel root search with sequential halving and the completed-Q policy target, see gumbel_options_of
+        self.gumbel = gumbel_options_of(self.args)
+        self._gumbel_g = None         # the device copy of the Gumbel draws in force (set_gumbel)
         # NON-REFERENCE option (default off): resignation and adjudicated game endings, see ending_options_of
         self.endings = ending_options_of(self.args)
         self.quiet = None             # boards whose next searches get no root noise (set_quiet; visit_targets mode)
@@ -326,7 +365,9 @@ class SelfPlayEngine:
             self.set_forced_playouts(self.forced_k)
         if self.fpu is not None:
             self.set_fpu(self.fpu)
-        if self.endings is not None:   # no holdout board until set_endings says otherwise
+        if self.gumbel is not None:    # g = None (a deterministic search) until set_gumbel hands over draws
+            self.set_gumbel(self.gumbel)
+        if self.endings is not None:  # no holdout board until set_endings says otherwise
             self.set_endings(self.endings)
 
     def close(self):
@@ -445,6 +486,36 @@ class SelfPlayEngine:
         o = None if opts is None else N.sz_fpu_options(int(opts[0]), float(opts[1]), int(opts[2]), float(opts[3]))
         N.check(N.lib().sz_set_fpu(self._e, None if o is None else C.byref(o), self._stream()), "sz_set_fpu")
         self.fpu = None if opts is None else tuple(opts)
+
+    def set_gumbel(self, opts, g=None):
+        """Gumbel root search (sz_set_gumbel, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (m, c_visit, c_scale) as
+        gumbel_options_of returns it, or None = off.  g: [B, SZ_MAX_MOVES] Gumbel(0,1) draws by root child (a float64 tensor or array; the
+        engine keeps its device copy alive and unchanged until the next call), None = all zeros, a deterministic search.  Between searches
+        only; a refused call changes nothing."""
+        o = None if opts is None else N.sz_gumbel_options(int(opts[0]), float(opts[1]), float(opts[2]))
+        gd = None
+        if o is not None and g is not None:
+            gd = torch.as_tensor(np.asarray(g, dtype=np.float64) if not torch.is_tensor(g) else g).to(self.device, torch.float64).contiguous()
+            if tuple(gd.shape) != (self.B, N.SZ_MAX_MOVES):
+                raise ValueError("set_gumbel: g must be [%d, %d], got %r" % (self.B, N.SZ_MAX_MOVES, tuple(gd.shape)))
+        N.check(N.lib().sz_set_gumbel(self._e, None if o is None else C.byref(o), _ptr(gd), self._stream()), "sz_set_gumbel")
+        # the search that ended last still reads its own draws in play(): the previous copy stays alive for one more call
+        self.gumbel, self._gumbel_g, self._gumbel_g_prev = (None if opts is None else tuple(opts)), gd, self._gumbel_g
+
+    def fetch_gumbel(self):
+        """sz_fetch_gumbel after play(): dict of policy [B, SZ_MAX_MOVES] f32 (the improved policy by root child, in fetch_ply()'s action
+        order), v_mix [B] f64 and root_value [B] f32; rows are valid where fetch_ply()'s active is 1"""
+        B = self.B
+        out = dict(policy=np.zeros((B, N.SZ_MAX_MOVES), np.float32), v_mix=np.zeros(B, np.float64), root_value=np.zeros(B, np.float32))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        N.check(N.lib().sz_fetch_gumbel(self._e, p(out["policy"]), p(out["v_mix"]), p(out["root_value"]), self._stream()), "sz_fetch_gumbel")
+        return out
+
+    def gumbel_stats(self):
+        """(root selections made by the Gumbel rule, those of them that found no child at the level), all boards, cumulative (sz_gumbel_stats)"""
+        out = (C.c_uint64 * 2)()
+        N.check(N.lib().sz_gumbel_stats(self._e, out, self._stream()), "sz_gumbel_stats")
+        return int(out[0]), int(out[1])
 
     def set_endings(self, opts, holdout=None):
         """Resignation and adjudicated game endings (sz_set_endings, a NON-REFERENCE option) from the next play() on, until changed.  opts: a

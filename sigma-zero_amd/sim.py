@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, ENDING_KINDS
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, ENDING_KINDS
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -71,7 +71,7 @@ def playout_cap_of(args):
 
 
 def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, learning=True, planes_dtype=None, max_plies=100000,
-               verbose=False, n_boards=None, compact=True, stats=None, full_search=None, root_gamma=None, holdout=None):
+               verbose=False, n_boards=None, compact=True, stats=None, full_search=None, root_gamma=None, holdout=None, gumbel_noise=None):
     """Plays n_games games to the end and returns a list of per-game history dicts (sim.py:38-43 layout), game g at index g.
 
     The games run concurrently on `n_boards` board slots of one engine (default: one slot per game).  A slot whose game ends is
@@ -113,6 +113,13 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     holdout flags of the games it starts.  The extra per-ply host copy (sz_fetch_endings) happens in this mode only.  Strength effect unmeasured.
     args["fpu"] = {...} (NON-REFERENCE, selfplay.fpu_options_of): first-play urgency, what selection takes an unvisited child to be worth
     (sz_set_fpu), one setting for the root and one below it, on fast and full plies alike; the engine applies it.  Strength effect unmeasured.
+    args["gumbel"] = {"m": m, "c_visit": x, "c_scale": y} (NON-REFERENCE, selfplay.gumbel_options_of): the Gumbel root search (sz_set_gumbel), on fast
+    and full plies alike.  The move is the search's own choice (`uniforms` is still drawn as always and not read by the engine) and a sample's
+    'actions' dict holds the completed-Q improved policy as Python floats instead of visit fractions.  With `learning` the Gumbel(0,1) draws
+    g = -log(-log(u)) come per board and ply from a numpy Generator of its own; without it g is NULL, a deterministic search for match play.
+    stats gets 'gumbel_fallbacks' (sz_gumbel_stats: root selections that found no child at their level, 0).  Strength effect unmeasured.
+    gumbel_noise(game, ply) -> 218 floats: the Gumbel(0,1) draws of that game's root at that ply by root child, like `uniforms`; replaces
+      the default above, with and without `learning`.
     holdout(game) -> bool: whether a game is a holdout game, like `uniforms`.  Default: a numpy Generator of its own, one draw per game in game
       order when the game starts, true with probability args["endings"]["holdout"].
     full_search(game, ply) -> bool: the full / fast decision, like `uniforms`.  Default: a numpy Generator of its own, drawn per ply for every
@@ -126,6 +133,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     if forced_k is not None and not learning:
         raise ValueError("args['forced_playouts'] needs learning=True")
     end_opts = ending_options_of(args)
+    gum = gumbel_options_of(args)
+    if gumbel_noise is not None and gum is None:
+        raise ValueError("gumbel_noise needs args['gumbel']")
     if holdout is not None and end_opts is None:
         raise ValueError("holdout needs args['endings']")
     if full_search is not None and pcap is None:
@@ -154,12 +164,13 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     games = [dict(states=[], actions=[], rewards=[], colours=[], result=None, packed_states=[], sample_plies=[], chosen_actions=[], termination=None, holdout=False, would_end=None) for _ in range(n_games)]   # packed_states: the (119,8) uint8 form (train_RL.py:42)
     cap_rng = np.random.default_rng() if pcap is not None and full_search is None else None
     holdout_rng = np.random.default_rng() if end_opts is not None and holdout is None else None
+    gumbel_rng = np.random.default_rng() if gum is not None and gumbel_noise is None and learning else None
     slot_holdout = np.zeros(B, dtype=np.uint8)            # the holdout flag of the game on each board slot
     slot_game = np.full(B, -1, dtype=np.int64)            # game running on each board slot, -1 = none
     plies = np.zeros(n_games, dtype=np.int64)             # plies played so far per game
     next_game = 0
     work = dict(sims=0, nn_rows=0, plies=0, full_plies=0, fast_plies=0, searches_without_network=0, forced_selections=0, pruned_visits=0,
-                resigned=0, adjudicated_draws=0, adjudicated_proven=0, holdout_games=0, holdout_marks=0)
+                resigned=0, adjudicated_draws=0, adjudicated_proven=0, holdout_games=0, holdout_marks=0, gumbel_fallbacks=0)
 
     def refill(slots):
         """start the next waiting games on these slots (ChessTensor.__init__/start_board for each); the rest go dark"""
@@ -183,7 +194,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
                 eng.set_endings(end_opts, slot_holdout)    # the new games' holdout flags; streaks and marks of the games that go on stay
         eng.set_active((slot_game >= 0).astype(np.uint8))
 
-    def absorb(rec, game_of_slot, sampled, ply_of_slot):
+    def absorb(rec, game_of_slot, sampled, ply_of_slot, improved=None):
         """host-side bookkeeping of one ply's records (sim.py:71-73); runs while the GPU searches the next ply"""
         slots = np.nonzero((game_of_slot >= 0) & rec["active"].astype(bool))[0]
         for s_ in slots.tolist():                          # the move played, sample or not: chosen_actions has one action index per ply of the game
@@ -204,7 +215,10 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             moves = _moves_for_record(rec["action"][s_, :k], white, rec["packed"][s_])
             games[g]["states"].append(states[i])
             games[g]["packed_states"].append(rec["packed"][s_])
-            games[g]["actions"].append(dict(zip(moves, (vis / int(vis.sum())).tolist())))      # int / int in float64: the reference's v / sum_values
+            if improved is not None:                       # args["gumbel"]: the completed-Q improved policy, f32 values as Python floats
+                games[g]["actions"].append(dict(zip(moves, improved[s_, :k].astype(np.float64).tolist())))
+            else:
+                games[g]["actions"].append(dict(zip(moves, (vis / int(vis.sum())).tolist())))      # int / int in float64: the reference's v / sum_values
             games[g]["colours"].append(white)
             games[g]["sample_plies"].append(int(ply_of_slot[s_]))
             if rec["game_over"][s_]:
@@ -241,6 +255,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
             for s_ in running:
                 gam[s_] = np.asarray(root_gamma(int(slot_game[s_]), int(plies[slot_game[s_]])), dtype=np.float32)
             eng.next_gamma = torch.from_numpy(gam).to(dev)
+        if gumbel_noise is not None or gumbel_rng is not None:
+            gn = np.zeros((B, 218), dtype=np.float64)
+            for s_ in running[np.argsort(slot_game[running], kind="stable")]:      # draws in game order
+                g = int(slot_game[s_])
+                gn[s_] = np.asarray(gumbel_noise(g, int(plies[g])), dtype=np.float64) if gumbel_noise is not None else -np.log(-np.log(gumbel_rng.random(218)))
+            eng.set_gumbel(gum, gn)
         eng.search()                                       # enqueues num_searches x (network + tree step); returns before the GPU is done
         t0 = lap("enqueue_search", t0)
         if pending is not None:
@@ -256,11 +276,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         eng.play(u)
         rec = eng.fetch_ply()
         ends = eng.fetch_endings() if end_opts is not None else None
+        improved = eng.fetch_gumbel()["policy"] if gum is not None else None
         if eng.stats()["boards_error"]:
             eng.check_errors()
         t0 = lap("play_fetch", t0)
         ply_of_slot = np.where(slot_game >= 0, plies[np.maximum(slot_game, 0)], -1)
-        pending = (rec, slot_game.copy(), sampled, ply_of_slot)
+        pending = (rec, slot_game.copy(), sampled, ply_of_slot, improved)
         n_full = int(sampled[running].sum())
         if vt:                                             # the goals actually made: a kept root's visits count towards its target
             work["sims"] += int(eng.last_goals[running].sum()) if eng.last_goals is not None else 0
@@ -290,6 +311,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         work["forced_selections"], work["pruned_visits"] = eng.forced_stats()
     if end_opts is not None:
         work["resigned"], work["adjudicated_draws"], work["adjudicated_proven"], work["holdout_marks"] = eng.ending_stats()
+    if gum is not None:
+        work["gumbel_fallbacks"] = eng.gumbel_stats()[1]
     eng.close()
     if stats is not None:
         stats.update(work)

@@ -462,7 +462,7 @@ def write_step_log(path, epoch, hist, lr_scheduler, append=True):
 
 def selfplay_args_of(a):
     """the self-play `args` dict of main()'s parsed flags `a`; nothing is checked here: the engine's option readers (selfplay.search_options_of,
-    visit_target_options_of, forced_playout_options_of, ending_options_of, sim.playout_cap_of) refuse what does not go together"""
+    visit_target_options_of, forced_playout_options_of, gumbel_options_of, ending_options_of, sim.playout_cap_of) refuse what does not go together"""
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
@@ -480,6 +480,8 @@ def selfplay_args_of(a):
         args["quiet_fast_plies"] = True
     if a.forced_playouts:
         args["forced_playouts"] = a.forced_playouts
+    if a.gumbel:
+        args["gumbel"] = {"m": a.gumbel, "c_visit": a.gumbel_c_visit, "c_scale": a.gumbel_c_scale}
     if a.resign_patience or a.draw_patience or a.adjudicate_proven:
         end = {"resign_patience": a.resign_patience, "resign_min_ply": a.resign_min_ply, "draw_patience": a.draw_patience, "draw_min_ply": a.draw_min_ply,
                "proven": bool(a.adjudicate_proven), "holdout": a.ending_holdout}
@@ -540,6 +542,12 @@ def flag_parser():
     ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
                     help="NON-REFERENCE: forced playouts at the root, n < sqrt(K * P * (N_root - 1)), and policy-target pruning of the recorded visits "
                          "(KataGo: K = 2; 0 = off); with --playout-cap-fast on full-search plies only (args['forced_playouts']); strength effect unmeasured")
+    ap.add_argument("--gumbel", type=int, default=0, metavar="M",
+                    help="NON-REFERENCE: Gumbel root search (args['gumbel'], sz_set_gumbel): M root moves sampled by Gumbel-top-k, sequential halving, "
+                         "and the completed-Q improved policy as the training target (the loss takes fractional targets); 0 = off; not combined with "
+                         "--reuse-subtree, leaf batching, the solver, --forced-playouts, the ending rules or --root-dirichlet-alpha; strength effect unmeasured")
+    ap.add_argument("--gumbel-c-visit", type=float, default=50.0, metavar="X", help="with --gumbel: c_visit of sigma(q) = (c_visit + max N) * c_scale * q")
+    ap.add_argument("--gumbel-c-scale", type=float, default=1.0, metavar="Y", help="with --gumbel: c_scale of sigma(q)")
     ap.add_argument("--resign-value", type=float, default=None, metavar="V",
                     help="NON-REFERENCE: a game is resigned when the mover's most visited move had an expected outcome <= V (in [-1, 1]) in "
                          "--resign-patience of the mover's searches in a row (args['endings'], sz_set_endings); strength effect unmeasured")
@@ -621,6 +629,7 @@ def main(argv=None):
                                         "quiet_fast_plies": bool(args.get("quiet_fast_plies", False)),
                                         "forced_playouts": args.get("forced_playouts"), "forced_selections": sp_stats.get("forced_selections"),
                                         "pruned_visits": sp_stats.get("pruned_visits"),
+                                        "gumbel": args.get("gumbel"), "gumbel_fallbacks": sp_stats.get("gumbel_fallbacks"),
                                         "endings": args.get("endings"), "ending_report": ending_report(games) if args.get("endings") else None,
                                         "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
