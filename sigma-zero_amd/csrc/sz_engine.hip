@@ -29,6 +29,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <cmath>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 #include "sz_chess.h"
@@ -135,30 +136,79 @@ __device__ __forceinline__ float ucb_value(int vc, double wsum, float prior, flo
     return q + u;
 }
 
+// The NON-REFERENCE options reach a kernel as a pack FO... of option structs (ForcedOpts, FpuOpts, GumbelOpts, EndOpts below), each one more, last
+// argument: an option's instantiation is the one that takes its struct, k_search_step<VL, SOLVE, ForcedOpts> against k_search_step<VL, SOLVE>,
+// whose argument list, and with it every line of its code, is what it was before the option existed.  has_opt: T is in the pack; opt_of: its member.
+template <typename T, typename... FO> constexpr bool has_opt = (std::is_same_v<FO, T> || ...);
+template <typename T, typename F, typename... R>
+__device__ __forceinline__ const T& opt_of(const F& f, const R&... r) {
+    if constexpr (std::is_same_v<T, F>) return f; else return opt_of<T>(r...);
+}
+
+// SOLVE (sz_set_solver): selection runs over the children that are not proven WIN (a child whose side to move wins is a refuted move); over all
+// of them when every child is WIN.  wave_skip_wins: some child is not WIN, so the WIN children are skipped (uniform; false without SOLVE).
+template <bool SOLVE>
+__device__ __forceinline__ bool wave_skip_wins(const EdgeMeta* cm, int n) {
+    bool skip_wins = false;
+    if constexpr (SOLVE) {
+        bool open = false;
+        for (int c = lane_id(); c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
+        skip_wins = __ballot(open) != 0;
+    }
+    return skip_wins;
+}
+
 // Node.select (mctsnode.py:23-31): argmax of get_ucb over the n contiguous children, first maximum wins (torch.argmax).
 // Lanes = children; wave64 xor-butterfly with lowest-index tie-break.  ucb_out (optional, test hook) receives every child's value.
 // VL (sz_set_leaf_batching): child c scores as if its k[c] descents in flight had each returned a loss for the parent, vc = N + k,
 // wsum = W + lam*k (f64); parentVC = N + k of the parent (N alone without VL).  k == 0 everywhere gives the VL = false result exactly.
-// SOLVE (sz_set_solver): the arg-max runs over the children that are not proven WIN (a child whose side to move wins is a refuted move);
-// over all of them when every child is WIN.  ucb_value, its operation order and the tie-break are the same in all four instantiations.
-template <bool VL, bool SOLVE>
-__device__ __forceinline__ int wave_select_child(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam, float* ucb_out) {
+// SOLVE: wave_skip_wins.  ucb_value, its operation order and the tie-break are the same in all instantiations.
+// FPU (sz_set_fpu; include/sigmazero.h is the rule): the score of an unvisited child (n_c = N_c + k_c == 0) is replaced by q0 + ucb_u(0, P_c, sq,
+// c_puct), q0 = (v0 + 1) / 2.  mode / value: the site's (the root's at depth 0, the tree's below; uniform); pN / pW: the parent's own stored
+// edge; all four are unread without FPU.  v0 and with it q0 are formed once per parent and are the same in every lane: the xor butterfly leaves
+// one sum in all 64 (f32 addition commutes), and it is read back through readfirstlane so that the compiler knows.  mode == SZ_FPU_REFERENCE
+// scores every child as without FPU.  With FPU ucb_out receives skipped WIN children too; without, the skip comes before the child is read.
+template <bool VL, bool SOLVE, bool FPU>
+__device__ __forceinline__ int wave_select_child(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam,
+                                                 int mode, float value, int pN, double pW, float* ucb_out) {
     const int lane = lane_id();
     const float sq = (float)sqrt((double)parentVC);                     // math.sqrt(self.visit_count) in double, then a float32 operand
-    bool skip_wins = false;
-    if constexpr (SOLVE) {
-        bool open = false;
-        for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
-        skip_wins = __ballot(open) != 0;
+    const bool skip_wins = wave_skip_wins<SOLVE>(cm, n);
+    float q0 = 0.5f;
+    if constexpr (FPU) {
+        if (mode != SZ_FPU_REFERENCE) {
+            float v0 = value;
+            if (mode == SZ_FPU_REDUCTION) {
+                float part = 0.f;                                        // the prior mass of the visited children, a label does not matter
+                for (int c = lane; c < n; c += 64) {
+                    const EdgeStat s = ch[c];
+                    int nc = s.N;
+                    if constexpr (VL) nc += k[c];
+                    if (nc >= 1) part = part + s.P;
+                }
+                const float mass = __int_as_float(uni(__float_as_int(wave_sum_butterfly(part))));
+                const float vp = (float)pW / ((float)pN + 1e-6f);
+                v0 = vp - (value * (float)sqrt((double)mass));
+            }
+            if (!(v0 >= -1.0f)) v0 = -1.0f;
+            if (v0 > 1.0f) v0 = 1.0f;
+            q0 = (v0 + 1.0f) / 2.0f;
+        }
     }
     float best = 0.f; int bi = 0x7fffffff;
     for (int c = lane; c < n; c += 64) {
-        if constexpr (SOLVE) { if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue; }
-        EdgeStat s = ch[c];
+        if constexpr (SOLVE && !FPU) { if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue; }
+        const EdgeStat s = ch[c];
+        int kc = 0;
+        if constexpr (VL) kc = k[c];
+        const int nc = s.N + kc;
         float u;
-        if constexpr (VL) { const int kc = k[c]; u = ucb_value(s.N + kc, s.W + (double)lam * (double)kc, s.P, sq, c_puct); }
-        else u = ucb_value(s.N, s.W, s.P, sq, c_puct);
+        if (!FPU || nc >= 1 || mode == SZ_FPU_REFERENCE) {
+            if constexpr (VL) u = ucb_value(nc, s.W + (double)lam * (double)kc, s.P, sq, c_puct);
+            else u = ucb_value(s.N, s.W, s.P, sq, c_puct);
+        } else u = q0 + ucb_u(0, s.P, sq, c_puct);
         if (ucb_out) ucb_out[c] = u;
+        if constexpr (SOLVE && FPU) { if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue; }
         if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
     }
     for (int off = 32; off >= 1; off >>= 1) {
@@ -174,9 +224,6 @@ struct ForcedOpts {
     const uint8_t* boards;      // [B] != 0: the board's next search is forced and pruned; k_search_begin latches it into ST_FORCED
     unsigned long long* stat;   // [B][2] root selections decided by a forced child, visits pruning took out of the records
 };
-// The FORCED instantiation of a kernel is the one that takes a ForcedOpts as one more, last argument: k_search_step<VL, SOLVE, ForcedOpts>
-// against k_search_step<VL, SOLVE>, whose argument list, and with it every line of its code, is what it was before the option existed
-template <typename... FO> constexpr bool is_forced = (std::is_same_v<FO, ForcedOpts> || ...);
 
 // NON-REFERENCE option (sz_set_endings): the per-board state of the ending rules, reset when a game starts on the board ...
 struct EndState { int rs[2]; int ds; int would_ply; int would_kind; int would_colour; };     // resign streak per colour, draw streak, the holdout mark (would_ply -1 = none)
@@ -191,24 +238,14 @@ struct EndOpts {
     double* mval;               // [B] ... and the mover's value m it saw (NaN likewise)
     unsigned long long* stat;   // [B][4] resignations, adjudicated draws, proven endings, holdout marks
 };
-template <typename... FO> constexpr bool is_ending = (std::is_same_v<FO, EndOpts> || ...);
-__device__ __forceinline__ const ForcedOpts& forced_opts(const ForcedOpts& fo) { return fo; }
-__device__ __forceinline__ const ForcedOpts& forced_opts(const ForcedOpts& fo, const EndOpts&) { return fo; }
-__device__ __forceinline__ const EndOpts& end_opts(const EndOpts& eo) { return eo; }
-__device__ __forceinline__ const EndOpts& end_opts(const ForcedOpts&, const EndOpts& eo) { return eo; }
 
 // forced playouts at a root (sz_set_forced_playouts): child c with n_c = N_c + k_c >= 1 visits is forced while n_c < sqrt((k * P_c) * T) in f64,
-// T = parentVC - 1.  Returns the forced child with the lowest index, -1 when none is forced.  Lanes = children as in wave_select_child; with
-// SOLVE a child proven WIN is not forced whenever the arg-max skips WIN children.  A NaN or negative product forces nothing.
+// T = parentVC - 1.  Returns the forced child with the lowest index, -1 when none is forced: the arg-max decides as everywhere.  Lanes = children
+// as in wave_select_child; with SOLVE a child proven WIN is not forced whenever the arg-max skips WIN children.  A NaN or negative product forces nothing.
 template <bool VL, bool SOLVE>
 __device__ __forceinline__ int wave_forced_child(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float fk) {
     const int lane = lane_id();
-    bool skip_wins = false;
-    if constexpr (SOLVE) {
-        bool open = false;
-        for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
-        skip_wins = __ballot(open) != 0;
-    }
+    const bool skip_wins = wave_skip_wins<SOLVE>(cm, n);
     const double T = (double)(parentVC - 1);
     int fi = 0x7fffffff;
     for (int c = lane; c < n && fi == 0x7fffffff; c += 64) {
@@ -223,81 +260,20 @@ __device__ __forceinline__ int wave_forced_child(const EdgeStat* ch, const EdgeM
     return fi == 0x7fffffff ? -1 : fi;
 }
 
-// selection at the root of a forced board: the lowest forced child if there is one (*forced = true), else wave_select_child as everywhere
+// selection at the root of a forced board without first-play urgency: the lowest forced child if there is one (*forced = true), else the arg-max
+// as everywhere.  With FPU k_search_step composes the two itself.
 template <bool VL, bool SOLVE>
 __device__ __forceinline__ int wave_select_root_forced(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam, float fk,
                                                        bool* forced) {
     int bi = wave_forced_child<VL, SOLVE>(ch, cm, k, n, parentVC, fk);
     *forced = bi >= 0;
-    if (bi < 0) bi = wave_select_child<VL, SOLVE>(ch, cm, k, n, parentVC, c_puct, lam, nullptr);
+    if (bi < 0) bi = wave_select_child<VL, SOLVE, false>(ch, cm, k, n, parentVC, c_puct, lam, SZ_FPU_REFERENCE, 0.f, 0, 0.0, nullptr);
     return bi;
 }
 
 // NON-REFERENCE option (sz_set_fpu): what the FPU instantiations of k_search_step take on top of View, and of ForcedOpts when both options are
 // on: k_search_step<VL, SOLVE, FpuOpts>, k_search_step<VL, SOLVE, ForcedOpts, FpuOpts>.  k_search_begin and k_play have no FPU variant.
 struct FpuOpts { sz_fpu_options o; };
-template <typename... FO> constexpr bool is_fpu = (std::is_same_v<FO, FpuOpts> || ...);
-__device__ __forceinline__ const ForcedOpts& forced_opts(const ForcedOpts& fo, const FpuOpts&) { return fo; }
-__device__ __forceinline__ const FpuOpts& fpu_opts(const FpuOpts& fp) { return fp; }
-__device__ __forceinline__ const FpuOpts& fpu_opts(const ForcedOpts&, const FpuOpts& fp) { return fp; }
-
-// Node.select under first-play urgency (sz_set_fpu; include/sigmazero.h is the rule): wave_select_child with the score of an unvisited
-// child (n_c = N_c + k_c == 0) replaced by q0 + ucb_u(0, P_c, sq, c_puct), q0 = (v0 + 1) / 2.  mode / value: the site's (the root's at depth 0,
-// the tree's below; uniform); pN / pW: the parent's own stored edge.  v0 and with it q0 are formed once per parent and are the same in every
-// lane: the xor butterfly leaves one sum in all 64 (f32 addition commutes), and it is read back through readfirstlane so that the compiler
-// knows.  A visited child, the arg-max, its tie-break and the solver's skipping of WIN children are wave_select_child's; mode ==
-// SZ_FPU_REFERENCE scores every child as it does.  ucb_out (optional, test hook) receives every child's value, skipped WIN children included.
-template <bool VL, bool SOLVE>
-__device__ __forceinline__ int wave_select_child_fpu(const EdgeStat* ch, const EdgeMeta* cm, const int* k, int n, int parentVC, float c_puct, float lam,
-                                                     int mode, float value, int pN, double pW, float* ucb_out) {
-    const int lane = lane_id();
-    const float sq = (float)sqrt((double)parentVC);
-    bool skip_wins = false;
-    if constexpr (SOLVE) {
-        bool open = false;
-        for (int c = lane; c < n; c += 64) open |= (cm[c].pad & PR_MASK) != PR_WIN;
-        skip_wins = __ballot(open) != 0;
-    }
-    float q0 = 0.5f;
-    if (mode != SZ_FPU_REFERENCE) {
-        float v0 = value;
-        if (mode == SZ_FPU_REDUCTION) {
-            float part = 0.f;                                            // the prior mass of the visited children, a label does not matter
-            for (int c = lane; c < n; c += 64) {
-                const EdgeStat s = ch[c];
-                int nc = s.N;
-                if constexpr (VL) nc += k[c];
-                if (nc >= 1) part = part + s.P;
-            }
-            const float mass = __int_as_float(uni(__float_as_int(wave_sum_butterfly(part))));
-            const float vp = (float)pW / ((float)pN + 1e-6f);
-            v0 = vp - (value * (float)sqrt((double)mass));
-        }
-        if (!(v0 >= -1.0f)) v0 = -1.0f;
-        if (v0 > 1.0f) v0 = 1.0f;
-        q0 = (v0 + 1.0f) / 2.0f;
-    }
-    float best = 0.f; int bi = 0x7fffffff;
-    for (int c = lane; c < n; c += 64) {
-        const EdgeStat s = ch[c];
-        int kc = 0;
-        if constexpr (VL) kc = k[c];
-        const int nc = s.N + kc;
-        float u;
-        if (nc >= 1 || mode == SZ_FPU_REFERENCE) {
-            if constexpr (VL) u = ucb_value(nc, s.W + (double)lam * (double)kc, s.P, sq, c_puct);
-            else u = ucb_value(s.N, s.W, s.P, sq, c_puct);
-        } else u = q0 + ucb_u(0, s.P, sq, c_puct);
-        if (ucb_out) ucb_out[c] = u;
-        if constexpr (SOLVE) { if (skip_wins && (cm[c].pad & PR_MASK) == PR_WIN) continue; }
-        if (bi == 0x7fffffff || u > best) { best = u; bi = c; }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        float ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
-    }
-    return uni(bi);
-}
 
 // NON-REFERENCE option (sz_set_gumbel): what the GUMBEL instantiations take on top of View, before FpuOpts when both options are on:
 // k_search_step<false, false, GumbelOpts[, FpuOpts]> and k_play<false, GumbelOpts>.  k_search_begin has no variant: the root's network value is
@@ -311,10 +287,6 @@ struct GumbelOpts {
     double* work;               // [B][SZ_MAX_MOVES] k_play's per-child terms, summed by one lane in child order
     unsigned long long* stat;   // [B][2] root selections made by the rule, of them over all children because none was at the level
 };
-template <typename... FO> constexpr bool is_gumbel = (std::is_same_v<FO, GumbelOpts> || ...);
-__device__ __forceinline__ const GumbelOpts& gumbel_opts(const GumbelOpts& go) { return go; }
-__device__ __forceinline__ const GumbelOpts& gumbel_opts(const GumbelOpts& go, const FpuOpts&) { return go; }
-__device__ __forceinline__ const FpuOpts& fpu_opts(const GumbelOpts&, const FpuOpts& fp) { return fp; }
 
 // the mover's value of a visited root child in [0, 1] (a child's W is stored from the child's side to move) ...
 __device__ __forceinline__ double gumbel_q(const EdgeStat& s) { return 0.5 - 0.5 * (s.W / (double)s.N); }
@@ -857,7 +829,7 @@ __global__ void k_reset_endings(EndState* st, const uint8_t* active, int B, int 
 // FO = ForcedOpts (sz_set_forced_playouts): the board's bit of fo.boards is latched into its status word beside ST_QUIET
 template <bool VL, bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb, BeginOpts o, FO... fo) {
-    constexpr bool FORCED = is_forced<FO...>;
+    constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -877,7 +849,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
     const int root_ply = uni(bp.ctl->game_ply);
     const int qbit = (o.quiet && uni((int)o.quiet[b])) ? ST_QUIET : 0;
     int fbit = 0;
-    if constexpr (FORCED) fbit = uni((int)forced_opts(fo...).boards[b]) ? ST_FORCED : 0;
+    if constexpr (FORCED) fbit = uni((int)opt_of<ForcedOpts>(fo...).boards[b]) ? ST_FORCED : 0;
     SzPos X = load_pos(bp.ring + (root_ply & (SZ_RING - 1)));
     path[0] = 0;
     if (v.reuse && uni(bp.ctl->reuse_ready) && uni(bp.ctl->n_nodes) <= v.S && 2 * (long long)uni(bp.ctl->n_edges) <= v.e_cap && v.S > 0) {
@@ -963,18 +935,20 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // is backed up on the spot, a descent that ends on a leaf already pending in this step (a collision) ends the gather.
 // SOLVE = true (sz_set_solver): proven results are carried up the tree; a descent ends at the first proven node on its way.
 // VL && SOLVE (sz_set_search_options): both at once; a proven stop puts nothing in flight and the gather goes on, a pending leaf is unknown.
-// One body for the four: selection is wave_select_child<VL, SOLVE>, a pending leaf's path / mask / depth / network row come from
+// One body for the four: selection is wave_select_child<VL, SOLVE, FPU>, a pending leaf's path / mask / depth / network row come from
 // leaf_ptrs<VL>; only the in-flight counts, n_pend, the collision break and "gather on" against "one leaf, stop" sit under if constexpr (VL).
-// FO = ForcedOpts (sz_set_forced_playouts): on a board with ST_FORCED the selection at depth 0 is wave_select_root_forced; below the root
-// nothing changes.
-// FO = [ForcedOpts,] FpuOpts (sz_set_fpu): every selection is wave_select_child_fpu, after wave_forced_child at the root of a forced board.
-// FO = GumbelOpts[, FpuOpts] (sz_set_gumbel, VL = SOLVE = false only): the selection at depth 0 is wave_select_root_gumbel and the root's network
-// value is kept when the root is expanded; below the root nothing changes (with FpuOpts: the tree's first-play value).
+// The options change the one selection site, in this order, and nothing else in the descent:
+// FO has ForcedOpts (sz_set_forced_playouts): at depth 0 of a board with ST_FORCED wave_forced_child decides when it finds a forced child
+// (without FpuOpts through wave_select_root_forced, which is that and the arg-max).
+// FO has GumbelOpts (sz_set_gumbel, VL = SOLVE = false only, never with ForcedOpts): the selection at depth 0 is wave_select_root_gumbel, and the
+// root's network value is kept when the root is expanded.
+// FO has FpuOpts (sz_set_fpu): the arg-max that decides otherwise scores unvisited children by the site's first-play value, the root's at
+// depth 0 and the tree's below.
 template <bool VL, bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb, FO... fo) {
-    constexpr bool FORCED = is_forced<FO...>;
-    constexpr bool FPU = is_fpu<FO...>;
-    constexpr bool GUMBEL = is_gumbel<FO...>;
+    constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
+    constexpr bool FPU = has_opt<FpuOpts, FO...>;
+    constexpr bool GUMBEL = has_opt<GumbelOpts, FO...>;
     static_assert(!GUMBEL || (!VL && !SOLVE && !FORCED), "sz_set_gumbel refuses leaf batching, the solver and forced playouts");
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
@@ -1086,7 +1060,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             n_edges += kept;
             (void)node;
         const double val = (double)value[lf.row];                        // node.value = value.item()
-        if constexpr (GUMBEL) { if (d == 0 && lane == 0) gumbel_opts(fo...).vhat[b] = value[lf.row]; }     // sz_set_gumbel: the root's network value
+        if constexpr (GUMBEL) { if (d == 0 && lane == 0) opt_of<GumbelOpts>(fo...).vhat[b] = value[lf.row]; }     // sz_set_gumbel: the root's network value
         if constexpr (VL) {                                             // its descent is no longer in flight
             for (int j = lane; j <= d; j += 64) vb.vk[(size_t)b * v.e_cap + path[j]] -= 1;
         }
@@ -1113,42 +1087,38 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         int proven = PR_UNKNOWN;                                        // solver: result of the first proven node on the way, the root included
         if constexpr (SOLVE) proven = uni((int)m.pad & PR_MASK);
         while (mn > 0 && !proven) {                                     // Node.select
-            int bi;
-            if constexpr (GUMBEL) {
+            int bi = -1;
+            EdgeStat ps;                                                // sz_set_fpu: vp comes from the parent's own stored edge (cur; the root is edge 0)
+            if constexpr (FPU) ps = bp.es[cur];
+            // In order: a forced child of the root (sz_set_forced_playouts), else the Gumbel rule at the root (sz_set_gumbel), else the arg-max.
+            // Without FPU the forced root keeps its own composition, wave_select_root_forced, and counts through `forced`: folded into the
+            // sequence below, three of the four k_search_step<.., ForcedOpts> instantiations spill 8 to 24 bytes more per lane.
+            bool forced = false;
+            if constexpr (FORCED && FPU) {
+                if (d == 0 && (status & ST_FORCED)) bi = wave_forced_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, opt_of<ForcedOpts>(fo...).k);
+                n_forced += bi >= 0 ? 1 : 0;
+            }
+            if (GUMBEL && d == 0) {
                 // sz_set_gumbel: only depth 0 changes.  One leaf per step and nothing in flight: sims - 1 root-child visits were made before this one
-                if (d == 0) {
-                    const GumbelOpts& go = gumbel_opts(fo...);
+                if constexpr (GUMBEL) {
+                    const GumbelOpts& go = opt_of<GumbelOpts>(fo...);
                     bool fallback;
                     bi = wave_select_root_gumbel(bp.es + m.first, go.g ? go.g + (size_t)b * SZ_MAX_MOVES : nullptr, mn, sims - 1, budget, go.o, &fallback);
                     n_gumbel++; n_fallback += fallback ? 1 : 0;
-                } else if constexpr (FPU) {                             // below the root FPU acts as without the option: the tree's mode and value
-                    const sz_fpu_options& fp = fpu_opts(fo...).o;
-                    const EdgeStat ps = bp.es[cur];
-                    bi = wave_select_child_fpu<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, fp.tree_mode, fp.tree_value,
-                                                          uni(ps.N), uni_f64(ps.W), nullptr);
-                } else
-                    bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
-            } else if constexpr (FPU) {
-                // sz_set_fpu: the root's mode and value at depth 0, the tree's below; vp from the parent's own stored edge (cur; the root is edge 0)
-                const sz_fpu_options& fp = fpu_opts(fo...).o;
-                const EdgeStat ps = bp.es[cur];
-                bi = -1;
-                if constexpr (FORCED) {                                 // the forced child decides first, as without the option
-                    if (d == 0 && (status & ST_FORCED)) bi = wave_forced_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, forced_opts(fo...).k);
-                    n_forced += bi >= 0 ? 1 : 0;
                 }
-                if (bi < 0)
-                    bi = wave_select_child_fpu<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, d == 0 ? fp.root_mode : fp.tree_mode,
-                                                          d == 0 ? fp.root_value : fp.tree_value, uni(ps.N), uni_f64(ps.W), nullptr);
-            } else if constexpr (FORCED) {
-                bool forced = false;
-                if (d == 0 && (status & ST_FORCED))
-                    bi = wave_select_root_forced<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, forced_opts(fo...).k, &forced);
-                else
-                    bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
-                n_forced += forced ? 1 : 0;
-            } else
-            bi = wave_select_child<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, nullptr);
+            } else if (FORCED && !FPU && d == 0 && (status & ST_FORCED)) {
+                if constexpr (FORCED)
+                    bi = wave_select_root_forced<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, opt_of<ForcedOpts>(fo...).k, &forced);
+            } else if (bi < 0) {
+                if constexpr (FPU) {
+                    // sz_set_fpu: the root's mode and value at depth 0, the tree's below
+                    const sz_fpu_options& fp = opt_of<FpuOpts>(fo...).o;
+                    bi = wave_select_child<VL, SOLVE, true>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, d == 0 ? fp.root_mode : fp.tree_mode,
+                                                            d == 0 ? fp.root_value : fp.tree_value, uni(ps.N), uni_f64(ps.W), nullptr);
+                } else
+                    bi = wave_select_child<VL, SOLVE, false>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, SZ_FPU_REFERENCE, 0.f, 0, 0.0, nullptr);
+            }
+            n_forced += forced ? 1 : 0;
             cur = m.first + bi;
             d++;
             if (d >= v.p_cap) { err = SZ_ERR_CAPACITY; break; }
@@ -1232,8 +1202,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if (err && !c->err) c->err = err;
         if constexpr (VL) c->n_pend = n_pend;
         if constexpr (SOLVE) { v.sstat[(size_t)b * 2] += n_stop; v.sstat[(size_t)b * 2 + 1] += n_proved; }
-        if constexpr (FORCED) forced_opts(fo...).stat[(size_t)b * 2] += n_forced;
-        if constexpr (GUMBEL) { gumbel_opts(fo...).stat[(size_t)b * 2] += n_gumbel; gumbel_opts(fo...).stat[(size_t)b * 2 + 1] += n_fallback; }
+        if constexpr (FORCED) opt_of<ForcedOpts>(fo...).stat[(size_t)b * 2] += n_forced;
+        if constexpr (GUMBEL) { opt_of<GumbelOpts>(fo...).stat[(size_t)b * 2] += n_gumbel; opt_of<GumbelOpts>(fo...).stat[(size_t)b * 2 + 1] += n_fallback; }
     }
 }
 
@@ -1346,9 +1316,9 @@ __device__ void wave_keep_subtree(const View& v, const BoardPtrs& bp, int b, int
 // v_mix and the root's network value are left for sz_fetch_gumbel; the record keeps the counted visits
 template <bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO... fo) {
-    constexpr bool FORCED = is_forced<FO...>;
-    constexpr bool ENDING = is_ending<FO...>;
-    constexpr bool GUMBEL = is_gumbel<FO...>;
+    constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
+    constexpr bool ENDING = has_opt<EndOpts, FO...>;
+    constexpr bool GUMBEL = has_opt<GumbelOpts, FO...>;
     static_assert(!GUMBEL || (!SOLVE && !FORCED && !ENDING), "sz_set_gumbel refuses the solver, forced playouts and endings");
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
@@ -1357,7 +1327,7 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     BoardPtrs bp = board_ptrs(v, b);
     int status = uni(bp.ctl->status);
     if constexpr (ENDING) {                                              // a board that does not play in this sz_play: kind 0, m NaN
-        if (lane == 0) { end_opts(fo...).kind[b] = SZ_END_NONE; end_opts(fo...).mval[b] = __longlong_as_double(0x7ff8000000000000LL); }
+        if (lane == 0) { opt_of<EndOpts>(fo...).kind[b] = SZ_END_NONE; opt_of<EndOpts>(fo...).mval[b] = __longlong_as_double(0x7ff8000000000000LL); }
     }
     if (!(status & ST_SEARCHING) || !(status & ST_DONE) || (status & (ST_ERROR | ST_GAMEOVER))) return;
     EdgeMeta rm = bp.em[0];
@@ -1379,7 +1349,7 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     }
     int end_kind = SZ_END_NONE, end_result = 0;
     if constexpr (ENDING) {                                              // on the counted visits, before any pruning
-        const EndOpts& eo = end_opts(fo...);
+        const EndOpts& eo = opt_of<EndOpts>(fo...);
         int code = PR_UNKNOWN;
         if constexpr (SOLVE) code = rm.pad & PR_MASK;
         const int colour = uni((int)szm_turn(bp.npos[0].meta));
@@ -1395,11 +1365,11 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     }
     if constexpr (FORCED) {
         if (status & ST_FORCED) {                                        // the zero-visit check above stays on the counted visits
-            const int cut = wave_prune(bp.es + first, n, uni(bp.es[0].N), v.c_puct, forced_opts(fo...).k, vis_lds, nullptr);
+            const int cut = wave_prune(bp.es + first, n, uni(bp.es[0].N), v.c_puct, opt_of<ForcedOpts>(fo...).k, vis_lds, nullptr);
             __syncthreads();
             total -= cut;
             if (v.rec_action) for (int c = lane; c < n; c += 64) v.rec_visits[(size_t)b * SZ_MAX_CHILDREN + c] = vis_lds[c];
-            if (lane == 0) forced_opts(fo...).stat[(size_t)b * 2 + 1] += (unsigned long long)cut;
+            if (lane == 0) opt_of<ForcedOpts>(fo...).stat[(size_t)b * 2 + 1] += (unsigned long long)cut;
         }
     }
     if constexpr (ENDING) {
@@ -1416,7 +1386,7 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; idx = searchsorted(cdf, u, 'right')   (sequential f64, like numpy)
     int chosen = 0;
     if constexpr (GUMBEL) {
-        const GumbelOpts& go = gumbel_opts(fo...);
+        const GumbelOpts& go = opt_of<GumbelOpts>(fo...);
         chosen = wave_gumbel_play(bp.es + first, go.g ? go.g + (size_t)b * SZ_MAX_MOVES : nullptr, n, go.o, go.vhat[b], go.work + (size_t)b * SZ_MAX_MOVES,
                                   go.policy + (size_t)b * SZ_MAX_MOVES, go.vmix + b);
     } else
@@ -1538,8 +1508,19 @@ __global__ __launch_bounds__(64) void k_debug_select(const int* offsets, const i
     if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane_id() == 0) argmax_out[cs] = -1; return; }
     for (int c = lane_id(); c < n; c += 64) { EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s; }
     __syncthreads();
-    const int bi = wave_select_child<false, false>(ch, nullptr, nullptr, n, parent_visits[cs], c_puct[cs], 0.f, ucb_out + lo);
+    const int bi = wave_select_child<false, false, false>(ch, nullptr, nullptr, n, parent_visits[cs], c_puct[cs], 0.f, SZ_FPU_REFERENCE, 0.f, 0, 0.0, ucb_out + lo);
     if (lane_id() == 0) argmax_out[cs] = bi;
+}
+
+// the children [lo, lo + n) of a hook's case staged as the records the search reads, for the hooks whose cases carry in-flight counts and proven
+// codes (proven == NULL: none): ch, cm and kk hold SZ_MAX_CHILDREN entries each, in this order, from the start of the LDS
+__device__ __forceinline__ void stage_case(int lo, int n, const int* vc, const int* inflight, const double* wsum, const float* prior, const int8_t* proven,
+                                           EdgeStat* ch, EdgeMeta* cm, int* kk) {
+    for (int c = lane_id(); c < n; c += 64) {
+        EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s;
+        EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = 0; m.term = 0; m.tval = 0; m.pad = (unsigned short)(proven ? (proven[lo + c] & PR_MASK) : 0); cm[c] = m;
+        kk[c] = inflight[lo + c];
+    }
 }
 
 // test hook (sz_debug_forced): wave_select_root_forced and wave_prune, the functions k_search_step<.., ForcedOpts> and k_play<.., ForcedOpts> call, on
@@ -1554,11 +1535,8 @@ __global__ __launch_bounds__(64) void k_debug_forced(const int* offsets, const i
     int* vis = kk + SZ_MAX_CHILDREN;
     const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
     if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) { selected_out[cs] = -1; forced_out[cs] = 0; cstar_out[cs] = -1; } return; }
-    for (int c = lane; c < n; c += 64) {
-        EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s;
-        EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = 0; m.term = 0; m.tval = 0; m.pad = (unsigned short)(proven ? (proven[lo + c] & PR_MASK) : 0); cm[c] = m;
-        kk[c] = inflight[lo + c]; vis[c] = s.N;
-    }
+    stage_case(lo, n, vc, inflight, wsum, prior, proven, ch, cm, kk);
+    for (int c = lane; c < n; c += 64) vis[c] = vc[lo + c];
     __syncthreads();
     const int pv = parent_visits[cs];
     bool forced;
@@ -1570,7 +1548,7 @@ __global__ __launch_bounds__(64) void k_debug_forced(const int* offsets, const i
     for (int c = lane; c < n; c += 64) pruned_out[lo + c] = vis[c];
 }
 
-// test hook (sz_debug_select_fpu): wave_select_child_fpu, the function k_search_step<.., FpuOpts> calls, on caller-supplied children, one wave per
+// test hook (sz_debug_select_fpu): wave_select_child<.., true>, the function k_search_step<.., FpuOpts> calls, on caller-supplied children, one wave per
 // case.  proven == NULL: the instantiations without the solver
 __global__ __launch_bounds__(64) void k_debug_select_fpu(const int* offsets, const int* vc, const int* inflight, const double* wsum, const float* prior,
                                                          const int8_t* proven, const int* parent_visits, const int* parent_n, const double* parent_w,
@@ -1581,18 +1559,14 @@ __global__ __launch_bounds__(64) void k_debug_select_fpu(const int* offsets, con
     int* kk = (int*)(cm + SZ_MAX_CHILDREN);
     const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
     if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) selected_out[cs] = -1; return; }
-    for (int c = lane; c < n; c += 64) {
-        EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s;
-        EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = 0; m.term = 0; m.tval = 0; m.pad = (unsigned short)(proven ? (proven[lo + c] & PR_MASK) : 0); cm[c] = m;
-        kk[c] = inflight[lo + c];
-    }
+    stage_case(lo, n, vc, inflight, wsum, prior, proven, ch, cm, kk);
     __syncthreads();
     const sz_fpu_options o = opts[cs];
     const int root = uni(is_root[cs]);
     const int mode = uni(root ? o.root_mode : o.tree_mode);
     const float value = root ? o.root_value : o.tree_value;
-    const int bi = proven ? wave_select_child_fpu<true, true>(ch, cm, kk, n, parent_visits[cs], c_puct[cs], lam, mode, value, uni(parent_n[cs]), uni_f64(parent_w[cs]), ucb_out + lo)
-                          : wave_select_child_fpu<true, false>(ch, cm, kk, n, parent_visits[cs], c_puct[cs], lam, mode, value, uni(parent_n[cs]), uni_f64(parent_w[cs]), ucb_out + lo);
+    const int bi = proven ? wave_select_child<true, true, true>(ch, cm, kk, n, parent_visits[cs], c_puct[cs], lam, mode, value, uni(parent_n[cs]), uni_f64(parent_w[cs]), ucb_out + lo)
+                          : wave_select_child<true, false, true>(ch, cm, kk, n, parent_visits[cs], c_puct[cs], lam, mode, value, uni(parent_n[cs]), uni_f64(parent_w[cs]), ucb_out + lo);
     if (lane == 0) selected_out[cs] = bi;
 }
 
@@ -1653,6 +1627,15 @@ __global__ __launch_bounds__(64) void k_debug_endings(const int* offsets, const 
 // ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
+// what sz_set_forced_playouts, sz_set_fpu and sz_set_gumbel set for the next sz_search_begin, which takes it up whole: a search, its descent-only
+// launch, its steps and its sz_play run with what its sz_search_begin saw, whatever the setters are told in between
+struct Latched {
+    float forced_k;                 // the forced constant, 0 = off; > 0 selects the FORCED instantiations
+    sz_fpu_options fpu;             // all zero = off; a mode other than SZ_FPU_REFERENCE selects the FPU instantiations
+    int gumbel_on;                  // != 0 selects the GUMBEL instantiations ...
+    sz_gumbel_options gumbel; const double* gumbel_g;      // ... which run with these
+};
+
 struct sz_engine {
     sz_config cfg;
     View v;
@@ -1671,15 +1654,9 @@ struct sz_engine {
     std::vector<void*> vb_allocs;
     int solver;                     // sz_set_solver: the SOLVE instantiations of begin / step / play run
     unsigned long long* d_sstat;    // its counters [n_boards][2], allocated by the first enabling call
-    float forced_k;                 // sz_set_forced_playouts: the constant the next sz_search_begin takes up (0 = off)
-    ForcedOpts fo;                  // ... and what the searches begun since run with: fo.k > 0 selects the FORCED instantiations.  fo.boards
-                                    //     [n_boards] and fo.stat [n_boards][2] are allocated by the first enabling call
-    sz_fpu_options fpu_next;        // sz_set_fpu: what the next sz_search_begin takes up (all zero = off)
-    FpuOpts fp;                     // ... and what the searches begun since run with: a mode other than SZ_FPU_REFERENCE selects the FPU instantiations
-    int gumbel_next_on;             // sz_set_gumbel: what the next sz_search_begin takes up (0 = off) ...
-    sz_gumbel_options gumbel_next; const double* gumbel_next_g;
-    int gumbel_on;                  // ... and what the searches begun since and their sz_play run with: the GUMBEL instantiations when != 0
-    GumbelOpts go;                  //     its arrays are allocated by the first enabling call (go.stat != NULL from then on)
+    Latched next, cur;              // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel: what the next sz_search_begin takes up, and what it took up last
+    ForcedOpts fo;                  // sz_set_forced_playouts: fo.boards [n_boards] and fo.stat [n_boards][2], allocated by the first enabling call
+    GumbelOpts go;                  // sz_set_gumbel: its arrays, allocated by the first enabling call (go.stat != NULL from then on)
     int end_on;                     // sz_set_endings: sz_play runs the ENDING instantiations of k_play
     EndOpts eo;                     // ... with these; its arrays are allocated by the first enabling call (eo.state != NULL from then on)
 };
@@ -1704,14 +1681,33 @@ template <typename T> static int dalloc(sz_engine* e, T** p, size_t count) {
     return SZ_OK;
 }
 
-// the one place that maps the options in force to a kernel instantiation: f(VL, SOLVE, FORCED) is called with three std::bool_constants,
-// VL = leaf batching on (vb.L > 1), SOLVE = the solver on, FORCED = forced playouts on in the searches begun last (fo.k > 0).
-// Instantiations without batching take an empty Batch.
+// The one place that maps the options in force to a kernel instantiation, for sz_search_begin, sz_search_step and sz_play alike.  f(vl, solve, o...)
+// is called with two std::bool_constants, VL = leaf batching on (vb.L > 1; instantiations without it take an empty Batch) and SOLVE = the solver
+// on, and with the option structs in force, in the order the kernels take them: ForcedOpts or else GumbelOpts (the search begun last, e->cur;
+// under Gumbel VL = SOLVE = false, which the setters' refusals see to), FpuOpts (e->cur), EndOpts (sz_set_endings; `proven` cleared while the
+// solver is off; never beside GumbelOpts).  Each kernel takes the members of the pack that concern it: pick below.
 template <typename F> static void with_search_options(const sz_engine* e, F&& f) {
-    auto g = [&](auto vl, auto solve) { if (e->fo.k > 0.0f) f(vl, solve, std::true_type{}); else f(vl, solve, std::false_type{}); };
-    if (e->vb.L > 1) { if (e->solver) g(std::true_type{}, std::true_type{}); else g(std::true_type{}, std::false_type{}); }
-    else             { if (e->solver) g(std::false_type{}, std::true_type{}); else g(std::false_type{}, std::false_type{}); }
+    const Latched& c = e->cur;
+    auto endings = [&](auto vl, auto solve, auto... o) {
+        if constexpr (has_opt<GumbelOpts, decltype(o)...>) f(vl, solve, o...);
+        else if (e->end_on) { EndOpts eo = e->eo; if (!decltype(solve)::value) eo.o.proven = 0; f(vl, solve, o..., eo); }
+        else f(vl, solve, o...);
+    };
+    auto fpu = [&](auto vl, auto solve, auto... o) {
+        if (c.fpu.tree_mode != SZ_FPU_REFERENCE || c.fpu.root_mode != SZ_FPU_REFERENCE) endings(vl, solve, o..., FpuOpts{c.fpu}); else endings(vl, solve, o...);
+    };
+    auto forced = [&](auto vl, auto solve) {
+        if (c.forced_k > 0.0f) { ForcedOpts fo = e->fo; fo.k = c.forced_k; fpu(vl, solve, fo); } else fpu(vl, solve);
+    };
+    if (c.gumbel_on) { GumbelOpts go = e->go; go.o = c.gumbel; go.g = c.gumbel_g; fpu(std::false_type{}, std::false_type{}, go); }
+    else if (e->vb.L > 1) { if (e->solver) forced(std::true_type{}, std::true_type{}); else forced(std::true_type{}, std::false_type{}); }
+    else                  { if (e->solver) forced(std::false_type{}, std::true_type{}); else forced(std::false_type{}, std::false_type{}); }
 }
+// the members of an option pack whose type is one of Keep..., as a tuple to std::apply a launch to
+template <typename... Keep, typename O> static auto pick1(const O& o) {
+    if constexpr (has_opt<O, Keep...>) return std::tuple<O>(o); else return std::tuple<>();
+}
+template <typename... Keep, typename... O> static auto pick(const O&... o) { return std::tuple_cat(pick1<Keep...>(o)...); }
 
 extern "C" {
 
@@ -1840,14 +1836,56 @@ int sz_compact(sz_engine* e, int32_t enable, int32_t* n_live_out, void* stream) 
     return SZ_OK;
 }
 
-// true while some board is between sz_search_begin and the end of its search (synchronises the stream)
-static int search_in_progress(sz_engine* e, hipStream_t s, bool* out) {
+// "only between searches": SZ_ERR_STATE while some board is between sz_search_begin and the end of its search (synchronises the stream)
+static int between_searches(sz_engine* e, hipStream_t s) {
     std::vector<Ctl> h(e->v.B);
     HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    *out = false;
     for (const Ctl& c : h)
-        if ((c.status & ST_SEARCHING) && !(c.status & (ST_DONE | ST_ERROR))) *out = true;
+        if ((c.status & ST_SEARCHING) && !(c.status & (ST_DONE | ST_ERROR))) return SZ_ERR_STATE;
+    return SZ_OK;
+}
+
+// sums of a per-board counter array [n_boards][width] (NULL: the option was never on, all zero) into out[0..width)
+static int sum_board_counters(sz_engine* e, const unsigned long long* counters, int width, uint64_t* out, void* stream) {
+    if (!e || !out) return SZ_ERR_INVALID;
+    for (int k = 0; k < width; k++) out[k] = 0;
+    if (!counters) return SZ_OK;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<unsigned long long> h((size_t)e->v.B * width);
+    HIPCHK(hipMemcpyAsync(h.data(), counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < h.size(); i++) out[i % width] += h[i];
+    return SZ_OK;
+}
+
+// The combinations of options an engine runs, in one place.  OptionState is what they depend on; a setter takes option_state(e), applies its own
+// change and asks option_refusal before it touches the engine, so the state in force is always an allowed one and switching an option off never
+// leads out of it.  SZ_ERR_INVALID comes before the question whether the engine searches, SZ_ERR_STATE is the root noise's code.
+struct OptionState {
+    int L, solver;                  // sz_set_leaf_batching / sz_set_solver / sz_set_search_options
+    bool forced, gumbel;            // sz_set_forced_playouts, sz_set_gumbel: what the next sz_search_begin takes up
+    bool endings, noise;            // sz_set_endings; sz_set_root_noise / sz_set_search_root_noise with a gamma
+};
+enum OptionSetter { BY_ANY, BY_LEAF_BATCHING, BY_SOLVER, BY_ROOT_NOISE };     // the setters whose own entry point accepts less than the engine runs
+static OptionState option_state(const sz_engine* e) {
+    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr};
+}
+static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter by = BY_ANY) {
+    const bool reuse = e->v.reuse != 0;
+    if (p.forced && !e->v.learning) return SZ_ERR_INVALID;                  // an exploration option of self-play, like root noise
+    // Gumbel, each combination a follow-up: a kept subtree's root was not expanded by this search, leaf batching has visits in flight, the
+    // solver and forced playouts select at the root themselves, the ending rules read the most visited move
+    if (p.gumbel && (reuse || p.L > 1 || p.solver || p.forced || p.endings)) return SZ_ERR_INVALID;
+    // leaf batching, the solver and subtree reuse combine through sz_set_search_options alone
+    if (by == BY_LEAF_BATCHING && p.L > 1 && (reuse || p.solver)) return SZ_ERR_INVALID;
+    if (by == BY_SOLVER && p.solver && (reuse || p.L > 1)) return SZ_ERR_INVALID;
+    if (p.gumbel && p.noise) return SZ_ERR_STATE;                           // Gumbel is the root's exploration
+    // sz_set_root_noise: a reused root was expanded as an inner node, on un-noised priors, and is never expanded again, so the noise would silently
+    // apply to the first ply of a game only; and a reuse engine under sz_set_search_root_noise leaves that mode through that setter, which drops
+    // the kept subtrees
+    if (by == BY_ROOT_NOISE && reuse && (p.noise || e->v.root_gamma)) return SZ_ERR_STATE;
     return SZ_OK;
 }
 
@@ -1859,10 +1897,8 @@ int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream) {
             if (budgets[b] < 0 || budgets[b] > e->v.S) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
+    int rc = between_searches(e, s);
     if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
     if (budgets) {
         HIPCHK(hipMemcpyAsync(e->d_budget, budgets, (size_t)e->v.B * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
@@ -1879,10 +1915,8 @@ int sz_set_visit_targets(sz_engine* e, const int32_t* targets, void* stream) {
             if (targets[b] < 0 || targets[b] > e->v.S) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
+    int rc = between_searches(e, s);
     if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
     if (targets) {
         HIPCHK(hipMemcpyAsync(e->d_target, targets, (size_t)e->v.B * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
@@ -1947,12 +1981,9 @@ int sz_compact_searching(sz_engine* e, void* planes_dev, int32_t* n_live_out, vo
 int sz_set_root_noise(sz_engine* e, const float* gamma_dev) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    // a reused root (sz_config.reuse_subtree) was expanded as an inner node, on un-noised priors, and is never expanded again: root noise would silently
-    // apply to the first ply of a game only.  The two non-reference options are therefore mutually exclusive.
-    if (gamma_dev && e->v.reuse) return SZ_ERR_STATE;
-    if (gamma_dev && e->gumbel_next_on) return SZ_ERR_STATE;               // sz_set_gumbel: Gumbel is the root's exploration
-    // ... and a reuse engine that runs sz_set_search_root_noise leaves that mode through the same setter, which drops the kept subtrees
-    if (e->v.reuse && e->v.root_gamma) return SZ_ERR_STATE;
+    OptionState p = option_state(e);
+    p.noise = gamma_dev != nullptr;
+    if (int rc = option_refusal(e, p, BY_ROOT_NOISE)) return rc;
     e->v.root_gamma = gamma_dev;
     e->bo.quiet = nullptr;
     return SZ_OK;
@@ -1960,13 +1991,13 @@ int sz_set_root_noise(sz_engine* e, const float* gamma_dev) {
 
 int sz_set_search_root_noise(sz_engine* e, const float* gamma_dev, const uint8_t* quiet, void* stream) {
     if (!e) return SZ_ERR_INVALID;
-    if (gamma_dev && e->gumbel_next_on) return SZ_ERR_STATE;               // sz_set_gumbel: Gumbel is the root's exploration
+    OptionState p = option_state(e);
+    p.noise = gamma_dev != nullptr;
+    int rc = option_refusal(e, p);
+    if (rc) return rc;
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
-    if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if ((rc = between_searches(e, s))) return rc;
     if (quiet) {
         HIPCHK(hipMemcpyAsync(e->d_quiet, quiet, (size_t)e->v.B, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
@@ -2008,42 +2039,23 @@ int sz_upload_game(sz_engine* e, int32_t board, const void* ring, int32_t ply, v
 
 // the k_search_step instantiation of the options in force; policy == NULL: the descent-only launch of sz_search_begin
 static void launch_step(sz_engine* e, const float* policy, const float* value, void* planes, hipStream_t s) {
-    const bool fpu = e->fp.o.tree_mode != SZ_FPU_REFERENCE || e->fp.o.root_mode != SZ_FPU_REFERENCE;          // sz_set_fpu
-    if (e->gumbel_on) {                                                     // sz_set_gumbel: its setter and the others' refusals leave VL = SOLVE = FORCED = false
-        if (fpu)
-            hipLaunchKernelGGL((k_search_step<false, false, GumbelOpts, FpuOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{}, e->go, e->fp);
-        else
-            hipLaunchKernelGGL((k_search_step<false, false, GumbelOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, Batch{}, e->go);
-        return;
-    }
-    with_search_options(e, [&](auto vl, auto solve, auto forced) {
+    with_search_options(e, [&](auto vl, auto solve, auto... o) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
-        if constexpr (decltype(forced)::value) {
-            if (fpu)
-                hipLaunchKernelGGL((k_search_step<VL, SOLVE, ForcedOpts, FpuOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fo, e->fp);
-            else
-                hipLaunchKernelGGL((k_search_step<VL, SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fo);
-        } else {
-            if (fpu)
-                hipLaunchKernelGGL((k_search_step<VL, SOLVE, FpuOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, e->fp);
-            else
-                hipLaunchKernelGGL((k_search_step<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{});
-        }
+        std::apply([&](auto... k) {
+            hipLaunchKernelGGL((k_search_step<VL, SOLVE, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, k...);
+        }, pick<ForcedOpts, GumbelOpts, FpuOpts>(o...));                    // the ending rules live in sz_play alone
     });
 }
 
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    e->fo.k = e->forced_k;                                                  // sz_set_forced_playouts takes effect here
-    e->fp.o = e->fpu_next;                                                  // ... and sz_set_fpu
-    e->gumbel_on = e->gumbel_next_on; e->go.o = e->gumbel_next; e->go.g = e->gumbel_next_g;      // ... and sz_set_gumbel
-    with_search_options(e, [&](auto vl, auto solve, auto forced) {
+    e->cur = e->next;                                                       // sz_set_forced_playouts, sz_set_fpu and sz_set_gumbel take effect here
+    with_search_options(e, [&](auto vl, auto solve, auto... o) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
-        if constexpr (decltype(forced)::value)
-            hipLaunchKernelGGL((k_search_begin<VL, SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo, e->fo);
-        else
-            hipLaunchKernelGGL((k_search_begin<VL, SOLVE>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo);
+        std::apply([&](auto... k) {
+            hipLaunchKernelGGL((k_search_begin<VL, SOLVE, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo, k...);
+        }, pick<ForcedOpts>(o...));                                         // the one option that acts where a root is made: the board's bit
     });
     HIPCHK(hipGetLastError());
     if (e->v.reuse && planes_dev) {
@@ -2098,13 +2110,14 @@ static int solver_counters(sz_engine* e, hipStream_t s) {
     return SZ_OK;
 }
 
-// what the three option setters share, after their own argument checks and refusals: only between searches; buffers and counters before
-// the assignment, so a call that fails changes no option (a failed allocation of the batch buffers leaves leaves_per_step = 1)
-static int set_options(sz_engine* e, int leaves_per_step, float virtual_loss, int solver, hipStream_t s) {
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
-    if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;
+// what the three option setters share, after their own argument checks: the combination rules as the setter `by` applies them, then only
+// between searches; buffers and counters before the assignment, so a call that fails changes no option (a failed allocation of the batch
+// buffers leaves leaves_per_step = 1)
+static int set_options(sz_engine* e, int leaves_per_step, float virtual_loss, int solver, OptionSetter by, hipStream_t s) {
+    OptionState p = option_state(e);
+    p.L = leaves_per_step; p.solver = solver;
+    int rc = option_refusal(e, p, by);
+    if (rc || (rc = between_searches(e, s))) return rc;
     if ((rc = batch_buffers(e, leaves_per_step))) return rc;
     if (solver && (rc = solver_counters(e, s))) return rc;
     e->vb.L = leaves_per_step;
@@ -2120,29 +2133,23 @@ static bool batching_args_ok(int leaves_per_step, float virtual_loss) {
 
 int sz_set_leaf_batching(sz_engine* e, int32_t leaves_per_step, float virtual_loss, void* stream) {
     if (!e || !batching_args_ok(leaves_per_step, virtual_loss)) return SZ_ERR_INVALID;
-    if (leaves_per_step > 1 && e->v.reuse) return SZ_ERR_INVALID;          // combining the two non-reference options is not supported
-    if (leaves_per_step > 1 && e->solver) return SZ_ERR_INVALID;           // nor leaf batching with the solver
-    if (leaves_per_step > 1 && e->gumbel_next_on) return SZ_ERR_INVALID;   // nor with the Gumbel root search (sz_set_gumbel)
     ENGINE_GUARD(e);
-    return set_options(e, leaves_per_step, virtual_loss, e->solver, (hipStream_t)stream);
+    return set_options(e, leaves_per_step, virtual_loss, e->solver, BY_LEAF_BATCHING, (hipStream_t)stream);
 }
 
 int sz_set_solver(sz_engine* e, int32_t enable, void* stream) {
     if (!e) return SZ_ERR_INVALID;
-    if (enable && (e->v.reuse || e->vb.L > 1)) return SZ_ERR_INVALID;      // not combined with subtree reuse or leaf batching
-    if (enable && e->gumbel_next_on) return SZ_ERR_INVALID;                // nor with the Gumbel root search (sz_set_gumbel)
     ENGINE_GUARD(e);
-    return set_options(e, e->vb.L, e->vb.lam, enable ? 1 : 0, (hipStream_t)stream);
+    return set_options(e, e->vb.L, e->vb.lam, enable ? 1 : 0, BY_SOLVER, (hipStream_t)stream);
 }
 
 int sz_set_search_options(sz_engine* e, const sz_search_options* opt, void* stream) {
     if (!e || !opt || !batching_args_ok(opt->leaves_per_step, opt->virtual_loss)) return SZ_ERR_INVALID;
-    if ((opt->leaves_per_step > 1 || opt->solver) && e->gumbel_next_on) return SZ_ERR_INVALID;      // sz_set_gumbel: neither is combined with it
     ENGINE_GUARD(e);
     const int solver = opt->solver ? 1 : 0;
     // a kept subtree built under other settings has no `complete` bits, or its in-flight counts were never written: start fresh
     const bool drop = e->v.reuse && (opt->leaves_per_step != e->vb.L || solver != e->solver);
-    int rc = set_options(e, opt->leaves_per_step, opt->virtual_loss, solver, (hipStream_t)stream);
+    int rc = set_options(e, opt->leaves_per_step, opt->virtual_loss, solver, BY_ANY, (hipStream_t)stream);
     if (rc) return rc;
     if (drop) {
         hipLaunchKernelGGL(k_drop_subtrees, dim3((e->v.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->v);
@@ -2159,29 +2166,17 @@ int sz_root_proven(sz_engine* e, int8_t* root_dev, int8_t* child_dev, void* stre
     return SZ_OK;
 }
 
-int sz_solver_stats(sz_engine* e, uint64_t out[2], void* stream) {
-    if (!e || !out) return SZ_ERR_INVALID;
-    out[0] = out[1] = 0;
-    if (!e->d_sstat) return SZ_OK;                                          // the solver was never on
-    ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<unsigned long long> h((size_t)e->v.B * 2);
-    HIPCHK(hipMemcpyAsync(h.data(), e->d_sstat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (size_t b = 0; b < (size_t)e->v.B; b++) { out[0] += h[2 * b]; out[1] += h[2 * b + 1]; }
-    return SZ_OK;
-}
+int sz_solver_stats(sz_engine* e, uint64_t out[2], void* stream) { return sum_board_counters(e, e ? e->d_sstat : nullptr, 2, out, stream); }
 
 int sz_set_forced_playouts(sz_engine* e, float k, const uint8_t* boards, void* stream) {
     if (!e || !(k >= 0.0f) || !std::isfinite(k)) return SZ_ERR_INVALID;
-    if (k > 0.0f && !e->v.learning) return SZ_ERR_INVALID;                  // an exploration option of self-play, like root noise
-    if (k > 0.0f && e->gumbel_next_on) return SZ_ERR_INVALID;               // not combined with the Gumbel root search (sz_set_gumbel)
+    OptionState p = option_state(e);
+    p.forced = k > 0.0f;
+    int rc = option_refusal(e, p);
+    if (rc) return rc;
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
-    if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if ((rc = between_searches(e, s))) return rc;
     if (k > 0.0f) {
         const size_t B = e->v.B;
         if (!e->fo.stat) {                                                  // the first enabling call: the boards' bits and the counters
@@ -2195,7 +2190,7 @@ int sz_set_forced_playouts(sz_engine* e, float k, const uint8_t* boards, void* s
         HIPCHK(hipMemcpyAsync((void*)e->fo.boards, h.data(), B, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));                                    // the staging array goes out of scope
     }
-    e->forced_k = k;
+    e->next.forced_k = k;
     return SZ_OK;
 }
 
@@ -2211,15 +2206,13 @@ int sz_set_fpu(sz_engine* e, const sz_fpu_options* opt, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     if (opt && (!fpu_site_ok(opt->tree_mode, opt->tree_value) || !fpu_site_ok(opt->root_mode, opt->root_value))) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    bool busy = false;
-    int rc = search_in_progress(e, (hipStream_t)stream, &busy);
+    int rc = between_searches(e, (hipStream_t)stream);
     if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
     sz_fpu_options o = {SZ_FPU_REFERENCE, 0.0f, SZ_FPU_REFERENCE, 0.0f};
     if (opt) o = *opt;
     if (o.tree_mode == SZ_FPU_REFERENCE) o.tree_value = 0.0f;
     if (o.root_mode == SZ_FPU_REFERENCE) o.root_value = 0.0f;
-    e->fpu_next = o;
+    e->next.fpu = o;
     return SZ_OK;
 }
 
@@ -2228,18 +2221,17 @@ int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_de
     if (opt) {
         if (opt->max_considered < 1 || opt->max_considered > SZ_MAX_MOVES) return SZ_ERR_INVALID;
         if (!std::isfinite(opt->c_visit) || opt->c_visit < 0.0f || !std::isfinite(opt->c_scale) || opt->c_scale < 0.0f) return SZ_ERR_INVALID;
-        // each combination is a follow-up: a kept subtree's root was not expanded by this search, leaf batching has visits in flight, the
-        // solver and forced playouts select at the root themselves, the ending rules read the most visited move
-        if (e->v.reuse || e->vb.L > 1 || e->solver || e->forced_k > 0.0f || e->end_on) return SZ_ERR_INVALID;
     }
+    OptionState p = option_state(e);
+    p.gumbel = opt != nullptr;
+    const int refused = option_refusal(e, p);
+    if (refused == SZ_ERR_INVALID) return refused;
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
+    int rc = between_searches(e, s);
     if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
-    if (!opt) { e->gumbel_next_on = 0; e->gumbel_next_g = nullptr; return SZ_OK; }
-    if (e->v.root_gamma) return SZ_ERR_STATE;                               // root noise is on: Gumbel is the root's exploration
+    if (!opt) { e->next.gumbel_on = 0; e->next.gumbel_g = nullptr; return SZ_OK; }
+    if (refused) return refused;                                            // root noise is on: SZ_ERR_STATE, after the question whether the engine searches
     if (!e->go.stat) {                                                      // the first enabling call: the per-board outputs and the counters
         const size_t B = e->v.B;
         float* vh = nullptr; float* po = nullptr; double* vm = nullptr; double* wk = nullptr; unsigned long long* st = nullptr;
@@ -2252,7 +2244,7 @@ int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_de
         HIPCHK(hipStreamSynchronize(s));
         e->go.vhat = vh; e->go.policy = po; e->go.vmix = vm; e->go.work = wk; e->go.stat = st;
     }
-    e->gumbel_next = *opt; e->gumbel_next_g = g_dev; e->gumbel_next_on = 1;
+    e->next.gumbel = *opt; e->next.gumbel_g = g_dev; e->next.gumbel_on = 1;
     return SZ_OK;
 }
 
@@ -2269,31 +2261,9 @@ int sz_fetch_gumbel(sz_engine* e, float* policy_target, double* v_mix, float* ro
     return SZ_OK;
 }
 
-int sz_gumbel_stats(sz_engine* e, uint64_t out[2], void* stream) {
-    if (!e || !out) return SZ_ERR_INVALID;
-    out[0] = out[1] = 0;
-    if (!e->go.stat) return SZ_OK;                                          // the option was never on
-    ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<unsigned long long> h((size_t)e->v.B * 2);
-    HIPCHK(hipMemcpyAsync(h.data(), e->go.stat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (size_t b = 0; b < (size_t)e->v.B; b++) { out[0] += h[2 * b]; out[1] += h[2 * b + 1]; }
-    return SZ_OK;
-}
+int sz_gumbel_stats(sz_engine* e, uint64_t out[2], void* stream) { return sum_board_counters(e, e ? e->go.stat : nullptr, 2, out, stream); }
 
-int sz_forced_stats(sz_engine* e, uint64_t out[2], void* stream) {
-    if (!e || !out) return SZ_ERR_INVALID;
-    out[0] = out[1] = 0;
-    if (!e->fo.stat) return SZ_OK;                                          // the option was never on
-    ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<unsigned long long> h((size_t)e->v.B * 2);
-    HIPCHK(hipMemcpyAsync(h.data(), e->fo.stat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (size_t b = 0; b < (size_t)e->v.B; b++) { out[0] += h[2 * b]; out[1] += h[2 * b + 1]; }
-    return SZ_OK;
-}
+int sz_forced_stats(sz_engine* e, uint64_t out[2], void* stream) { return sum_board_counters(e, e ? e->fo.stat : nullptr, 2, out, stream); }
 
 int sz_set_endings(sz_engine* e, const sz_ending_options* opt, const uint8_t* holdout, void* stream) {
     if (!e) return SZ_ERR_INVALID;
@@ -2302,14 +2272,14 @@ int sz_set_endings(sz_engine* e, const sz_ending_options* opt, const uint8_t* ho
         if (!std::isfinite(opt->draw_value) || opt->draw_value < 0.0f || opt->draw_value > 1.0f) return SZ_ERR_INVALID;
         if (opt->resign_patience < 0 || opt->resign_patience > END_STREAK_MAX || opt->draw_patience < 0 || opt->draw_patience > END_STREAK_MAX) return SZ_ERR_INVALID;
         if (opt->resign_min_ply < 0 || opt->draw_min_ply < 0) return SZ_ERR_INVALID;
-        if (e->gumbel_next_on) return SZ_ERR_INVALID;                       // not combined with the Gumbel root search (sz_set_gumbel)
     }
+    OptionState p = option_state(e);
+    p.endings = opt != nullptr;
+    int rc = option_refusal(e, p);
+    if (rc) return rc;
     ENGINE_GUARD(e);
     hipStream_t s = (hipStream_t)stream;
-    bool busy = false;
-    int rc = search_in_progress(e, s, &busy);
-    if (rc) return rc;
-    if (busy) return SZ_ERR_STATE;                                          // only between searches
+    if ((rc = between_searches(e, s))) return rc;
     if (!opt) { e->end_on = 0; return SZ_OK; }
     const size_t B = e->v.B;
     if (!e->eo.state) {                                                     // the first enabling call: state, flags, last-play readouts, counters
@@ -2357,18 +2327,7 @@ int sz_fetch_endings(sz_engine* e, uint8_t* kind, double* mover_value, int32_t* 
     return SZ_OK;
 }
 
-int sz_ending_stats(sz_engine* e, uint64_t out[4], void* stream) {
-    if (!e || !out) return SZ_ERR_INVALID;
-    out[0] = out[1] = out[2] = out[3] = 0;
-    if (!e->eo.stat) return SZ_OK;                                          // the option was never on
-    ENGINE_GUARD(e);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<unsigned long long> h((size_t)e->v.B * 4);
-    HIPCHK(hipMemcpyAsync(h.data(), e->eo.stat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (size_t b = 0; b < (size_t)e->v.B; b++) for (int k = 0; k < 4; k++) out[k] += h[4 * b + k];
-    return SZ_OK;
-}
+int sz_ending_stats(sz_engine* e, uint64_t out[4], void* stream) { return sum_board_counters(e, e ? e->eo.stat : nullptr, 4, out, stream); }
 
 int sz_pending_boards(sz_engine* e, int32_t* n_out, void* stream) {
     if (!e || !n_out) return SZ_ERR_INVALID;
@@ -2413,24 +2372,10 @@ int sz_root_children(sz_engine* e, int32_t* action_dev, int32_t* visits_dev, int
 int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    if (e->gumbel_on) {                                                     // sz_set_gumbel: the search that ended ran under it
-        hipLaunchKernelGGL((k_play<false, GumbelOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->go);
-        HIPCHK(hipGetLastError());
-        return SZ_OK;
-    }
-    with_search_options(e, [&](auto, auto solve, auto forced) {
-        constexpr bool SOLVE = decltype(solve)::value;
-        if (e->end_on) {                                                    // sz_set_endings: the ENDING instantiations
-            EndOpts eo = e->eo;
-            if (!SOLVE) eo.o.proven = 0;                                    // ignored while the solver is off
-            if constexpr (decltype(forced)::value)
-                hipLaunchKernelGGL((k_play<SOLVE, ForcedOpts, EndOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->fo, eo);
-            else
-                hipLaunchKernelGGL((k_play<SOLVE, EndOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, eo);
-        } else if constexpr (decltype(forced)::value)
-            hipLaunchKernelGGL((k_play<SOLVE, ForcedOpts>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, e->fo);
-        else
-            hipLaunchKernelGGL(k_play<SOLVE>, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev);
+    with_search_options(e, [&](auto, auto solve, auto... o) {
+        std::apply([&](auto... k) {
+            hipLaunchKernelGGL((k_play<decltype(solve)::value, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, k...);
+        }, pick<ForcedOpts, GumbelOpts, EndOpts>(o...));                    // first-play urgency acts in the descent alone
     });
     HIPCHK(hipGetLastError());
     return SZ_OK;

@@ -1,5 +1,5 @@
 """Plain-Python restatement of first-play urgency for unvisited children (sz_set_fpu / sz_debug_select_fpu, args["fpu"], a NON-REFERENCE
-option; include/sigmazero.h is the specification).  It is what wave_select_child_fpu, the selection of k_search_step<.., FpuOpts> (the
+option; include/sigmazero.h is the specification).  It is what wave_select_child<.., true>, the selection of k_search_step<.., FpuOpts> (the
 descent-only launch of sz_search_begin included) in csrc/sz_engine.hip, is held to, bit for bit (tests/test_gpu_fpu.py).  Built on forcedref
 (Search / Game), which stays as it is:
 
