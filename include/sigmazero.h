@@ -504,11 +504,11 @@ int sz_debug_select_fpu(const int32_t* offsets_dev, const int32_t* vc_dev, const
  *   policy       sumN = sum of N_c.  v_mix = v01 when sumN is 0, else (v01 + (double)sumN * (sum over N_c >= 1 of (double)P_c * q_c /
  *                sum over N_c >= 1 of (double)P_c)) / (1.0 + (double)sumN).  cq_c = q_c if N_c >= 1 else v_mix; z_c = logit_c + sigma(cq_c);
  *                zmax = the maximum of z_c; e_c = sexp(z_c - zmax); policy_target[b][c] = (float)(e_c / sum of e) for c < K and 0 beyond.
- * Not done, each a follow-up: the paper's deterministic completed-Q selection below the root; recording fast plies as training samples; and
- * every combination refused below.
+ * Below the root the paper's deterministic completed-Q selection is an option of its own on top of this one, sz_set_gumbel_tree below.
+ * Not done, each a follow-up: recording fast plies as training samples; and every combination refused below.
  * Works with learning 0 and 1, budgets and visit targets on an engine without reuse_subtree (the rule reads the board's goal), sz_compact,
- * sz_compact_searching, sz_play_moves and sz_set_fpu (below the root FPU acts as without the option; its root_mode is not consulted, Gumbel
- * decides there).  Held bit for bit to the host restatement tests/gumbelref.py by tests/test_gpu_gumbel.py.  Strength effect unmeasured. */
+ * sz_compact_searching, sz_play_moves and sz_set_fpu (below the root FPU acts as without the option, unless sz_set_gumbel_tree decides there; its root_mode
+ * is not consulted, Gumbel decides there).  Held bit for bit to the host restatement tests/gumbelref.py by tests/test_gpu_gumbel.py.  Strength effect unmeasured. */
 typedef struct sz_gumbel_options { int32_t max_considered; float c_visit; float c_scale; } sz_gumbel_options;   /* 12 bytes */
 /* opt == NULL switches the option off.  g_dev: device array [n_boards][SZ_MAX_MOVES] of f64 Gumbel(0,1) draws, indexed by root child in action
  * order as gamma_dev is; NULL = all zeros, a deterministic search for match play.  It is read at every root selection and by sz_play: the
@@ -536,6 +536,49 @@ int sz_debug_gumbel(const double* x_dev, double* slog_out_dev, double* sexp_out_
                     const int32_t* visit_dev, const int32_t* goal_dev, const float* root_value_dev, const sz_gumbel_options* opts_dev,
                     int32_t* selected_out_dev, int32_t* fallback_out_dev, int32_t* final_out_dev, float* policy_out_dev, double* v_mix_out_dev,
                     int32_t n_cases, void* stream);
+
+/* NON-REFERENCE option, off by default, on top of sz_set_gumbel: COMPLETED-Q SELECTION BELOW THE ROOT (Danihelka et al., section 5, "Full
+ * Gumbel").  With sz_set_gumbel alone every inner node spends its visits by PUCT, a rule tuned for hundreds of visits whose counts at 16 to 64
+ * simulations are mostly its c_puct * P * sqrt(N) term.  With this flag an inner node picks the child whose share of the visits lags furthest
+ * behind the completed-Q improved policy of that node: deterministic, stateless per simulation, one wavefront per board.  Never switched on,
+ * every kernel that runs today runs unchanged: the flag is one more instantiation, k_search_step<false, false, GumbelTreeOpts>, which also
+ * keeps every expanded node's network value, [n_boards][num_searches + 2] f32 by node id; k_play and k_search_begin have no variant.
+ * The rule applies wherever a child is selected at depth d >= 1 of a descent, in a search begun with Gumbel on and the flag on.  The parent is
+ * node p with children c = 0..K-1, N_c, W_c, P_c as stored; vhat_p is the f32 network value sz_search_step read from value_dev when it
+ * expanded p.  All arithmetic is f64, every operator one IEEE rounding (-ffp-contract=off); slog, sexp, q_c and the sigma factor are
+ * sz_set_gumbel's:
+ *   wsum(t)      lane l (0..63) starts from 0.0 and adds t_c for c = l, l+64, l+128, l+192 (< K), ascending; then for off = 32, 16, 8, 4, 2, 1:
+ *                v_l = v_l + v_(l xor off).  Every lane ends with the same bits because f64 addition commutes (the argument of sz_set_fpu's
+ *                prior mass); the result is read back through readfirstlane.  NOT the sequential sum of sz_play's improved policy, which runs
+ *                once per ply: this one runs at every depth of every descent.
+ *   q_c          = 0.5 - 0.5 * (W_c / (double)N_c) for N_c >= 1.
+ *   maxN         = max_c N_c;  sf = ((double)c_visit + (double)maxN) * (double)c_scale;  sumN = the integer sum of N_c, exact.
+ *   v01          = 0.5 + 0.5 * (double)vhat_p.
+ *   pq           = wsum(N_c >= 1 ? (double)P_c * q_c : 0.0);  pm = wsum(N_c >= 1 ? (double)P_c : 0.0).
+ *   v_mix        = v01 when sumN == 0, else (v01 + (double)sumN * (pq / pm)) / (1.0 + (double)sumN).
+ *   z_c          = slog((double)P_c) + sf * (N_c >= 1 ? q_c : v_mix);  zmax = max_c z_c;  e_c = sexp(z_c - zmax);  se = wsum(e_c), at least 1.
+ *   score_c      = (e_c / se) - ((double)N_c / (1.0 + (double)sumN)).
+ *   selection    the arg-max of score_c, the first maximum in child order (the loop and butterfly tie-break of the root's selection).
+ * Terminal children are scored like any other.  The precondition on P_c is slog's own: positive.  Under the rule neither c_puct nor
+ * sz_set_fpu's tree setting is consulted (its root setting already is not): FPU is accepted beside the rule and ignored.  Depth 0
+ * (sz_set_gumbel's root selection), sz_play and the policy target are unchanged.
+ * Latched by sz_search_begin like sz_set_gumbel.  SZ_ERR_INVALID: e is NULL.  SZ_ERR_STATE: a call during a search (nothing is changed
+ * then); enabling while Gumbel is not on for the next search.  enable == 0 is always accepted between searches.  sz_set_gumbel(NULL) clears
+ * the flag; sz_set_gumbel(opt != NULL) leaves it as it is.  The node values and the counter are allocated by the first enabling call.
+ * Everything sz_set_gumbel refuses stays refused.  Held bit for bit to the host restatement tests/gumbeltreeref.py by
+ * tests/test_gpu_gumbel_tree.py.  Strength effect unmeasured. */
+int sz_set_gumbel_tree(sz_engine* e, int32_t enable, void* stream);
+/* cumulative over all boards: out[0] selections below the root made by the rule.  sz_gumbel_stats is unchanged. */
+int sz_gumbel_tree_stats(sz_engine* e, uint64_t out[1], void* stream);
+/* test: the DEVICE function of the rule on caller-supplied cases, one wavefront per case, in the manner of sz_debug_gumbel.  Case c owns children
+ * offsets[c]..offsets[c+1] (1..SZ_MAX_MOVES each, else selected_out -1) of vc (N), value_sum (f64) and prior (f32); node_value[c] is vhat_p and
+ * opts[c] the constants (max_considered is not read).  Writes every child's score, the selected child and v_mix.  All device pointers. */
+int sz_debug_gumbel_tree(const int32_t* offsets_dev, const int32_t* vc_dev, const double* value_sum_dev, const float* prior_dev, const float* node_value_dev,
+                         const sz_gumbel_options* opts_dev, double* score_out_dev, int32_t* selected_out_dev, double* v_mix_out_dev, int32_t n_cases, void* stream);
+/* test: the stored network value of every node of one board's tree, rows in sz_debug_tree's order; a node that was never expanded (unvisited,
+ * terminal, or waiting for the network) has NaN.  HOST pointers; max_nodes 0 / node_value NULL only counts.  SZ_ERR_STATE unless the search
+ * begun last runs under sz_set_gumbel_tree. */
+int sz_debug_tree_values(sz_engine* e, int32_t board, int32_t max_nodes, float* node_value, int32_t* n_out, void* stream);
 
 /* NON-REFERENCE option, off by default: RESIGNATION and ADJUDICATED GAME ENDINGS (AlphaZero, lc0, KataGo).  A self-play cycle lasts as long
  * as its longest game, and a game the rules have not ended yet is cut by the host without a result.  With the option on, sz_play ends a

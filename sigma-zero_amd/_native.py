@@ -81,6 +81,10 @@ EXPORTS = {
     "sz_fetch_gumbel": (C.c_int, [C.c_void_p] * 5),
     "sz_gumbel_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "sz_debug_gumbel": (C.c_int, [C.c_void_p] * 19 + [C.c_int32, C.c_void_p]),
+    "sz_set_gumbel_tree": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "sz_gumbel_tree_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_debug_gumbel_tree": (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]),
+    "sz_debug_tree_values": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_set_endings": (C.c_int, [C.c_void_p, C.POINTER(sz_ending_options), C.c_void_p, C.c_void_p]),
     "sz_fetch_endings": (C.c_int, [C.c_void_p] * 7),
     "sz_ending_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

@@ -29,6 +29,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <cmath>
+#include <limits>
 #include <tuple>
 #include <type_traits>
 #include <vector>
@@ -332,6 +333,93 @@ __device__ __forceinline__ int wave_select_root_gumbel(const EdgeStat* ch, const
     *fallback = bi < 0;
     if (bi < 0) bi = wave_gumbel_best(ch, g, n, -1, sf);
     return bi;
+}
+
+// NON-REFERENCE option (sz_set_gumbel_tree, on top of sz_set_gumbel): what k_search_step<false, false, GumbelTreeOpts> takes in GumbelOpts' place.
+// k_play and k_search_begin have no variant: sz_play receives the GumbelOpts part.  FpuOpts is never beside it: under the rule neither of
+// sz_set_fpu's sites is consulted.
+struct GumbelTreeOpts : GumbelOpts {
+    float* nval;                // [B][n_cap] the network value of every node by node id, written where the node is expanded
+    unsigned long long* tstat;  // [B] selections below the root made by the rule
+};
+// the GumbelOpts of a pack that holds GumbelOpts or GumbelTreeOpts
+template <typename F, typename... R>
+__device__ __forceinline__ const GumbelOpts& gumbel_of(const F& f, const R&... r) {
+    if constexpr (std::is_base_of_v<GumbelOpts, F>) return f; else return gumbel_of(r...);
+}
+
+// wsum of sz_set_gumbel_tree: the lanes' partial sums through the xor butterfly.  f64 addition commutes, so all 64 lanes end with the same bits;
+// read back through readfirstlane so that the compiler knows.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+    return uni_f64(v);
+}
+
+// selection below the root under sz_set_gumbel_tree (include/sigmazero.h is the rule): the arg-max over the children ch[0..n), n >= 1, of
+// softmax(slog(P_c) + sigma(completed q_c))_c - N_c / (1 + sumN), first maximum, wave_gumbel_best's loop and butterfly tie-break.  vhat: the
+// parent's own network value.  Lanes = children, up to four per lane, whose z_c / e_c stay in registers.  score_out [n] and vmix_out (both
+// optional, the test hook) receive every child's score and v_mix.
+__device__ __forceinline__ int wave_select_tree_gumbel(const EdgeStat* ch, int n, const sz_gumbel_options& o, float vhat, double* score_out, double* vmix_out) {
+    constexpr int R = (SZ_MAX_CHILDREN + 63) / 64;
+    const int lane = lane_id();
+    int maxN = 0, sumN = 0; double pq = 0.0, pm = 0.0;
+    for (int c = lane; c < n; c += 64) {
+        const EdgeStat s = ch[c];
+        if (s.N > maxN) maxN = s.N;
+        sumN += s.N;
+        double tq = 0.0, tm = 0.0;
+        if (s.N >= 1) { tq = (double)s.P * gumbel_q(s); tm = (double)s.P; }
+        pq = pq + tq; pm = pm + tm;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int om = __shfl_xor(maxN, off); if (om > maxN) maxN = om;
+        sumN += __shfl_xor(sumN, off);
+    }
+    maxN = uni(maxN); sumN = uni(sumN);
+    pq = wave_sum_f64(pq); pm = wave_sum_f64(pm);
+    const double sf = gumbel_sigma_factor(o, maxN);
+    const double v01 = 0.5 + 0.5 * (double)vhat;
+    double vmix = v01;
+    if (sumN != 0) vmix = (v01 + (double)sumN * (pq / pm)) / (1.0 + (double)sumN);
+    double z[R]; double zmax = 0.0; bool any = false;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        const int c = lane + 64 * j;
+        z[j] = 0.0;
+        if (c < n) {
+            const EdgeStat s = ch[c];
+            z[j] = sz_slog((double)s.P) + sf * (s.N >= 1 ? gumbel_q(s) : vmix);
+            if (!any || z[j] > zmax) { zmax = z[j]; any = true; }
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double oz = __shfl_xor(zmax, off); const int oa = __shfl_xor((int)any, off);
+        if (oa && (!any || oz > zmax)) { zmax = oz; any = true; }
+    }
+    zmax = uni_f64(zmax);
+    double se = 0.0;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        if (lane + 64 * j < n) { z[j] = sz_sexp(z[j] - zmax); se = se + z[j]; }
+    }
+    se = wave_sum_f64(se);
+    const double dn = 1.0 + (double)sumN;
+    double best = 0.0; int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        const int c = lane + 64 * j;
+        if (c < n) {
+            const double sc = (z[j] / se) - ((double)ch[c].N / dn);
+            if (score_out) score_out[c] = sc;
+            if (bi == 0x7fffffff || sc > best) { best = sc; bi = c; }
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        double ob = __shfl_xor(best, off); int oi = __shfl_xor(bi, off);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+    }
+    if (vmix_out && lane == 0) *vmix_out = vmix;
+    return uni(bi);
 }
 
 // sz_play on a Gumbel board: the move (the best child among the most visited) and the completed-Q improved policy of the root's children
@@ -942,14 +1030,18 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // (without FpuOpts through wave_select_root_forced, which is that and the arg-max).
 // FO has GumbelOpts (sz_set_gumbel, VL = SOLVE = false only, never with ForcedOpts): the selection at depth 0 is wave_select_root_gumbel, and the
 // root's network value is kept when the root is expanded.
+// FO = GumbelTreeOpts (sz_set_gumbel_tree, in GumbelOpts' place and alone): on top of that every expanded node's network value is kept by node
+// id, and the selection at depth >= 1 is wave_select_tree_gumbel, which reads the parent's.
 // FO has FpuOpts (sz_set_fpu): the arg-max that decides otherwise scores unvisited children by the site's first-play value, the root's at
 // depth 0 and the tree's below.
 template <bool VL, bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb, FO... fo) {
     constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
     constexpr bool FPU = has_opt<FpuOpts, FO...>;
-    constexpr bool GUMBEL = has_opt<GumbelOpts, FO...>;
+    constexpr bool GTREE = has_opt<GumbelTreeOpts, FO...>;
+    constexpr bool GUMBEL = has_opt<GumbelOpts, FO...> || GTREE;
     static_assert(!GUMBEL || (!VL && !SOLVE && !FORCED), "sz_set_gumbel refuses leaf batching, the solver and forced playouts");
+    static_assert(!GTREE || !FPU, "sz_set_gumbel_tree consults neither site of sz_set_fpu");
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -966,6 +1058,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     unsigned long long n_stop = 0, n_proved = 0;                // solver: simulations ended on a proven non-terminal node, nodes proven by the update
     unsigned long long n_forced = 0;                            // forced playouts: root selections decided by a forced child
     unsigned long long n_gumbel = 0, n_fallback = 0;            // Gumbel: root selections made by the rule, of them over all children
+    unsigned long long n_gtree = 0;                             // sz_set_gumbel_tree: selections below the root made by the rule
     int err = 0;
     STEP_STAMP(0);
 
@@ -1060,7 +1153,11 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             n_edges += kept;
             (void)node;
         const double val = (double)value[lf.row];                        // node.value = value.item()
-        if constexpr (GUMBEL) { if (d == 0 && lane == 0) opt_of<GumbelOpts>(fo...).vhat[b] = value[lf.row]; }     // sz_set_gumbel: the root's network value
+        if constexpr (GUMBEL) { if (d == 0 && lane == 0) gumbel_of(fo...).vhat[b] = value[lf.row]; }     // sz_set_gumbel: the root's network value
+        if constexpr (GTREE) {                                          // sz_set_gumbel_tree: every node's, read by selections later in this launch
+            if (lane == 0 && node >= 0 && node < v.n_cap) opt_of<GumbelTreeOpts>(fo...).nval[(size_t)b * v.n_cap + node] = value[lf.row];
+            __threadfence_block();
+        }
         if constexpr (VL) {                                             // its descent is no longer in flight
             for (int j = lane; j <= d; j += 64) vb.vk[(size_t)b * v.e_cap + path[j]] -= 1;
         }
@@ -1101,10 +1198,18 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             if (GUMBEL && d == 0) {
                 // sz_set_gumbel: only depth 0 changes.  One leaf per step and nothing in flight: sims - 1 root-child visits were made before this one
                 if constexpr (GUMBEL) {
-                    const GumbelOpts& go = opt_of<GumbelOpts>(fo...);
+                    const GumbelOpts& go = gumbel_of(fo...);
                     bool fallback;
                     bi = wave_select_root_gumbel(bp.es + m.first, go.g ? go.g + (size_t)b * SZ_MAX_MOVES : nullptr, mn, sims - 1, budget, go.o, &fallback);
                     n_gumbel++; n_fallback += fallback ? 1 : 0;
+                }
+            } else if (GTREE) {
+                // sz_set_gumbel_tree: completed-Q selection below the root, with the parent's own network value (a parent with children was expanded)
+                if constexpr (GTREE) {
+                    const GumbelTreeOpts& gt = opt_of<GumbelTreeOpts>(fo...);
+                    const float vh = __int_as_float(uni(__float_as_int(gt.nval[(size_t)b * v.n_cap + uni(m.node)])));
+                    bi = wave_select_tree_gumbel(bp.es + m.first, mn, gt.o, vh, nullptr, nullptr);
+                    n_gtree++;
                 }
             } else if (FORCED && !FPU && d == 0 && (status & ST_FORCED)) {
                 if constexpr (FORCED)
@@ -1203,7 +1308,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if constexpr (VL) c->n_pend = n_pend;
         if constexpr (SOLVE) { v.sstat[(size_t)b * 2] += n_stop; v.sstat[(size_t)b * 2 + 1] += n_proved; }
         if constexpr (FORCED) opt_of<ForcedOpts>(fo...).stat[(size_t)b * 2] += n_forced;
-        if constexpr (GUMBEL) { opt_of<GumbelOpts>(fo...).stat[(size_t)b * 2] += n_gumbel; opt_of<GumbelOpts>(fo...).stat[(size_t)b * 2 + 1] += n_fallback; }
+        if constexpr (GUMBEL) { gumbel_of(fo...).stat[(size_t)b * 2] += n_gumbel; gumbel_of(fo...).stat[(size_t)b * 2 + 1] += n_fallback; }
+        if constexpr (GTREE) opt_of<GumbelTreeOpts>(fo...).tstat[b] += n_gtree;
     }
 }
 
@@ -1603,6 +1709,21 @@ __global__ __launch_bounds__(64) void k_debug_gumbel(const double* x, double* sl
     if (lane == 0) { selected_out[cs] = bi; fallback_out[cs] = fallback ? 1 : 0; final_out[cs] = mv; vmix_out[cs] = vmix; }
 }
 
+// test hook (sz_debug_gumbel_tree): wave_select_tree_gumbel, the function k_search_step<.., GumbelTreeOpts> calls, on caller-supplied cases, one
+// wave per case
+__global__ __launch_bounds__(64) void k_debug_gumbel_tree(const int* offsets, const int* vc, const double* wsum, const float* prior, const float* vhat,
+                                                          const sz_gumbel_options* opts, double* score_out, int* selected_out, double* vmix_out) {
+    extern __shared__ u64 lds64[];
+    EdgeStat* ch = (EdgeStat*)lds64;
+    const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
+    if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) selected_out[cs] = -1; return; }
+    for (int c = lane; c < n; c += 64) { EdgeStat s; s.W = wsum[lo + c]; s.N = vc[lo + c]; s.P = prior[lo + c]; ch[c] = s; }
+    __syncthreads();
+    const sz_gumbel_options o = opts[cs];
+    const int bi = wave_select_tree_gumbel(ch, n, o, vhat[cs], score_out + lo, vmix_out + cs);
+    if (lane == 0) selected_out[cs] = bi;
+}
+
 // test hook (sz_debug_endings): wave_ending, the function k_play<.., EndOpts> calls, on caller-supplied cases, one wave per case
 __global__ __launch_bounds__(64) void k_debug_endings(const int* offsets, const int* vc, const double* wsum, const int8_t* root_proven, const uint8_t* colour,
                                                       const int* ply, const uint8_t* holdout, const int* state_in, const sz_ending_options* opts,
@@ -1634,6 +1755,7 @@ struct Latched {
     sz_fpu_options fpu;             // all zero = off; a mode other than SZ_FPU_REFERENCE selects the FPU instantiations
     int gumbel_on;                  // != 0 selects the GUMBEL instantiations ...
     sz_gumbel_options gumbel; const double* gumbel_g;      // ... which run with these
+    int gumbel_tree;                // sz_set_gumbel_tree: != 0 (only beside gumbel_on) selects k_search_step<false, false, GumbelTreeOpts>
 };
 
 struct sz_engine {
@@ -1657,6 +1779,8 @@ struct sz_engine {
     Latched next, cur;              // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel: what the next sz_search_begin takes up, and what it took up last
     ForcedOpts fo;                  // sz_set_forced_playouts: fo.boards [n_boards] and fo.stat [n_boards][2], allocated by the first enabling call
     GumbelOpts go;                  // sz_set_gumbel: its arrays, allocated by the first enabling call (go.stat != NULL from then on)
+    float* gt_nval;                 // sz_set_gumbel_tree: the node values [n_boards][n_cap] and the counter [n_boards], allocated by the first
+    unsigned long long* gt_stat;    //     enabling call (gt_stat != NULL from then on)
     int end_on;                     // sz_set_endings: sz_play runs the ENDING instantiations of k_play
     EndOpts eo;                     // ... with these; its arrays are allocated by the first enabling call (eo.state != NULL from then on)
 };
@@ -1684,12 +1808,13 @@ template <typename T> static int dalloc(sz_engine* e, T** p, size_t count) {
 // The one place that maps the options in force to a kernel instantiation, for sz_search_begin, sz_search_step and sz_play alike.  f(vl, solve, o...)
 // is called with two std::bool_constants, VL = leaf batching on (vb.L > 1; instantiations without it take an empty Batch) and SOLVE = the solver
 // on, and with the option structs in force, in the order the kernels take them: ForcedOpts or else GumbelOpts (the search begun last, e->cur;
-// under Gumbel VL = SOLVE = false, which the setters' refusals see to), FpuOpts (e->cur), EndOpts (sz_set_endings; `proven` cleared while the
+// under Gumbel VL = SOLVE = false, which the setters' refusals see to; GumbelTreeOpts in its place and no FpuOpts under sz_set_gumbel_tree),
+// FpuOpts (e->cur), EndOpts (sz_set_endings; `proven` cleared while the
 // solver is off; never beside GumbelOpts).  Each kernel takes the members of the pack that concern it: pick below.
 template <typename F> static void with_search_options(const sz_engine* e, F&& f) {
     const Latched& c = e->cur;
     auto endings = [&](auto vl, auto solve, auto... o) {
-        if constexpr (has_opt<GumbelOpts, decltype(o)...>) f(vl, solve, o...);
+        if constexpr (has_opt<GumbelOpts, decltype(o)...> || has_opt<GumbelTreeOpts, decltype(o)...>) f(vl, solve, o...);
         else if (e->end_on) { EndOpts eo = e->eo; if (!decltype(solve)::value) eo.o.proven = 0; f(vl, solve, o..., eo); }
         else f(vl, solve, o...);
     };
@@ -1699,7 +1824,13 @@ template <typename F> static void with_search_options(const sz_engine* e, F&& f)
     auto forced = [&](auto vl, auto solve) {
         if (c.forced_k > 0.0f) { ForcedOpts fo = e->fo; fo.k = c.forced_k; fpu(vl, solve, fo); } else fpu(vl, solve);
     };
-    if (c.gumbel_on) { GumbelOpts go = e->go; go.o = c.gumbel; go.g = c.gumbel_g; fpu(std::false_type{}, std::false_type{}, go); }
+    if (c.gumbel_on) {
+        GumbelOpts go = e->go; go.o = c.gumbel; go.g = c.gumbel_g;
+        if (c.gumbel_tree) {                                                // sz_set_gumbel_tree: in GumbelOpts' place, and FpuOpts is left out: neither site is consulted
+            GumbelTreeOpts gt; static_cast<GumbelOpts&>(gt) = go; gt.nval = e->gt_nval; gt.tstat = e->gt_stat;
+            endings(std::false_type{}, std::false_type{}, gt);
+        } else fpu(std::false_type{}, std::false_type{}, go);
+    }
     else if (e->vb.L > 1) { if (e->solver) forced(std::true_type{}, std::true_type{}); else forced(std::true_type{}, std::false_type{}); }
     else                  { if (e->solver) forced(std::false_type{}, std::true_type{}); else forced(std::false_type{}, std::false_type{}); }
 }
@@ -1708,6 +1839,9 @@ template <typename... Keep, typename O> static auto pick1(const O& o) {
     if constexpr (has_opt<O, Keep...>) return std::tuple<O>(o); else return std::tuple<>();
 }
 template <typename... Keep, typename... O> static auto pick(const O&... o) { return std::tuple_cat(pick1<Keep...>(o)...); }
+// sz_play's view of a member of the pack: the tree rule (sz_set_gumbel_tree) acts in the descent alone, k_play takes its GumbelOpts part
+template <typename O> static const O& play_opt(const O& o) { return o; }
+static GumbelOpts play_opt(const GumbelTreeOpts& o) { return o; }
 
 extern "C" {
 
@@ -2043,7 +2177,7 @@ static void launch_step(sz_engine* e, const float* policy, const float* value, v
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         std::apply([&](auto... k) {
             hipLaunchKernelGGL((k_search_step<VL, SOLVE, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, k...);
-        }, pick<ForcedOpts, GumbelOpts, FpuOpts>(o...));                    // the ending rules live in sz_play alone
+        }, pick<ForcedOpts, GumbelOpts, GumbelTreeOpts, FpuOpts>(o...));    // the ending rules live in sz_play alone
     });
 }
 
@@ -2230,7 +2364,7 @@ int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_de
     hipStream_t s = (hipStream_t)stream;
     int rc = between_searches(e, s);
     if (rc) return rc;
-    if (!opt) { e->next.gumbel_on = 0; e->next.gumbel_g = nullptr; return SZ_OK; }
+    if (!opt) { e->next.gumbel_on = 0; e->next.gumbel_g = nullptr; e->next.gumbel_tree = 0; return SZ_OK; }      // ... and sz_set_gumbel_tree's flag goes with it
     if (refused) return refused;                                            // root noise is on: SZ_ERR_STATE, after the question whether the engine searches
     if (!e->go.stat) {                                                      // the first enabling call: the per-board outputs and the counters
         const size_t B = e->v.B;
@@ -2262,6 +2396,29 @@ int sz_fetch_gumbel(sz_engine* e, float* policy_target, double* v_mix, float* ro
 }
 
 int sz_gumbel_stats(sz_engine* e, uint64_t out[2], void* stream) { return sum_board_counters(e, e ? e->go.stat : nullptr, 2, out, stream); }
+
+int sz_set_gumbel_tree(sz_engine* e, int32_t enable, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = between_searches(e, s);
+    if (rc) return rc;
+    if (!enable) { e->next.gumbel_tree = 0; return SZ_OK; }
+    if (!e->next.gumbel_on) return SZ_ERR_STATE;                            // the rule is a part of the Gumbel search
+    if (!e->gt_stat) {                                                      // the first enabling call: the node values and the counter
+        const size_t B = e->v.B;
+        float* nv = nullptr; unsigned long long* st = nullptr;
+        if ((rc = dalloc(e, &nv, B * e->v.n_cap)) || (rc = dalloc(e, &st, B))) return rc;
+        HIPCHK(hipMemsetAsync(nv, 0, B * e->v.n_cap * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(st, 0, B * sizeof(unsigned long long), s));
+        HIPCHK(hipStreamSynchronize(s));
+        e->gt_nval = nv; e->gt_stat = st;
+    }
+    e->next.gumbel_tree = 1;
+    return SZ_OK;
+}
+
+int sz_gumbel_tree_stats(sz_engine* e, uint64_t out[1], void* stream) { return sum_board_counters(e, e ? e->gt_stat : nullptr, 1, out, stream); }
 
 int sz_forced_stats(sz_engine* e, uint64_t out[2], void* stream) { return sum_board_counters(e, e ? e->fo.stat : nullptr, 2, out, stream); }
 
@@ -2375,7 +2532,7 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     with_search_options(e, [&](auto, auto solve, auto... o) {
         std::apply([&](auto... k) {
             hipLaunchKernelGGL((k_play<decltype(solve)::value, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, k...);
-        }, pick<ForcedOpts, GumbelOpts, EndOpts>(o...));                    // first-play urgency acts in the descent alone
+        }, pick<ForcedOpts, GumbelOpts, EndOpts>(play_opt(o)...));          // first-play urgency acts in the descent alone
     });
     HIPCHK(hipGetLastError());
     return SZ_OK;
@@ -2499,6 +2656,36 @@ int sz_debug_tree_proven(sz_engine* e, int32_t board, int32_t max_nodes, int8_t*
     return SZ_OK;
 }
 
+int sz_debug_tree_values(sz_engine* e, int32_t board, int32_t max_nodes, float* node_value, int32_t* n_out, void* stream) {
+    if (!e || board < 0 || board >= e->v.B || !n_out) return SZ_ERR_INVALID;
+    if (!e->gt_nval || !e->cur.gumbel_tree) return SZ_ERR_STATE;            // the search begun last kept no node values
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    Ctl c;
+    HIPCHK(hipMemcpyAsync(&c, e->v.ctl + board, sizeof c, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n_out = 0;
+    if (!(c.status & ST_SEARCHING) || c.n_edges <= 0) return SZ_OK;
+    std::vector<EdgeMeta> em(c.n_edges);
+    std::vector<float> nv(e->v.n_cap);
+    HIPCHK(hipMemcpyAsync(em.data(), e->v.em + (size_t)board * e->v.e_cap, em.size() * sizeof(EdgeMeta), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(nv.data(), e->gt_nval + (size_t)board * e->v.n_cap, nv.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<int> stack;                                 // the walk of sz_debug_tree
+    int n = 0;
+    stack.push_back(0);
+    while (!stack.empty()) {
+        const int ed = stack.back(); stack.pop_back();
+        // a node is expanded exactly when its edge has a child span; its value was stored then.  Unvisited, terminal and pending nodes: NaN
+        const bool expanded = em[ed].first >= 0 && em[ed].node >= 0 && em[ed].node < e->v.n_cap;
+        if (n < max_nodes && node_value) node_value[n] = expanded ? nv[em[ed].node] : std::numeric_limits<float>::quiet_NaN();
+        n++;
+        if (em[ed].first >= 0) for (int k = (int)em[ed].n - 1; k >= 0; k--) stack.push_back(em[ed].first + k);
+    }
+    *n_out = n;
+    return SZ_OK;
+}
+
 int sz_debug_select(const int32_t* offsets_dev, const int32_t* vc_dev, const double* value_sum_dev, const float* prior_dev, const int32_t* parent_visits_dev,
                     const float* c_dev, float* ucb_out_dev, int32_t* argmax_out_dev, int32_t n_cases, void* stream) {
     if (!offsets_dev || !vc_dev || !value_sum_dev || !prior_dev || !parent_visits_dev || !c_dev || !ucb_out_dev || !argmax_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
@@ -2546,6 +2733,16 @@ int sz_debug_gumbel(const double* x_dev, double* slog_out_dev, double* sexp_out_
     hipLaunchKernelGGL(k_debug_gumbel, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(double) + sizeof(float)), (hipStream_t)stream,
                        x_dev, slog_out_dev, sexp_out_dev, tnm_dev, level_out_dev, offsets_dev, vc_dev, value_sum_dev, prior_dev, g_dev, visit_dev, goal_dev,
                        root_value_dev, opts_dev, selected_out_dev, fallback_out_dev, final_out_dev, policy_out_dev, v_mix_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_gumbel_tree(const int32_t* offsets_dev, const int32_t* vc_dev, const double* value_sum_dev, const float* prior_dev, const float* node_value_dev,
+                         const sz_gumbel_options* opts_dev, double* score_out_dev, int32_t* selected_out_dev, double* v_mix_out_dev, int32_t n_cases, void* stream) {
+    if (n_cases <= 0 || !offsets_dev || !vc_dev || !value_sum_dev || !prior_dev || !node_value_dev || !opts_dev || !score_out_dev || !selected_out_dev ||
+        !v_mix_out_dev) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_gumbel_tree, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * sizeof(EdgeStat), (hipStream_t)stream,
+                       offsets_dev, vc_dev, value_sum_dev, prior_dev, node_value_dev, opts_dev, score_out_dev, selected_out_dev, v_mix_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

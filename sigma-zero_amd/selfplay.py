@@ -192,7 +192,7 @@ def gumbel_options_of(args):
     args["gumbel"] = {"m": int, "c_visit": x, "c_scale": y} (defaults 16 / 50 / 1) switches the root of every search from PUCT with root noise
     to Gumbel AlphaZero's rule (sz_set_gumbel): m root moves are sampled without replacement by Gumbel-top-k, the simulations are spent on
     them by sequential halving, play() takes the best of the most visited moves, and the policy target is the completed-Q improved policy
-    (fetch_gumbel) instead of the visit fractions.  Below the root nothing changes.  Refused with a reuse_subtree engine, leaves_per_step > 1,
+    (fetch_gumbel) instead of the visit fractions.  Below the root nothing changes unless args["gumbel_tree"] says so (gumbel_tree_of).  Refused with a reuse_subtree engine, leaves_per_step > 1,
     the solver, forced playouts, endings and root_dirichlet_alpha: each combination is a follow-up.  Checked in this order: the dict and its
     keys, m, c_visit, c_scale, the combinations.  Its effect on playing strength is unmeasured."""
     opt = args.get("gumbel")
@@ -218,7 +218,22 @@ def gumbel_options_of(args):
     return tuple(out)
 
 
-ENDING_KEYS = ("resign_value", "resign_patience", "resign_min_ply", "draw_value", "draw_patience", "draw_min_ply", "proven", "holdout")
+def gumbel_tree_of(args):
+    """args["gumbel_tree"], checked: True or False (absent: False).  NON-REFERENCE, default off.
+
+    args["gumbel_tree"] = True, a key of its own beside args["gumbel"], switches the selection below the root of every Gumbel search from PUCT
+    to the paper's deterministic completed-Q rule (sz_set_gumbel_tree): an inner node picks the child whose share of the visits lags furthest
+    behind the completed-Q improved policy of that node.  Neither C nor args["fpu"] is consulted there then.  Needs args["gumbel"].  Its
+    effect on playing strength is unmeasured."""
+    on = args.get("gumbel_tree", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError("args['gumbel_tree'] must be True or False, got %r" % (on,))
+    if on and args.get("gumbel") is None:
+        raise ValueError("args['gumbel_tree'] needs args['gumbel']: the rule is a part of the Gumbel search")
+    return bool(on)
+
+
+ENDING_KEYS =("resign_value", "resign_patience", "resign_min_ply", "draw_value", "draw_patience", "draw_min_ply", "proven", "holdout")
 ENDING_KINDS = {N.SZ_END_RESIGN: "resign", N.SZ_END_DRAW: "draw_adjudicated", N.SZ_END_PROVEN: "proven"}
 
 
@@ -311,6 +326,8 @@ class SelfPlayEngine:
         # NON-REFERENCE option (default off): Gumbel root search with sequential halving and the completed-Q policy target, see gumbel_options_of
         self.gumbel = gumbel_options_of(self.args)
         self._gumbel_g = None         # the device copy of the Gumbel draws in force (set_gumbel)
+        # NON-REFERENCE option (default off): completed-Q selection below the root of a Gumbel search, see gumbel_tree_of
+        self.gumbel_tree = gumbel_tree_of(self.args)
         # NON-REFERENCE option (default off): resignation and adjudicated game endings, see ending_options_of
         self.endings = ending_options_of(self.args)
         self.quiet = None             # boards whose next searches get no root noise (set_quiet; visit_targets mode)
@@ -367,6 +384,8 @@ class SelfPlayEngine:
             self.set_fpu(self.fpu)
         if self.gumbel is not None:    # g = None (a deterministic search) until set_gumbel hands over draws
             self.set_gumbel(self.gumbel)
+        if self.gumbel_tree:
+            self.set_gumbel_tree(True)
         if self.endings is not None:  # no holdout board until set_endings says otherwise
             self.set_endings(self.endings)
 
@@ -501,6 +520,20 @@ class SelfPlayEngine:
         N.check(N.lib().sz_set_gumbel(self._e, None if o is None else C.byref(o), _ptr(gd), self._stream()), "sz_set_gumbel")
         # the search that ended last still reads its own draws in play(): the previous copy stays alive for one more call
         self.gumbel, self._gumbel_g, self._gumbel_g_prev = (None if opts is None else tuple(opts)), gd, self._gumbel_g
+        if opts is None:
+            self.gumbel_tree = False  # sz_set_gumbel(NULL) clears sz_set_gumbel_tree's flag
+
+    def set_gumbel_tree(self, on):
+        """Completed-Q selection below the root of a Gumbel search (sz_set_gumbel_tree, a NON-REFERENCE option) from the next begin() on, until
+        changed or until set_gumbel(None).  Between searches only; switching it on needs Gumbel on; a refused call changes nothing."""
+        N.check(N.lib().sz_set_gumbel_tree(self._e, int(bool(on)), self._stream()), "sz_set_gumbel_tree")
+        self.gumbel_tree = bool(on)
+
+    def gumbel_tree_stats(self):
+        """selections below the root made by the completed-Q rule, all boards, cumulative (sz_gumbel_tree_stats)"""
+        out = (C.c_uint64 * 1)()
+        N.check(N.lib().sz_gumbel_tree_stats(self._e, out, self._stream()), "sz_gumbel_tree_stats")
+        return int(out[0])
 
     def fetch_gumbel(self):
         """sz_fetch_gumbel after play(): dict of policy [B, SZ_MAX_MOVES] f32 (the improved policy by root child, in fetch_ply()'s action
@@ -742,6 +775,15 @@ class SelfPlayEngine:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         N.check(N.lib().sz_debug_tree_proven(self._e, int(board), n.value, p(r), p(c), C.byref(n), self._stream()), "sz_debug_tree_proven")
         return r, c
+
+    def debug_tree_values(self, board):
+        """the stored network value of every node of one board's tree (f32, NaN where the node was never expanded), rows in debug_tree()'s
+        order (sz_debug_tree_values; a search under set_gumbel_tree only)"""
+        n = C.c_int32()
+        N.check(N.lib().sz_debug_tree_values(self._e, int(board), 0, None, C.byref(n), self._stream()), "sz_debug_tree_values")
+        val = np.zeros(n.value, np.float32)
+        N.check(N.lib().sz_debug_tree_values(self._e, int(board), n.value, val.ctypes.data_as(C.c_void_p), C.byref(n), self._stream()), "sz_debug_tree_values")
+        return val
 
     def debug_position(self, board):
         pos = np.zeros(10, np.uint64)

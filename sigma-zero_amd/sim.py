@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, ENDING_KINDS
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, gumbel_tree_of, ENDING_KINDS
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -118,6 +118,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     'actions' dict holds the completed-Q improved policy as Python floats instead of visit fractions.  With `learning` the Gumbel(0,1) draws
     g = -log(-log(u)) come per board and ply from a numpy Generator of its own; without it g is NULL, a deterministic search for match play.
     stats gets 'gumbel_fallbacks' (sz_gumbel_stats: root selections that found no child at their level, 0).  Strength effect unmeasured.
+    args["gumbel_tree"] = True (NON-REFERENCE, selfplay.gumbel_tree_of; needs args["gumbel"]): below the root of every Gumbel search the
+    completed-Q selection of sz_set_gumbel_tree replaces PUCT; the engine applies it and the per-ply set_gumbel leaves it on.  Strength effect unmeasured.
     gumbel_noise(game, ply) -> 218 floats: the Gumbel(0,1) draws of that game's root at that ply by root child, like `uniforms`; replaces
       the default above, with and without `learning`.
     holdout(game) -> bool: whether a game is a holdout game, like `uniforms`.  Default: a numpy Generator of its own, one draw per game in game
@@ -134,6 +136,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         raise ValueError("args['forced_playouts'] needs learning=True")
     end_opts = ending_options_of(args)
     gum = gumbel_options_of(args)
+    gumbel_tree_of(args)
     if gumbel_noise is not None and gum is None:
         raise ValueError("gumbel_noise needs args['gumbel']")
     if holdout is not None and end_opts is None:

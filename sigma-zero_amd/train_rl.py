@@ -462,7 +462,7 @@ def write_step_log(path, epoch, hist, lr_scheduler, append=True):
 
 def selfplay_args_of(a):
     """the self-play `args` dict of main()'s parsed flags `a`; nothing is checked here: the engine's option readers (selfplay.search_options_of,
-    visit_target_options_of, forced_playout_options_of, gumbel_options_of, ending_options_of, sim.playout_cap_of) refuse what does not go together"""
+    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, sim.playout_cap_of) refuse what does not go together"""
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
@@ -482,6 +482,8 @@ def selfplay_args_of(a):
         args["forced_playouts"] = a.forced_playouts
     if a.gumbel:
         args["gumbel"] = {"m": a.gumbel, "c_visit": a.gumbel_c_visit, "c_scale": a.gumbel_c_scale}
+    if a.gumbel_tree:
+        args["gumbel_tree"] = True
     if a.resign_patience or a.draw_patience or a.adjudicate_proven:
         end = {"resign_patience": a.resign_patience, "resign_min_ply": a.resign_min_ply, "draw_patience": a.draw_patience, "draw_min_ply": a.draw_min_ply,
                "proven": bool(a.adjudicate_proven), "holdout": a.ending_holdout}
@@ -548,6 +550,9 @@ def flag_parser():
                          "--reuse-subtree, leaf batching, the solver, --forced-playouts, the ending rules or --root-dirichlet-alpha; strength effect unmeasured")
     ap.add_argument("--gumbel-c-visit", type=float, default=50.0, metavar="X", help="with --gumbel: c_visit of sigma(q) = (c_visit + max N) * c_scale * q")
     ap.add_argument("--gumbel-c-scale", type=float, default=1.0, metavar="Y", help="with --gumbel: c_scale of sigma(q)")
+    ap.add_argument("--gumbel-tree", action="store_true",
+                    help="NON-REFERENCE, with --gumbel: below the root the paper's deterministic completed-Q selection replaces PUCT (args['gumbel_tree'], "
+                         "sz_set_gumbel_tree); strength effect unmeasured")
     ap.add_argument("--resign-value", type=float, default=None, metavar="V",
                     help="NON-REFERENCE: a game is resigned when the mover's most visited move had an expected outcome <= V (in [-1, 1]) in "
                          "--resign-patience of the mover's searches in a row (args['endings'], sz_set_endings); strength effect unmeasured")

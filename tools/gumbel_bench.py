@@ -1,7 +1,8 @@
 """The Gumbel root search (args["gumbel"], sz_set_gumbel): what the option costs per search step, on the GPU.  4096 boards from the start
 position, bf16 MFMA network with random-init weights, one search of 64 and one of 800 simulations per run.  Legs: the option off and on
-(seeded Gumbel draws), and, with --parent-tree DIR (a checkout of the parent commit with its library built), the default path of that
-checkout, so that "no default kernel changed" is also a measurement.  The legs run alternately (off, on[, parent], off, on, ...), one fresh
+(seeded Gumbel draws), `tree` = on with the completed-Q selection below the root as well (args["gumbel_tree"], sz_set_gumbel_tree), and, with
+--parent-tree DIR (a checkout of the parent commit with its library built), the default path of that
+checkout, so that "no default kernel changed" is also a measurement.  The legs run alternately (off, on, tree[, parent], off, on, ...), one fresh
 process per run under its own time limit, all in one session on one GPU; the first run that fails ends the tool.  Reported per run:
 
   ms per step       wall time of the search (begin + num_searches network calls and tree steps, synchronised) / num_searches
@@ -32,14 +33,16 @@ def child(leg, root, boards, searches, m):
     torch.manual_seed(0)
     net = FastPolicyNet(sz.policyNN({}).cuda().eval(), operands="bf16")
     args = {"C": 2, "num_searches": searches}
-    if leg == "on":
+    if leg in ("on", "tree"):
         args["gumbel"] = {"m": m}
+    if leg == "tree":
+        args["gumbel_tree"] = True
     eng = SelfPlayEngine(net, args, boards, learning=True, planes_dtype="bits128")
     rng = np.random.default_rng(0)
     out = []
     for rep in range(3):                                     # the first search is the warm-up (code objects, buffers) and is not reported
         eng.new_games([-1] * boards)
-        if leg == "on":
+        if leg in ("on", "tree"):
             eng.set_gumbel(eng.gumbel, -np.log(-np.log(rng.random((boards, 218)))))
         st0 = eng.stats()
         torch.cuda.synchronize()
@@ -53,9 +56,11 @@ def child(leg, root, boards, searches, m):
         if rep:
             out.append(dict(seconds=seconds, ms_per_step=1e3 * seconds / searches, simulations=sims,
                             mean_leaf_depth=float(st["sum_depth"] - st0["sum_depth"]) / max(sims, 1)))
-    fallbacks = eng.gumbel_stats()[1] if leg == "on" else 0
+    fallbacks = eng.gumbel_stats()[1] if leg in ("on", "tree") else 0
+    tree_selections = eng.gumbel_tree_stats() if leg == "tree" else 0      # over the three searches of the process
     eng.close()
-    print("RESULT " + json.dumps(dict(leg=leg, boards=boards, searches=searches, m=m, runs=out, fallbacks=fallbacks, device=torch.cuda.get_device_name(0))), flush=True)
+    print("RESULT " + json.dumps(dict(leg=leg, boards=boards, searches=searches, m=m, runs=out, fallbacks=fallbacks, tree_selections=tree_selections,
+                                      device=torch.cuda.get_device_name(0))), flush=True)
 
 
 def main():
@@ -72,7 +77,7 @@ def main():
     a = ap.parse_args()
     if a.child:
         return child(a.child, a.root, a.boards, int(a.searches), a.m)
-    legs = ["off", "on"] + (["parent"] if a.parent_tree else [])
+    legs = ["off", "on", "tree"] + (["parent"] if a.parent_tree else [])
     lines, device = [], None
     for searches in [int(x) for x in a.searches.split(",")]:
         per_leg = {leg: [] for leg in legs}
@@ -91,7 +96,7 @@ def main():
                     per_leg[leg].append(run["ms_per_step"])
                     lines.append("%4d simulations  round %d run %d  %-6s  %8.4f ms per step   %9d simulations in %7.3f s   mean leaf depth %6.3f%s"
                                  % (searches, rnd, k, leg, run["ms_per_step"], run["simulations"], run["seconds"], run["mean_leaf_depth"],
-                                    "   fall-back selections %d" % r["fallbacks"] if leg == "on" else ""))
+                                    "   fall-back selections %d" % r["fallbacks"] if leg in ("on", "tree") else ""))
                     print(lines[-1], flush=True)
         for leg in legs:
             v = per_leg[leg]
@@ -99,7 +104,7 @@ def main():
                          % (searches, leg, sum(v) / len(v), len(v), min(v), max(v), 100.0 * (max(v) - min(v)) / min(v)))
             print(lines[-1], flush=True)
     head = ("tools/gumbel_bench.py on %s: %d boards from the start position, bf16 network, random-init weights, learning engine; gumbel = {\"m\": %d}\n"
-            "with seeded draws on the `on` legs%s; legs run alternately in one session, one process per run, the first search of a\n"
+            "with seeded draws on the `on` and `tree` legs (`tree` = with gumbel_tree as well)%s; legs run alternately in one session, one process per run, the first search of a\n"
             "process not reported.  ms per step = wall time of a whole search / num_searches.  Nothing is gated; random-init weights say nothing about\n"
             "playing strength, which is unmeasured.\n"
             % (device, a.boards, a.m, "; `parent` = the default path of a checkout of the parent commit" if a.parent_tree else ""))
