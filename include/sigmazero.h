@@ -637,6 +637,83 @@ int sz_debug_endings(const int32_t* offsets_dev, const int32_t* vc_dev, const do
                      const int32_t* ply_dev, const uint8_t* holdout_dev, const int32_t* state_in_dev, const sz_ending_options* opts_dev,
                      int32_t* kind_out_dev, double* m_out_dev, int32_t* state_out_dev, int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, off by default: MOVE-SELECTION TEMPERATURE with a visit offset and a value cutoff (AlphaZero, lc0 TempVisitOffset /
+ * TempValueCutoff, KataGo).  The reference samples every self-play move from the root's visit counts at temperature 1 (sim.py:68-76), at ply
+ * 150 as at ply 1, and the only alternative is a negative uniform, the most visited move.  With the option on sz_play samples child c with a
+ * probability proportional to (n_c + visit_offset)^(1/T), T a number per board that the caller rewrites between plies, and never samples a
+ * move whose value lies more than value_cutoff below the most visited move's: a one-visit blunder is not played in a won game.  The schedule
+ * (T by ply, by game, by fast or full search) is the caller's: the engine reads temps_dev[b] and nothing else.  Never switched on, every kernel
+ * that runs today runs unchanged: the option is an instantiation of k_play of its own, k_play<SOLVE, [ForcedOpts,] TempOpts[, EndOpts]>;
+ * k_search_begin, k_search_step and k_play_moves have none.
+ * The rule, per board that passes sz_play's early return (searching, done, no error, game not over) and its zero-visit check, after the ending
+ * decision of sz_set_endings (an ending that fires reads neither uniform nor temperature: nothing below happens on that board) and after
+ * policy-target pruning.  All arithmetic is f64, every operator one IEEE rounding (-ffp-contract=off); slog, sexp and SZG_EXP_CUTOFF are
+ * sz_set_gumbel's (csrc/sz_gumbel.h):
+ *   inputs    the root's children c = 0..K-1 in action order.  n_c = the counts today's sampling reads: the counted visits, or the pruned
+ *             counts n' of sz_set_forced_playouts on a forced board.  N_c, W_c = the tree's counted visits and value sums, never pruned.
+ *             T = temps_dev[b], u = uniforms_dev[b], both read once.  c* = the first maximum of n_c in child order (n_c* >= 1 after the
+ *             zero-visit check; pruning leaves the first maximum where it was).  off = (double)visit_offset.
+ *   solver    on a root proven WIN the move is the first child proven LOSS, as without the option, whatever T and u are.
+ *   greedy    otherwise, if u < 0.0, or !(T > 0.0) (zero, negative, NaN), or a_c* <= 0.0 with a_c = (double)n_c + off: the move is c*, exactly
+ *             the negative-uniform path of sz_play.
+ *   eligible  otherwise the move is sampled.  m_c = -(W_c / (double)N_c), the mover's expected outcome of move c (wave_ending's convention; N_c
+ *             >= n_c >= 1 where it is read).  Child c is eligible iff n_c >= 1 && a_c > 0.0 && (!use_cutoff || m_c >= m_c* - (double)value_cutoff).
+ *             c* is eligible: a_c* > 0.0 here, and m_c* >= m_c* - cutoff for a finite m_c* and a cutoff >= 0 (W is a finite sum of values in
+ *             [-1, 1]).  Every positive a_c is a normal number, which is what slog asks for: n_c is an integer >= 1 and off the double of an
+ *             f32, so a sum below 0.5 has |off| > 0.5, is exact (Sterbenz) and is a multiple of off's f32 spacing, at least 2^-24; the sums
+ *             from 0.5 on are normal anyway.
+ *   weights   w_c = 0.0 for a child that is not eligible.  For an eligible child w_c = a_c when T == 1.0, else
+ *             d_c = slog(a_c) - slog(a_c*); if (d_c > 0.0) d_c = 0.0; w_c = sexp(d_c / T): normalised by the largest, since 800^20 (N = 800 at
+ *             T = 0.05) has no f64.  a_c <= a_c*, so d_c is positive only by slog's own rounding, between neighbouring doubles under an
+ *             offset of 2^22 and more; the clamp keeps sexp's argument at or below 0.0 whatever T is.  For every child with n_c = n_c* the
+ *             argument is exactly 0.0 and w = sexp(0.0) = 1.0 exactly.  A weight whose argument lies below SZG_EXP_CUTOFF is 0.0; the child
+ *             still counts as eligible.
+ *   sampling  today's two sequential passes of one lane, in child order, with w_c in the place of (double)n_c and S, the sequential sum of
+ *             w_c starting from 0.0, in the place of (double)total: acc = 0.0; acc += w_c / S for every c; last = acc; then acc = 0.0,
+ *             idx = 0 and for every c: acc += w_c / S; if (acc / last <= u) idx = c + 1; at the end idx = min(idx, K - 1).  A child of weight
+ *             0.0 leaves acc as it is, so for u in [0, 1) the move has a positive weight: no child that is not eligible is ever played.
+ *             With T == 1.0, off == 0.0 and no cutoff w_c = (double)n_c and S = (double)total exactly (integer-valued doubles add exactly):
+ *             the arithmetic of sz_play without the option, bit for bit.
+ *   outputs   n_eligible[b] = the number of eligible children and p_chosen[b] = w_move / S of the last sz_play; 1 and 1.0 on a greedy or
+ *             proven-win play; 0 and NaN for a board that did not play a move in it (early return, zero visits, a game ended by
+ *             sz_set_endings), and for every board while the option is off.  Counters, per board, cumulative: out[0] plays sampled by the
+ *             rule, out[1] greedy plays under the option (proven-win plays included), out[2] children with n_c >= 1 that a sampled play
+ *             found not eligible.
+ *   record    unchanged: action and visits (pruned where forced) as without the option, `chosen` the action played.  The policy target is not
+ *             tempered.  With reuse_subtree the subtree kept is the played child's, as always.
+ * Composes with sz_set_search_options (any L, solver on or off), sz_set_forced_playouts, sz_set_endings, sz_set_fpu, reuse_subtree, budgets,
+ * visit targets, root noise, sz_compact, sz_compact_searching and sz_play_moves: k_play is independent of all of them.  Gumbel chooses its own
+ * move: see the setter.  Held bit for bit to the host restatement tests/tempref.py by tests/test_gpu_temperature.py.  Its effect on playing
+ * strength is unmeasured. */
+typedef struct sz_temperature_options {
+    float   visit_offset;   /* added to every count before the power (lc0 TempVisitOffset); finite, any sign; 0 = none */
+    float   value_cutoff;   /* >= 0, finite: a move whose mover value lies more than this below the most visited move's is not sampled (lc0 TempValueCutoff) */
+    int32_t use_cutoff;     /* 0 = value_cutoff ignored (and not checked) */
+} sz_temperature_options;                         /* 12 bytes */
+/* opt == NULL switches the option off (temps_dev is ignored; the counters stay); otherwise on, for every board.  temps_dev: device array
+ * [n_boards] of f64, read by every sz_play while the option is on; the caller rewrites its contents between plies, as it does with
+ * uniforms_dev, and keeps it alive until the option is off or set anew.  SZ_ERR_INVALID: e NULL; opt != NULL with temps_dev NULL; visit_offset
+ * not finite; with use_cutoff != 0 a value_cutoff that is negative or not finite.  SZ_ERR_STATE: a call during a search (the rule of
+ * sz_set_search_budgets; nothing is changed then); switching on while Gumbel is on for the next search, and sz_set_gumbel(opt != NULL)
+ * refuses with SZ_ERR_STATE while this option is on.  Takes effect at the next sz_play and holds until changed.  Never drops kept subtrees.
+ * The arrays (weights [n_boards][SZ_MAX_MOVES] f64, the two outputs, the counters) are allocated by the first enabling call. */
+int sz_set_move_temperature(sz_engine* e, const sz_temperature_options* opt, const double* temps_dev, void* stream);
+/* HOST arrays [n_boards], either may be NULL; synchronises.  n_eligible and p_chosen of the last sz_play as the rule's `outputs` says. */
+int sz_fetch_temperature(sz_engine* e, int32_t* n_eligible, double* p_chosen, void* stream);
+/* temperature counters, all boards, cumulative since the option was first switched on (synchronises): out[0] sampled plays, out[1] greedy
+ * plays, out[2] excluded children.  sz_stats is unchanged. */
+int sz_temperature_stats(sz_engine* e, uint64_t out[3], void* stream);
+/* test: the DEVICE code of the move choice (the function the option's k_play calls) on caller-supplied cases, one wavefront per case, in the
+ * manner of sz_debug_endings.  Case c owns children offsets[c]..offsets[c+1] (1..SZ_MAX_MOVES each, else chosen_out -1) of vc (n_c, the counts
+ * sampled from), tree_vc (N_c; NULL = vc) and value_sum (W_c, f64); temps[c] (T), uniforms[c] (u), proven_move[c] (the proving move of a
+ * WIN root, -1 = none; the array may be NULL) and opts[c] (not checked).  Writes per case the move, how it was chosen (0 sampled, 1 greedy,
+ * 2 proven win), n_eligible, p_chosen and the number of excluded children, and for a sampled case every child's weight w_c into
+ * weights_out[offsets[c]..] (left as it is otherwise).  All device pointers. */
+int sz_debug_temperature(const int32_t* offsets_dev, const int32_t* vc_dev, const int32_t* tree_vc_dev, const double* value_sum_dev, const double* temps_dev,
+                         const double* uniforms_dev, const int32_t* proven_move_dev, const sz_temperature_options* opts_dev, int32_t* chosen_out_dev,
+                         int32_t* kind_out_dev, int32_t* n_eligible_out_dev, double* p_chosen_out_dev, int32_t* excluded_out_dev, double* weights_out_dev,
+                         int32_t n_cases, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

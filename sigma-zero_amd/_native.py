@@ -17,6 +17,7 @@ SZ_MAX_LEAVES_PER_STEP = 256
 SZ_PROVEN_UNKNOWN, SZ_PROVEN_WIN, SZ_PROVEN_DRAW, SZ_PROVEN_LOSS = 0, 1, 2, 3      # codes of sz_root_proven / sz_debug_tree_proven
 SZ_END_NONE, SZ_END_RESIGN, SZ_END_DRAW, SZ_END_PROVEN = 0, 1, 2, 3                # kinds of sz_fetch_endings (sz_set_endings)
 SZ_FPU_REFERENCE, SZ_FPU_ABSOLUTE, SZ_FPU_REDUCTION = 0, 1, 2                      # modes of sz_fpu_options (sz_set_fpu)
+SZ_TEMP_SAMPLED, SZ_TEMP_GREEDY, SZ_TEMP_PROVEN = 0, 1, 2                          # how sz_debug_temperature's move was chosen (sz_set_move_temperature)
 
 
 class sz_config(C.Structure):
@@ -40,6 +41,10 @@ class sz_fpu_options(C.Structure):
 
 class sz_gumbel_options(C.Structure):
     _fields_ = [("max_considered", C.c_int32), ("c_visit", C.c_float), ("c_scale", C.c_float)]
+
+
+class sz_temperature_options(C.Structure):
+    _fields_ = [("visit_offset", C.c_float), ("value_cutoff", C.c_float), ("use_cutoff", C.c_int32)]
 
 
 class sz_stats(C.Structure):
@@ -89,6 +94,10 @@ EXPORTS = {
     "sz_fetch_endings": (C.c_int, [C.c_void_p] * 7),
     "sz_ending_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "sz_debug_endings": (C.c_int, [C.c_void_p] * 12 + [C.c_int32, C.c_void_p]),
+    "sz_set_move_temperature": (C.c_int, [C.c_void_p, C.POINTER(sz_temperature_options), C.c_void_p, C.c_void_p]),
+    "sz_fetch_temperature": (C.c_int, [C.c_void_p] * 4),
+    "sz_temperature_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_debug_temperature": (C.c_int, [C.c_void_p] * 14 + [C.c_int32, C.c_void_p]),
     "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_set_visit_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

@@ -4,7 +4,7 @@ learning=False; every game is one board of a batch, colours alternate over the b
 import numpy as np
 import torch
 
-from .selfplay import SelfPlayEngine
+from .selfplay import SelfPlayEngine, temperature_options_of, temperature_at
 
 
 @torch.no_grad()
@@ -105,6 +105,9 @@ def play_options_match(model, args_a, args_b, n_pairs, chess960=True, scharnagl=
     2i and 2i+1 are a pair: the same start (scharnagl[i]; drawn from default_rng(seed) when chess960 and None) and the same opening
     (openings[i % len(openings)], a list of action indices played into both engines before the first search), A white in game 2i and black
     in game 2i+1.  Each side's first sample_plies moves are sampled from the visits with uniforms of default_rng(seed); later moves are greedy.
+    A side whose args have "temperature" (selfplay.temperature_options_of) samples every move with uniforms of default_rng(seed) at the
+    temperature its schedule gives for the GAME's ply (opening included; a final temperature of 0 plays the most visited move); sample_plies
+    must be 0 then (ValueError otherwise): the two are the same control.
 
     One ply: each engine has exactly the boards active where its side is to move (set_active + compact), searches them, plays, and hands
     the chosen moves to the other engine by play_moves (sz_play_moves), which re-roots that engine's kept subtree on a reuse_subtree
@@ -123,6 +126,9 @@ def play_options_match(model, args_a, args_b, n_pairs, chess960=True, scharnagl=
     if planes_dtype is None:
         planes_dtype = ("bits128" if getattr(model, "w16", False) and getattr(model_b, "w16", False) else "nhwc128") if hasattr(model, "tower") else torch.float32
     rng = np.random.default_rng(seed)
+    temps = [temperature_options_of(args_a), temperature_options_of(args_b)]
+    if any(t is not None for t in temps) and sample_plies != 0:
+        raise ValueError("play_options_match: a side with args['temperature'] needs sample_plies == 0 (the schedule says which plies are sampled)")
     if chess960:
         sch = rng.integers(0, 960, size=n_pairs) if scharnagl is None else np.asarray(scharnagl, np.int64).reshape(-1)
         if len(sch) != n_pairs:
@@ -156,7 +162,7 @@ def play_options_match(model, args_a, args_b, n_pairs, chess960=True, scharnagl=
             break
         white_to_move = plies % 2 == 0
         to_move = [live & (a_is_white == white_to_move), live & (a_is_white != white_to_move)]
-        draws = rng.random(n) if sample_plies > 0 else None
+        draws = rng.random(n) if sample_plies > 0 or any(t is not None for t in temps) else None
         given = [np.full(n, -1, np.int32), np.full(n, -1, np.int32)]        # what each engine receives from the other
         recs = [None, None]
         for k, e in enumerate(engines):
@@ -168,7 +174,10 @@ def play_options_match(model, args_a, args_b, n_pairs, chess960=True, scharnagl=
             e.search()
             e.check_errors()
             u = np.full(n, -1.0)
-            if draws is not None:
+            if temps[k] is not None:                      # every move is the rule's: the schedule by game ply decides what is sampled
+                u[to_move[k]] = draws[to_move[k]]
+                e.set_temperatures([temperature_at(temps[k], int(p)) for p in plies])
+            elif draws is not None:
                 sample = to_move[k] & (moves_made[k] < sample_plies)
                 u[sample] = draws[sample]
             e.play(u)

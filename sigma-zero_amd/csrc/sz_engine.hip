@@ -240,6 +240,19 @@ struct EndOpts {
     unsigned long long* stat;   // [B][4] resignations, adjudicated draws, proven endings, holdout marks
 };
 
+// NON-REFERENCE option (sz_set_move_temperature): what k_play's TEMPERATURE instantiations take on top of View, after ForcedOpts and before EndOpts
+// when those options are on: k_play<SOLVE, [ForcedOpts,] TempOpts[, EndOpts]>.  Never beside GumbelOpts (Gumbel chooses its own move).
+// k_search_begin, k_search_step and k_play_moves have no variant: the option lives in sz_play's move choice alone.
+struct TempOpts {
+    sz_temperature_options o;
+    const double* temps;        // [B] the caller's temperatures, read by every sz_play while the option is on
+    double* work;               // [B][SZ_MAX_MOVES] the per-child weights, formed by the lanes, summed by one lane in child order
+    int* nelig;                 // [B] eligible children of the last sz_play (0 for a board that did not play in it) ...
+    double* pch;                // [B] ... and w_chosen / S (NaN likewise)
+    unsigned long long* stat;   // [B][3] plays sampled by the rule, greedy plays under the option, visited children excluded
+};
+enum { TEMP_SAMPLED = 0, TEMP_GREEDY = 1, TEMP_PROVEN = 2 };                                  // how wave_temperature came to its move
+
 // forced playouts at a root (sz_set_forced_playouts): child c with n_c = N_c + k_c >= 1 visits is forced while n_c < sqrt((k * P_c) * T) in f64,
 // T = parentVC - 1.  Returns the forced child with the lowest index, -1 when none is forced: the arg-max decides as everywhere.  Lanes = children
 // as in wave_select_child; with SOLVE a child proven WIN is not forced whenever the arg-max skips WIN children.  A NaN or negative product forces nothing.
@@ -547,6 +560,67 @@ __device__ __forceinline__ int ending_result(int kind, int code, int colour) {
     if (kind == SZ_END_RESIGN) return -mover;
     if (kind == SZ_END_PROVEN) return code == PR_WIN ? mover : (code == PR_LOSS ? -mover : 0);
     return 0;
+}
+
+// the move of sz_play under sz_set_move_temperature (include/sigmazero.h is the rule): ch[0..n) the root's children with their counted N and W,
+// vis[0..n) the counts today's sampling reads (LDS: the counted visits, or wave_prune's pruned counts), T the board's temperature, u its
+// uniform, pmove the first child proven LOSS of a root proven WIN (-1: none, or no solver).  The lanes form the weights w_c into work[0..n)
+// (one sz_slog and one sz_sexp per child), lane 0 adds them up in child order and runs today's two sequential passes over w_c / S.
+// *kind = TEMP_*; *nelig, *pch and *excl as sz_fetch_temperature and sz_temperature_stats report them.  Every lane returns the same.
+__device__ __forceinline__ int wave_temperature(const EdgeStat* ch, const int* vis, int n, const sz_temperature_options& o, double T, double u, int pmove,
+                                                double* work, int* kind, int* nelig, double* pch, int* excl) {
+    const int lane = lane_id();
+    int bn = -1, bi = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) { const int nc = vis[c]; if (nc > bn) { bn = nc; bi = c; } }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
+        if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+    }
+    const int cs = uni(bi);
+    const double voff = (double)o.visit_offset;
+    const double astar = (double)uni(bn) + voff;
+    *nelig = 1; *pch = 1.0; *excl = 0;
+    if (pmove >= 0) { *kind = TEMP_PROVEN; return pmove; }
+    if (u < 0.0 || !(T > 0.0) || astar <= 0.0) { *kind = TEMP_GREEDY; return cs; }
+    *kind = TEMP_SAMPLED;
+    const EdgeStat top = ch[cs];
+    const double floor_m = -(top.W / (double)top.N) - (double)o.value_cutoff;
+    double lstar = 0.0;
+    if (T != 1.0) lstar = sz_slog(astar);
+    int ne = 0, ex = 0;
+    for (int c = lane; c < n; c += 64) {
+        const int nc = vis[c];
+        double w = 0.0;
+        if (nc >= 1) {
+            const double a = (double)nc + voff;
+            bool ok = a > 0.0;
+            if (ok && o.use_cutoff) { const EdgeStat s = ch[c]; ok = -(s.W / (double)s.N) >= floor_m; }
+            if (ok) {
+                ne++;
+                if (T == 1.0) w = a;
+                else { double d = sz_slog(a) - lstar; if (d > 0.0) d = 0.0; w = sz_sexp(d / T); }
+            } else ex++;
+        }
+        work[c] = w;
+    }
+    for (int off = 32; off >= 1; off >>= 1) { ne += __shfl_xor(ne, off); ex += __shfl_xor(ex, off); }
+    __threadfence_block();
+    __syncthreads();
+    int chosen = 0; double p = 0.0;
+    if (lane == 0) {
+        double S = 0.0;
+        for (int c = 0; c < n; c++) S = S + work[c];
+        double acc = 0.0;
+        for (int c = 0; c < n; c++) acc += work[c] / S;
+        const double last = acc;
+        acc = 0.0;
+        int idx = 0;
+        for (int c = 0; c < n; c++) { acc += work[c] / S; if (acc / last <= u) idx = c + 1; }
+        if (idx >= n) idx = n - 1;
+        chosen = idx; p = work[idx] / S;
+    }
+    *nelig = uni(ne); *excl = uni(ex); *pch = uni_f64(p);
+    return uni(chosen);
 }
 
 // solver update after a backup whose last node path[d] has just become proven: walk towards the root; the parent of a newly proven node is
@@ -1420,12 +1494,15 @@ __device__ void wave_keep_subtree(const View& v, const BoardPtrs& bp, int b, int
 // FO ends in EndOpts (sz_set_endings): wave_ending decides on the counted visits whether the game ends here instead of a move
 // FO = GumbelOpts (sz_set_gumbel, SOLVE = false only): the move is wave_gumbel_play's, the board's uniform is not read, and the improved policy,
 // v_mix and the root's network value are left for sz_fetch_gumbel; the record keeps the counted visits
+// FO holds TempOpts (sz_set_move_temperature): the move is wave_temperature's, from the counts the sampling reads (pruned on a forced board), after
+// the ending decision; the record and the subtree kept are untouched
 template <bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO... fo) {
     constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
     constexpr bool ENDING = has_opt<EndOpts, FO...>;
     constexpr bool GUMBEL = has_opt<GumbelOpts, FO...>;
-    static_assert(!GUMBEL || (!SOLVE && !FORCED && !ENDING), "sz_set_gumbel refuses the solver, forced playouts and endings");
+    constexpr bool TEMP = has_opt<TempOpts, FO...>;
+    static_assert(!GUMBEL || (!SOLVE && !FORCED && !ENDING && !TEMP), "sz_set_gumbel refuses the solver, forced playouts, endings and the move temperature");
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     int* vis_lds = path + 8;
@@ -1434,6 +1511,9 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     int status = uni(bp.ctl->status);
     if constexpr (ENDING) {                                              // a board that does not play in this sz_play: kind 0, m NaN
         if (lane == 0) { opt_of<EndOpts>(fo...).kind[b] = SZ_END_NONE; opt_of<EndOpts>(fo...).mval[b] = __longlong_as_double(0x7ff8000000000000LL); }
+    }
+    if constexpr (TEMP) {                                                // likewise: no eligible child, p NaN
+        if (lane == 0) { opt_of<TempOpts>(fo...).nelig[b] = 0; opt_of<TempOpts>(fo...).pch[b] = __longlong_as_double(0x7ff8000000000000LL); }
     }
     if (!(status & ST_SEARCHING) || !(status & ST_DONE) || (status & (ST_ERROR | ST_GAMEOVER))) return;
     EdgeMeta rm = bp.em[0];
@@ -1495,6 +1575,26 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
         const GumbelOpts& go = opt_of<GumbelOpts>(fo...);
         chosen = wave_gumbel_play(bp.es + first, go.g ? go.g + (size_t)b * SZ_MAX_MOVES : nullptr, n, go.o, go.vhat[b], go.work + (size_t)b * SZ_MAX_MOVES,
                                   go.policy + (size_t)b * SZ_MAX_MOVES, go.vmix + b);
+    } else if constexpr (TEMP) {
+        const TempOpts& to = opt_of<TempOpts>(fo...);
+        int pmove = -1;
+        if constexpr (SOLVE) {
+            if (uni((int)rm.pad & PR_MASK) == PR_WIN) {                  // the proving move, whatever T is: the first child proven LOSS
+                int fi = 0x7fffffff;
+                for (int c = lane; c < n && fi == 0x7fffffff; c += 64) if ((bp.em[first + c].pad & PR_MASK) == PR_LOSS) fi = c;
+                for (int off = 32; off >= 1; off >>= 1) { const int oi = __shfl_xor(fi, off); if (oi < fi) fi = oi; }
+                fi = uni(fi);
+                if (fi != 0x7fffffff) pmove = fi;
+            }
+        }
+        int kind, ne, ex; double p;
+        chosen = wave_temperature(bp.es + first, vis_lds, n, to.o, uni_f64(to.temps[b]), uni_f64(uniforms[b]), pmove, to.work + (size_t)b * SZ_MAX_MOVES,
+                                  &kind, &ne, &p, &ex);
+        if (lane == 0) {
+            to.nelig[b] = ne; to.pch[b] = p;
+            to.stat[(size_t)b * 3 + (kind == TEMP_SAMPLED ? 0 : 1)] += 1;
+            to.stat[(size_t)b * 3 + 2] += (unsigned long long)ex;
+        }
     } else
     if (lane == 0) {
         const double u = uniforms[b];
@@ -1745,6 +1845,25 @@ __global__ __launch_bounds__(64) void k_debug_endings(const int* offsets, const 
     }
 }
 
+// test hook (sz_debug_temperature): wave_temperature, the function k_play<.., TempOpts> calls, on caller-supplied cases, one wave per case.
+// The weights go straight to weights_out (the case's span is the function's work array); a greedy or proven-win case writes none.
+__global__ __launch_bounds__(64) void k_debug_temperature(const int* offsets, const int* vc, const int* tree_vc, const double* wsum, const double* temps,
+                                                          const double* uniforms, const int* proven_move, const sz_temperature_options* opts, int* chosen_out,
+                                                          int* kind_out, int* nelig_out, double* pch_out, int* excl_out, double* weights_out) {
+    extern __shared__ u64 lds64[];
+    EdgeStat* ch = (EdgeStat*)lds64;
+    int* vis = (int*)(ch + SZ_MAX_CHILDREN);
+    const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
+    if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) chosen_out[cs] = -1; return; }
+    for (int c = lane; c < n; c += 64) { EdgeStat s; s.W = wsum[lo + c]; s.N = tree_vc ? tree_vc[lo + c] : vc[lo + c]; s.P = 0.0f; ch[c] = s; vis[c] = vc[lo + c]; }
+    __syncthreads();
+    int pmove = proven_move ? uni(proven_move[cs]) : -1;
+    if (pmove >= n) pmove = -1;
+    int kind, ne, ex; double p;
+    const int mv = wave_temperature(ch, vis, n, opts[cs], uni_f64(temps[cs]), uni_f64(uniforms[cs]), pmove, weights_out + lo, &kind, &ne, &p, &ex);
+    if (lane == 0) { chosen_out[cs] = mv; kind_out[cs] = kind; nelig_out[cs] = ne; pch_out[cs] = p; excl_out[cs] = ex; }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
@@ -1783,6 +1902,8 @@ struct sz_engine {
     unsigned long long* gt_stat;    //     enabling call (gt_stat != NULL from then on)
     int end_on;                     // sz_set_endings: sz_play runs the ENDING instantiations of k_play
     EndOpts eo;                     // ... with these; its arrays are allocated by the first enabling call (eo.state != NULL from then on)
+    int temp_on;                    // sz_set_move_temperature: sz_play runs the TEMPERATURE instantiations of k_play
+    TempOpts to;                    // ... with these; its arrays are allocated by the first enabling call (to.stat != NULL from then on)
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
@@ -1809,7 +1930,7 @@ template <typename T> static int dalloc(sz_engine* e, T** p, size_t count) {
 // is called with two std::bool_constants, VL = leaf batching on (vb.L > 1; instantiations without it take an empty Batch) and SOLVE = the solver
 // on, and with the option structs in force, in the order the kernels take them: ForcedOpts or else GumbelOpts (the search begun last, e->cur;
 // under Gumbel VL = SOLVE = false, which the setters' refusals see to; GumbelTreeOpts in its place and no FpuOpts under sz_set_gumbel_tree),
-// FpuOpts (e->cur), EndOpts (sz_set_endings; `proven` cleared while the
+// FpuOpts (e->cur), TempOpts (sz_set_move_temperature; never beside GumbelOpts), EndOpts (sz_set_endings; `proven` cleared while the
 // solver is off; never beside GumbelOpts).  Each kernel takes the members of the pack that concern it: pick below.
 template <typename F> static void with_search_options(const sz_engine* e, F&& f) {
     const Latched& c = e->cur;
@@ -1818,8 +1939,13 @@ template <typename F> static void with_search_options(const sz_engine* e, F&& f)
         else if (e->end_on) { EndOpts eo = e->eo; if (!decltype(solve)::value) eo.o.proven = 0; f(vl, solve, o..., eo); }
         else f(vl, solve, o...);
     };
+    auto temperature = [&](auto vl, auto solve, auto... o) {
+        if constexpr (has_opt<GumbelOpts, decltype(o)...>) endings(vl, solve, o...);
+        else if (e->temp_on) endings(vl, solve, o..., e->to);
+        else endings(vl, solve, o...);
+    };
     auto fpu = [&](auto vl, auto solve, auto... o) {
-        if (c.fpu.tree_mode != SZ_FPU_REFERENCE || c.fpu.root_mode != SZ_FPU_REFERENCE) endings(vl, solve, o..., FpuOpts{c.fpu}); else endings(vl, solve, o...);
+        if (c.fpu.tree_mode != SZ_FPU_REFERENCE || c.fpu.root_mode != SZ_FPU_REFERENCE) temperature(vl, solve, o..., FpuOpts{c.fpu}); else temperature(vl, solve, o...);
     };
     auto forced = [&](auto vl, auto solve) {
         if (c.forced_k > 0.0f) { ForcedOpts fo = e->fo; fo.k = c.forced_k; fpu(vl, solve, fo); } else fpu(vl, solve);
@@ -2001,10 +2127,11 @@ struct OptionState {
     int L, solver;                  // sz_set_leaf_batching / sz_set_solver / sz_set_search_options
     bool forced, gumbel;            // sz_set_forced_playouts, sz_set_gumbel: what the next sz_search_begin takes up
     bool endings, noise;            // sz_set_endings; sz_set_root_noise / sz_set_search_root_noise with a gamma
+    bool temperature;               // sz_set_move_temperature
 };
 enum OptionSetter { BY_ANY, BY_LEAF_BATCHING, BY_SOLVER, BY_ROOT_NOISE };     // the setters whose own entry point accepts less than the engine runs
 static OptionState option_state(const sz_engine* e) {
-    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr};
+    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0};
 }
 static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter by = BY_ANY) {
     const bool reuse = e->v.reuse != 0;
@@ -2016,6 +2143,7 @@ static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter
     if (by == BY_LEAF_BATCHING && p.L > 1 && (reuse || p.solver)) return SZ_ERR_INVALID;
     if (by == BY_SOLVER && p.solver && (reuse || p.L > 1)) return SZ_ERR_INVALID;
     if (p.gumbel && p.noise) return SZ_ERR_STATE;                           // Gumbel is the root's exploration
+    if (p.gumbel && p.temperature) return SZ_ERR_STATE;                     // ... and chooses its own move
     // sz_set_root_noise: a reused root was expanded as an inner node, on un-noised priors, and is never expanded again, so the noise would silently
     // apply to the first ply of a game only; and a reuse engine under sz_set_search_root_noise leaves that mode through that setter, which drops
     // the kept subtrees
@@ -2486,6 +2614,57 @@ int sz_fetch_endings(sz_engine* e, uint8_t* kind, double* mover_value, int32_t* 
 
 int sz_ending_stats(sz_engine* e, uint64_t out[4], void* stream) { return sum_board_counters(e, e ? e->eo.stat : nullptr, 4, out, stream); }
 
+int sz_set_move_temperature(sz_engine* e, const sz_temperature_options* opt, const double* temps_dev, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (opt) {
+        if (!temps_dev) return SZ_ERR_INVALID;
+        if (!std::isfinite(opt->visit_offset)) return SZ_ERR_INVALID;
+        if (opt->use_cutoff && (!std::isfinite(opt->value_cutoff) || opt->value_cutoff < 0.0f)) return SZ_ERR_INVALID;
+    }
+    OptionState p = option_state(e);
+    p.temperature = opt != nullptr;
+    int rc = option_refusal(e, p);
+    if (rc) return rc;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = between_searches(e, s))) return rc;
+    if (!opt) { e->temp_on = 0; return SZ_OK; }
+    const size_t B = e->v.B;
+    if (!e->to.stat) {                                                      // the first enabling call: the weights, last-play readouts, counters
+        double* wk = nullptr; int* ne = nullptr; double* pc = nullptr; unsigned long long* ct = nullptr;
+        if ((rc = dalloc(e, &wk, B * SZ_MAX_MOVES)) || (rc = dalloc(e, &ne, B)) || (rc = dalloc(e, &pc, B)) || (rc = dalloc(e, &ct, B * 3))) return rc;
+        HIPCHK(hipMemsetAsync(ct, 0, B * 3 * sizeof(unsigned long long), s));
+        e->to.work = wk; e->to.nelig = ne; e->to.pch = pc; e->to.stat = ct;
+    }
+    if (!e->temp_on) {                                                      // off -> on: no sz_play of the option to describe yet
+        HIPCHK(hipMemsetAsync(e->to.nelig, 0, B * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(e->to.pch, 0xff, B * sizeof(double), s));     // all ones: a NaN
+    }
+    e->to.o = *opt;
+    e->to.o.use_cutoff = opt->use_cutoff ? 1 : 0;
+    if (!e->to.o.use_cutoff) e->to.o.value_cutoff = 0.0f;
+    e->to.temps = temps_dev;
+    e->temp_on = 1;
+    return SZ_OK;
+}
+
+int sz_fetch_temperature(sz_engine* e, int32_t* n_eligible, double* p_chosen, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = e->v.B;
+    if (e->temp_on) {
+        if (n_eligible) HIPCHK(hipMemcpyAsync(n_eligible, e->to.nelig, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (p_chosen) HIPCHK(hipMemcpyAsync(p_chosen, e->to.pch, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (!e->temp_on)
+        for (size_t b = 0; b < B; b++) { if (n_eligible) n_eligible[b] = 0; if (p_chosen) p_chosen[b] = std::nan(""); }
+    return SZ_OK;
+}
+
+int sz_temperature_stats(sz_engine* e, uint64_t out[3], void* stream) { return sum_board_counters(e, e ? e->to.stat : nullptr, 3, out, stream); }
+
 int sz_pending_boards(sz_engine* e, int32_t* n_out, void* stream) {
     if (!e || !n_out) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
@@ -2532,7 +2711,7 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     with_search_options(e, [&](auto, auto solve, auto... o) {
         std::apply([&](auto... k) {
             hipLaunchKernelGGL((k_play<decltype(solve)::value, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, k...);
-        }, pick<ForcedOpts, GumbelOpts, EndOpts>(play_opt(o)...));          // first-play urgency acts in the descent alone
+        }, pick<ForcedOpts, GumbelOpts, TempOpts, EndOpts>(play_opt(o)...));   // first-play urgency acts in the descent alone
     });
     HIPCHK(hipGetLastError());
     return SZ_OK;
@@ -2755,6 +2934,19 @@ int sz_debug_endings(const int32_t* offsets_dev, const int32_t* vc_dev, const do
     hipLaunchKernelGGL(k_debug_endings, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * sizeof(EdgeStat), (hipStream_t)stream,
                        offsets_dev, vc_dev, value_sum_dev, root_proven_dev, colour_dev, ply_dev, holdout_dev, state_in_dev, opts_dev,
                        kind_out_dev, m_out_dev, state_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_temperature(const int32_t* offsets_dev, const int32_t* vc_dev, const int32_t* tree_vc_dev, const double* value_sum_dev, const double* temps_dev,
+                         const double* uniforms_dev, const int32_t* proven_move_dev, const sz_temperature_options* opts_dev, int32_t* chosen_out_dev,
+                         int32_t* kind_out_dev, int32_t* n_eligible_out_dev, double* p_chosen_out_dev, int32_t* excluded_out_dev, double* weights_out_dev,
+                         int32_t n_cases, void* stream) {
+    if (!offsets_dev || !vc_dev || !value_sum_dev || !temps_dev || !uniforms_dev || !opts_dev || !chosen_out_dev || !kind_out_dev || !n_eligible_out_dev ||
+        !p_chosen_out_dev || !excluded_out_dev || !weights_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_temperature, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(int)), (hipStream_t)stream,
+                       offsets_dev, vc_dev, tree_vc_dev, value_sum_dev, temps_dev, uniforms_dev, proven_move_dev, opts_dev, chosen_out_dev, kind_out_dev,
+                       n_eligible_out_dev, p_chosen_out_dev, excluded_out_dev, weights_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

@@ -117,7 +117,8 @@ def visit_target_options_of(args):
     network call at all) and sz_set_search_root_noise in place of sz_set_root_noise (the root is noised at every search, kept roots included).
     Without args["playout_cap"] every board's target is num_searches.
     args["quiet_fast_plies"] = True (needs visit_targets, playout_cap and root_dirichlet_alpha): fast plies are searched without root noise
-    (KataGo); the sampling temperature is not touched.  The effect of either on playing strength is unmeasured."""
+    (KataGo); their sampling temperature is args["temperature"]["fast"] (temperature_options_of).  The effect of either on playing strength
+    is unmeasured."""
     vt, quiet = args.get("visit_targets", False), args.get("quiet_fast_plies", False)
     for key, val in (("visit_targets", vt), ("quiet_fast_plies", quiet)):
         if not isinstance(val, (bool, np.bool_)):
@@ -278,6 +279,73 @@ def ending_options_of(args):
     return out
 
 
+TEMPERATURE_KEYS = ("t0", "t_final", "plies", "halflife", "fast", "visit_offset", "value_cutoff")
+
+
+def temperature_options_of(args):
+    """The move-selection temperature of args, checked: a dict with every key of TEMPERATURE_KEYS, or None when the key is absent.
+    NON-REFERENCE, default off.
+
+    args["temperature"] = {"t0": 1.0, "t_final": 0.0, "plies": 60, "halflife": None, "fast": None, "visit_offset": 0.0, "value_cutoff": None}
+    (the defaults) switches play() from sampling the visit counts as they are, at every ply, to sampling child c with a probability
+    proportional to (n_c + visit_offset) ** (1 / T) (sz_set_move_temperature), T from temperature_at(): t0 for the first `plies` plies of a
+    game and t_final from then on, or with `halflife` a decay from t0 towards t_final that halves the distance every `halflife` plies after
+    them.  T = 0 plays the most visited move.  fast: the temperature of args["playout_cap"]'s fast plies (KataGo: 0.0), whatever the ply.
+    visit_offset (lc0's TempVisitOffset, usually negative) is added to every count, a child it leaves at or below 0 is not sampled;
+    value_cutoff (lc0's TempValueCutoff) keeps moves out whose value lies more than that below the most visited move's.  The training
+    record is not tempered.  Refused with args["gumbel"], which chooses its own move.  Checked in this order: the dict and its keys, t0,
+    t_final, plies, halflife, fast, visit_offset, value_cutoff, the combinations.  Its effect on playing strength is unmeasured."""
+    opt = args.get("temperature")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(TEMPERATURE_KEYS):
+        raise ValueError("args['temperature'] must be a dict with keys from %s, got %r" % (TEMPERATURE_KEYS, opt))
+    number = lambda x: not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating))
+    out = {}
+    for key, default in (("t0", 1.0), ("t_final", 0.0)):
+        t = opt.get(key, default)
+        if not number(t) or not (math.isfinite(t) and t >= 0):                   # NaN fails the comparison
+            raise ValueError("args['temperature'][%r] must be a finite number >= 0, got %r" % (key, t))
+        out[key] = float(t)
+    n = opt.get("plies", 60)
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 2 ** 31 - 1:
+        raise ValueError("args['temperature']['plies'] must be an integer >= 0, got %r" % (n,))
+    out["plies"] = int(n)
+    h = opt.get("halflife")
+    if h is not None and (not number(h) or not (math.isfinite(h) and h > 0)):
+        raise ValueError("args['temperature']['halflife'] must be None or a finite number > 0, got %r" % (h,))
+    out["halflife"] = None if h is None else float(h)
+    f = opt.get("fast")
+    if f is not None and (not number(f) or not (math.isfinite(f) and f >= 0)):
+        raise ValueError("args['temperature']['fast'] must be None or a finite number >= 0, got %r" % (f,))
+    out["fast"] = None if f is None else float(f)
+    v = opt.get("visit_offset", 0.0)
+    if not number(v) or not (math.isfinite(v) and abs(v) <= float(np.finfo(np.float32).max)):       # the struct holds an f32
+        raise ValueError("args['temperature']['visit_offset'] must be a finite number, got %r" % (v,))
+    out["visit_offset"] = float(np.float32(v))
+    c = opt.get("value_cutoff")
+    if c is not None and (not number(c) or not (math.isfinite(c) and math.isfinite(float(np.float32(c))) and c >= 0)):
+        raise ValueError("args['temperature']['value_cutoff'] must be None or a finite number >= 0, got %r" % (c,))
+    out["value_cutoff"] = None if c is None else float(np.float32(c))
+    if out["fast"] is not None and args.get("playout_cap") is None:
+        raise ValueError("args['temperature']['fast'] needs args['playout_cap']: there are no fast plies without it")
+    if args.get("gumbel") is not None:
+        raise ValueError("args['temperature'] and args['gumbel'] exclude each other: the Gumbel search chooses its own move")
+    return out
+
+
+def temperature_at(opts, ply, full=True):
+    """The schedule of args["temperature"]: the temperature of game ply `ply` (0 = the game's first move) under opts, a dict as
+    temperature_options_of returns it.  full = False: a fast ply of args["playout_cap"], which takes opts["fast"] when that is set.  Pure,
+    f64: t0 while ply < plies; then t_final, or with a halflife t_final + (t0 - t_final) * 0.5 ** ((ply - plies) / halflife)."""
+    if not full and opts["fast"] is not None:
+        return float(opts["fast"])
+    t0, t_final, ply = float(opts["t0"]), float(opts["t_final"]), int(ply)
+    if opts["halflife"] is None:
+        return t0 if ply < opts["plies"] else t_final
+    return t_final + (t0 - t_final) * 0.5 ** (max(0, ply - opts["plies"]) / float(opts["halflife"]))
+
+
 def raise_if_overflowed(model):
     """ValueError when `model` keeps a range flag (FastPolicyNet / SplitPolicyNet: overflowed()) and a forward since the last look returned inf / NaN:
     with f16 operands a stored activation of 65520 or more is inf, the heads make NaN of it, and the search keeps a NaN prior without complaint.
@@ -330,6 +398,9 @@ class SelfPlayEngine:
         self.gumbel_tree = gumbel_tree_of(self.args)
         # NON-REFERENCE option (default off): resignation and adjudicated game endings, see ending_options_of
         self.endings = ending_options_of(self.args)
+        # NON-REFERENCE option (default off): move-selection temperature, visit offset and value cutoff, see temperature_options_of
+        self.temperature = temperature_options_of(self.args)
+        self._temps = None            # the device array [B] f64 sz_play reads its temperatures from (set_move_temperature)
         self.quiet = None             # boards whose next searches get no root noise (set_quiet; visit_targets mode)
         self.last_goals = None        # visit_targets mode: search_goals() of the last search()
         self._compact_on = False      # the mapping chosen by the last compact() call
@@ -388,6 +459,8 @@ class SelfPlayEngine:
             self.set_gumbel_tree(True)
         if self.endings is not None:  # no holdout board until set_endings says otherwise
             self.set_endings(self.endings)
+        if self.temperature is not None:  # every board at t0 until set_temperatures says otherwise
+            self.set_move_temperature(self.temperature, np.full(self.B, self.temperature["t0"], np.float64))
 
     def close(self):
         if self._e:
@@ -582,6 +655,48 @@ class SelfPlayEngine:
         """(resignations, adjudicated draws, proven endings, holdout marks), all boards, cumulative (sz_ending_stats)"""
         out = (C.c_uint64 * 4)()
         N.check(N.lib().sz_ending_stats(self._e, out, self._stream()), "sz_ending_stats")
+        return tuple(int(x) for x in out)
+
+    def set_temperatures(self, temps):
+        """Rewrite the per-board temperatures the next play() reads (no engine call: the device array sz_set_move_temperature was given is
+        overwritten in stream order, as play() does with the uniforms).  temps: [B] numbers >= 0; a negative or NaN entry is a ValueError."""
+        t = np.ascontiguousarray(temps, dtype=np.float64).reshape(-1)
+        if t.shape[0] != self.B:
+            raise ValueError("set_temperatures: %d temperatures for %d boards" % (t.shape[0], self.B))
+        if not (t >= 0).all():                                   # NaN fails the comparison
+            raise ValueError("set_temperatures: temperatures must be >= 0, got %r" % (t.tolist(),))
+        if self._temps is None:
+            self._temps = torch.zeros(self.B, dtype=torch.float64, device=self.device)
+        self._temps.copy_(torch.from_numpy(t))
+
+    def set_move_temperature(self, opts, temps=None):
+        """Move-selection temperature (sz_set_move_temperature, a NON-REFERENCE option) from the next play() on, until changed.  opts: a dict
+        with 'visit_offset' and 'value_cutoff' (None: no cutoff), as temperature_options_of returns it (the schedule keys are the caller's
+        business and ignored here), or None = off.  temps: the boards' temperatures [B], uploaded (None: left as they are, 1.0 at first);
+        set_temperatures() rewrites them between plies.  Between searches only; refused while Gumbel is on; kept subtrees are not touched."""
+        if opts is None:
+            N.check(N.lib().sz_set_move_temperature(self._e, None, None, self._stream()), "sz_set_move_temperature")
+            self.temperature = None
+            return
+        if temps is not None or self._temps is None:
+            self.set_temperatures(np.ones(self.B) if temps is None else temps)
+        cut = opts.get("value_cutoff")
+        o = N.sz_temperature_options(float(opts.get("visit_offset", 0.0)), 0.0 if cut is None else float(cut), int(cut is not None))
+        N.check(N.lib().sz_set_move_temperature(self._e, C.byref(o), _ptr(self._temps), self._stream()), "sz_set_move_temperature")
+        self.temperature = dict(opts)
+
+    def fetch_temperature(self):
+        """sz_fetch_temperature after play(): dict of [B] arrays: n_eligible (children the rule could have sampled; 1 on a greedy or
+        proven-win play, 0 for a board that played no move) and p_chosen (the probability the move played had; 1.0 / NaN likewise)"""
+        out = dict(n_eligible=np.zeros(self.B, np.int32), p_chosen=np.zeros(self.B, np.float64))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        N.check(N.lib().sz_fetch_temperature(self._e, p(out["n_eligible"]), p(out["p_chosen"]), self._stream()), "sz_fetch_temperature")
+        return out
+
+    def temperature_stats(self):
+        """(plays sampled by the rule, greedy plays under the option, visited children excluded), all boards, cumulative (sz_temperature_stats)"""
+        out = (C.c_uint64 * 3)()
+        N.check(N.lib().sz_temperature_stats(self._e, out, self._stream()), "sz_temperature_stats")
         return tuple(int(x) for x in out)
 
     def set_quiet(self, quiet):

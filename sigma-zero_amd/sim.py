@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, gumbel_tree_of, ENDING_KINDS
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, gumbel_tree_of, temperature_options_of, temperature_at, ENDING_KINDS
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -71,7 +71,7 @@ def playout_cap_of(args):
 
 
 def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, learning=True, planes_dtype=None, max_plies=100000,
-               verbose=False, n_boards=None, compact=True, stats=None, full_search=None, root_gamma=None, holdout=None, gumbel_noise=None):
+               verbose=False, n_boards=None, compact=True, stats=None, full_search=None, root_gamma=None, holdout=None, gumbel_noise=None, temperature=None):
     """Plays n_games games to the end and returns a list of per-game history dicts (sim.py:38-43 layout), game g at index g.
 
     The games run concurrently on `n_boards` board slots of one engine (default: one slot per game).  A slot whose game ends is
@@ -90,7 +90,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     stats: optional dict, receives 'sims', 'nn_rows', 'plies' (work done; sims = new simulations, nn_rows = network rows evaluated), 'full_plies' / 'fast_plies' (game
       plies searched with the full / the fast budget), 'searches_without_network' (lock-step searches that made no network call: args["visit_targets"]) and 'host_seconds' (the host's wall time per phase of the ply loop: enqueue_search returns before the GPU is done,
       wait_search is the wait for it), 'forced_selections' / 'pruned_visits' (sz_forced_stats; 0 without args["forced_playouts"]), 'resigned' /
-      'adjudicated_draws' / 'adjudicated_proven' / 'holdout_marks' (sz_ending_stats) and 'holdout_games' (0 without args["endings"]).
+      'adjudicated_draws' / 'adjudicated_proven' / 'holdout_marks' (sz_ending_stats) and 'holdout_games' (0 without args["endings"]),
+      and, with args["temperature"] only, 'tempered_plays' / 'greedy_plays' / 'excluded_children' (sz_temperature_stats).
     Every game dict has 'termination', one of "rules" | "resign" | "draw_adjudicated" | "proven" | "max_plies", 'holdout' (the game was a holdout
       game) and 'would_end', None or {"kind", "ply", "colour"}: the first ply at which a rule would have ended a holdout game.
 
@@ -99,11 +100,13 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     full budget args["num_searches"] with probability p, else with n_fast simulations (2 <= n_fast <= num_searches); every ply is played, but ONLY
     full-search plies become training samples (states / actions / colours / packed_states); the game dict's 'sample_plies' lists the ply of
     each sample and 'rewards' takes its sign from that ply.  The batch shrinks to the full-search boards once the fast ones are done
-    (SelfPlayEngine.search).  Noise and temperature are the same on fast and full plies (`learning` is per engine).
+    (SelfPlayEngine.search).  Noise is the same on fast and full plies (`learning` is per engine); so is the sampling temperature unless
+    args["temperature"]["fast"] says otherwise.
     args["visit_targets"] = True (NON-REFERENCE, selfplay.visit_target_options_of): playout_cap and root_dirichlet_alpha together with
     args["reuse_subtree"].  The per-ply numbers np.where(sampled, num_searches, n_fast) are then root visit TARGETS: the visits of the kept
     subtree count, stats['sims'] are the new simulations actually made, and the root is noised at every ply.  With
-    args["quiet_fast_plies"] = True fast plies are searched without root noise; the sampling temperature is not touched.  Strength effect unmeasured.
+    args["quiet_fast_plies"] = True fast plies are searched without root noise; their sampling temperature is args["temperature"]["fast"]
+    (KataGo's "no temperature on fast plies" is fast: 0.0).  Strength effect unmeasured.
     args["forced_playouts"] = k (NON-REFERENCE, selfplay.forced_playout_options_of): forced playouts at the root and policy-target pruning of the
     record ('actions' are the pruned visit fractions; the move is sampled from them).  With args["playout_cap"] only full-search plies are forced
     (fast plies are not recorded, and KataGo leaves them un-forced); without it every ply is.  Needs learning.  Strength effect unmeasured.
@@ -120,6 +123,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     stats gets 'gumbel_fallbacks' (sz_gumbel_stats: root selections that found no child at their level, 0).  Strength effect unmeasured.
     args["gumbel_tree"] = True (NON-REFERENCE, selfplay.gumbel_tree_of; needs args["gumbel"]): below the root of every Gumbel search the
     completed-Q selection of sz_set_gumbel_tree replaces PUCT; the engine applies it and the per-ply set_gumbel leaves it on.  Strength effect unmeasured.
+    args["temperature"] = {...} (NON-REFERENCE, selfplay.temperature_options_of): the move-selection temperature with lc0's visit offset and
+    value cutoff (sz_set_move_temperature).  Every running game's temperature is computed at every ply from THAT GAME's ply (a game that starts
+    on a refilled slot starts at t0 again) by selfplay.temperature_at, with full = the ply's full / fast decision under args["playout_cap"].
+    The record is not tempered: 'actions' stay the visit fractions.  With the key absent nothing is drawn or consumed differently.
+    Strength effect unmeasured.
+    temperature(game, ply) -> float >= 0: that game's temperature at that ply, like `uniforms`; replaces the schedule.  Needs args["temperature"].
     gumbel_noise(game, ply) -> 218 floats: the Gumbel(0,1) draws of that game's root at that ply by root child, like `uniforms`; replaces
       the default above, with and without `learning`.
     holdout(game) -> bool: whether a game is a holdout game, like `uniforms`.  Default: a numpy Generator of its own, one draw per game in game
@@ -139,6 +148,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     gumbel_tree_of(args)
     if gumbel_noise is not None and gum is None:
         raise ValueError("gumbel_noise needs args['gumbel']")
+    temp_opts = temperature_options_of(args)
+    if temperature is not None and temp_opts is None:
+        raise ValueError("temperature needs args['temperature']")
     if holdout is not None and end_opts is None:
         raise ValueError("holdout needs args['endings']")
     if full_search is not None and pcap is None:
@@ -276,6 +288,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         for s_ in running[np.argsort(slot_game[running], kind="stable")]:      # draws in game order
             g = int(slot_game[s_])
             u[s_] = uniforms(g, int(plies[g])) if uniforms is not None else np.random.random_sample()
+        if temp_opts is not None:                          # each game's temperature from its own ply, not the slot's
+            temps = np.zeros(B, dtype=np.float64)
+            for s_ in running:
+                g = int(slot_game[s_])
+                temps[s_] = float(temperature(g, int(plies[g]))) if temperature is not None else temperature_at(temp_opts, int(plies[g]), full=bool(sampled[s_]))
+            eng.set_temperatures(temps)
         eng.play(u)
         rec = eng.fetch_ply()
         ends = eng.fetch_endings() if end_opts is not None else None
@@ -316,6 +334,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         work["resigned"], work["adjudicated_draws"], work["adjudicated_proven"], work["holdout_marks"] = eng.ending_stats()
     if gum is not None:
         work["gumbel_fallbacks"] = eng.gumbel_stats()[1]
+    if temp_opts is not None:
+        work["tempered_plays"], work["greedy_plays"], work["excluded_children"] = eng.temperature_stats()
     eng.close()
     if stats is not None:
         stats.update(work)

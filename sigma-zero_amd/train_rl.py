@@ -462,7 +462,7 @@ def write_step_log(path, epoch, hist, lr_scheduler, append=True):
 
 def selfplay_args_of(a):
     """the self-play `args` dict of main()'s parsed flags `a`; nothing is checked here: the engine's option readers (selfplay.search_options_of,
-    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, sim.playout_cap_of) refuse what does not go together"""
+    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, temperature_options_of, sim.playout_cap_of) refuse what does not go together"""
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
@@ -492,6 +492,10 @@ def selfplay_args_of(a):
         if a.draw_value is not None:
             end["draw_value"] = a.draw_value
         args["endings"] = end
+    temp = {key: val for key, val in (("plies", a.temperature_plies), ("t_final", a.temperature_final), ("halflife", a.temperature_halflife),
+                                      ("fast", a.temperature_fast), ("visit_offset", a.temp_visit_offset), ("value_cutoff", a.temp_value_cutoff)) if val is not None}
+    if temp:
+        args["temperature"] = temp
     return args
 
 
@@ -539,8 +543,8 @@ def flag_parser():
                     help="NON-REFERENCE: Dirichlet(alpha) noise on the root's children only instead of the reference's constant (0 = off); with subtree reuse "
                          "only together with --visit-targets")
     ap.add_argument("--quiet-fast-plies", action="store_true",
-                    help="NON-REFERENCE: fast plies are searched without root noise (needs --visit-targets, --playout-cap-fast and --root-dirichlet-alpha); the "
-                         "sampling temperature is not touched; strength effect unmeasured")
+                    help="NON-REFERENCE: fast plies are searched without root noise (needs --visit-targets, --playout-cap-fast and --root-dirichlet-alpha); "
+                         "their sampling temperature is --temperature-fast; strength effect unmeasured")
     ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
                     help="NON-REFERENCE: forced playouts at the root, n < sqrt(K * P * (N_root - 1)), and policy-target pruning of the recorded visits "
                          "(KataGo: K = 2; 0 = off); with --playout-cap-fast on full-search plies only (args['forced_playouts']); strength effect unmeasured")
@@ -565,6 +569,18 @@ def flag_parser():
     ap.add_argument("--adjudicate-proven", action="store_true", help="NON-REFERENCE: a game whose root the solver has proven ends with that result (needs --solver)")
     ap.add_argument("--ending-holdout", type=float, default=0.0, metavar="Q",
                     help="share of the games that are played out and only marked where a rule would have ended them; the cycle log counts how often the mark was wrong")
+    ap.add_argument("--temperature-plies", type=int, default=None, metavar="N",
+                    help="NON-REFERENCE: moves are sampled at temperature 1 for the first N plies of a game and at --temperature-final after them "
+                         "(args['temperature'], sz_set_move_temperature; any of the six temperature flags switches the option on, N defaults to 60); "
+                         "the reference samples every ply at temperature 1; not combined with --gumbel; strength effect unmeasured")
+    ap.add_argument("--temperature-final", type=float, default=None, metavar="T", help="the temperature after --temperature-plies (default 0: the most visited move)")
+    ap.add_argument("--temperature-halflife", type=float, default=None, metavar="H",
+                    help="instead of the step: after --temperature-plies the temperature halves its distance to --temperature-final every H plies")
+    ap.add_argument("--temperature-fast", type=float, default=None, metavar="T", help="the temperature of fast plies (needs --playout-cap-fast; KataGo: 0)")
+    ap.add_argument("--temp-visit-offset", type=float, default=None, metavar="X",
+                    help="added to every visit count before the power; a move it leaves at or below 0 is not sampled (lc0 TempVisitOffset)")
+    ap.add_argument("--temp-value-cutoff", type=float, default=None, metavar="D",
+                    help="a move whose value lies more than D below the most visited move's is not sampled (lc0 TempValueCutoff)")
     return ap
 
 
@@ -636,6 +652,8 @@ def main(argv=None):
                                         "pruned_visits": sp_stats.get("pruned_visits"),
                                         "gumbel": args.get("gumbel"), "gumbel_fallbacks": sp_stats.get("gumbel_fallbacks"),
                                         "endings": args.get("endings"), "ending_report": ending_report(games) if args.get("endings") else None,
+                                        "temperature": args.get("temperature"), "tempered_plays": sp_stats.get("tempered_plays"),
+                                        "greedy_plays": sp_stats.get("greedy_plays"), "excluded_children": sp_stats.get("excluded_children"),
                                         "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"
