@@ -714,6 +714,53 @@ int sz_debug_temperature(const int32_t* offsets_dev, const int32_t* vc_dev, cons
                          int32_t* kind_out_dev, int32_t* n_eligible_out_dev, double* p_chosen_out_dev, int32_t* excluded_out_dev, double* weights_out_dev,
                          int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, off by default: a VISIT-DEPENDENT EXPLORATION RATE (AlphaZero's c(s) = log((1 + N(s) + c_base) / c_base) + c_init with
+ * c_base = 19652, c_init = 1.25; lc0's CPuct + CPuctFactor * log((N + CPuctBase) / CPuctBase) with a second triple for the root).  Selection
+ * everywhere is q + c * P * sqrt(n_p) / (1 + n_c) with the one constant c = sz_config.c_puct (Node.get_ucb).  With the option on c grows with the
+ * parent's visit count, by one triple (init, base, factor) for the board's root and one for every node below it.  The growth matters at 800
+ * simulations and more, and where a kept root starts a search with hundreds of visits (reuse_subtree, sz_set_visit_targets).  Never switched
+ * on, every kernel that runs today runs unchanged: the option is an instantiation of its own, PuctOpts after FpuOpts and before TempOpts in the
+ * pack: k_search_step<VL, SOLVE, [ForcedOpts,] [FpuOpts,] PuctOpts>, and k_play<SOLVE, ForcedOpts, PuctOpts[, TempOpts][, EndOpts]> because
+ * policy-target pruning is k_play's only use of c.  k_search_begin and k_play_moves have no variant.
+ * The rule:
+ *   site       the root triple is used where a child of the root is selected (depth 0 of a descent, of a fresh and of a continued search alike)
+ *              and by policy-target pruning; the tree triple is used at depth >= 1.
+ *   n_p        the parent count that selection's sqrt already reads: in k_search_step N_p, or N_p + k_p under leaf batching (k_p the parent's
+ *              in-flight count); in policy-target pruning the root's counted N.  A kept root's visits count (and a fresh root's N carries the
+ *              reference's extra 1 of mcts.py:46, as in the sqrt).
+ *   c          all in f64, every operator one IEEE rounding (-ffp-contract=off); slog is sz_set_gumbel's (csrc/sz_gumbel.h):
+ *                x = (((double)n_p + (double)base) + 1.0) / (double)base
+ *                c = (float)((double)init + (double)factor * slog(x))
+ *              This f32 takes c_puct's place in ucb_value / ucb_u, whose operation order is not touched.  x > 1 always (base >= 1, n_p >= 0), so
+ *              slog's precondition holds.  AlphaZero is (1.25, 19652, 1); lc0's form is the same up to the + 1.  The scalar function is
+ *              sz_cpuct in csrc/sz_cpuct.h, plain C++ for host and device; it is evaluated once per selection, uniform across the wave, and
+ *              not cached per node.
+ *   identity   at factor == 0, c == init exactly: an engine with the option at (C, any base, 0) at both sites builds the trees and records of
+ *              the engine without the option and c_puct = C, bit for bit, through different kernels.
+ *   unchanged  q, the first-play rule of sz_set_fpu (its u takes the same c), the forced-child rule n_c < sqrt(k P_c T), the arg-max and its
+ *              tie-break, the solver's skipping of WIN children, virtual loss, and sz_play's sampling.
+ *   pruning    wave_prune reads the root triple's c at the root's counted N for both `best` and the candidates' u.
+ * sz_search_begin latches the setting, like sz_set_fpu's: a search, its steps and its sz_play (which prunes under what its search ran under)
+ * see what their sz_search_begin saw.  Only selection and pruning change and the tree is never modified: kept subtrees are never dropped.
+ * Composes with sz_set_search_options (any L, solver, reuse), budgets, visit targets, root noise, forced playouts, sz_set_fpu, endings, the
+ * move temperature, sz_compact, sz_compact_searching and sz_play_moves.  Gumbel exists for 16 to 64 simulations, where the growth is nil, and
+ * its restatement is a separate chain: the two refuse each other, see the setter; combining them is a follow-up.
+ * Held bit for bit to the host restatement tests/puctref.py by tests/test_gpu_cpuct.py.  Its effect on playing strength is unmeasured. */
+typedef struct sz_cpuct_options {
+    float tree_init, tree_base, tree_factor;      /* every node below the root */
+    float root_init, root_base, root_factor;      /* the board's root (depth 0 of a descent) and policy-target pruning */
+} sz_cpuct_options;                               /* 24 bytes */
+/* opt == NULL switches the option off: the kernels that run without it then run, with sz_config.c_puct.  SZ_ERR_INVALID (nothing is changed):
+ * a field that is not finite, an init outside [0, 100], a factor outside [0, 100], a base outside [1, 1e9].  SZ_ERR_STATE: a call during a
+ * search (the rule of sz_set_search_budgets; nothing is changed then); switching on while Gumbel is on for the next search, and
+ * sz_set_gumbel(opt != NULL) refuses with SZ_ERR_STATE while this option is on.  Takes effect at the next sz_search_begin and holds until
+ * changed. */
+int sz_set_cpuct(sz_engine* e, const sz_cpuct_options* opt, void* stream);
+/* test: the DEVICE code of the rate (sz_cpuct as the option's kernels call it) on caller-supplied cases, one lane per case, in the manner of
+ * sz_debug_gumbel's maths part: c_out[i] = the c of opts[i] at parent count n_p[i], by the root triple where is_root[i] != 0 and the tree triple
+ * otherwise.  opts are not checked.  All device pointers. */
+int sz_debug_cpuct(const int32_t* n_p_dev, const uint8_t* is_root_dev, const sz_cpuct_options* opts_dev, float* c_out_dev, int32_t n_cases, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

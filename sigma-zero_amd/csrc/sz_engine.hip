@@ -35,6 +35,7 @@
 #include <vector>
 #include "sz_chess.h"
 #include "sz_gumbel.h"
+#include "sz_cpuct.h"
 #include "../../include/sigmazero.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -288,6 +289,17 @@ __device__ __forceinline__ int wave_select_root_forced(const EdgeStat* ch, const
 // NON-REFERENCE option (sz_set_fpu): what the FPU instantiations of k_search_step take on top of View, and of ForcedOpts when both options are
 // on: k_search_step<VL, SOLVE, FpuOpts>, k_search_step<VL, SOLVE, ForcedOpts, FpuOpts>.  k_search_begin and k_play have no FPU variant.
 struct FpuOpts { sz_fpu_options o; };
+
+// NON-REFERENCE option (sz_set_cpuct): what the instantiations with a visit-dependent exploration rate take on top of View, after ForcedOpts and
+// FpuOpts and before TempOpts when those options are on: k_search_step<VL, SOLVE, [ForcedOpts,] [FpuOpts,] PuctOpts> and, because pruning is its
+// only use of c, k_play<SOLVE, ForcedOpts, PuctOpts[, TempOpts][, EndOpts]>.  Never beside GumbelOpts / GumbelTreeOpts.  k_search_begin and
+// k_play_moves have no variant.
+struct PuctOpts { sz_cpuct_options o; };
+// the f32 that takes c_puct's place at a parent with n_p visits (include/sigmazero.h is the rule; sz_cpuct.h the arithmetic): the root's triple
+// where a child of the root is selected and in pruning, the tree's below.  n_p and root are uniform, and so is the result.
+__device__ __forceinline__ float puct_c(const sz_cpuct_options& o, int n_p, bool root) {
+    return sz_cpuct(root ? o.root_init : o.tree_init, root ? o.root_base : o.tree_base, root ? o.root_factor : o.tree_factor, n_p);
+}
 
 // NON-REFERENCE option (sz_set_gumbel): what the GUMBEL instantiations take on top of View, before FpuOpts when both options are on:
 // k_search_step<false, false, GumbelOpts[, FpuOpts]> and k_play<false, GumbelOpts>.  k_search_begin has no variant: the root's network value is
@@ -1108,6 +1120,8 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
 // id, and the selection at depth >= 1 is wave_select_tree_gumbel, which reads the parent's.
 // FO has FpuOpts (sz_set_fpu): the arg-max that decides otherwise scores unvisited children by the site's first-play value, the root's at
 // depth 0 and the tree's below.
+// FO has PuctOpts (sz_set_cpuct, never with GumbelOpts): every selection reads puct_c at its parent's count in c_puct's place, the root's triple
+// at depth 0 and the tree's below.
 template <bool VL, bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __restrict__ policy, const float* __restrict__ value, void* planes, Batch vb, FO... fo) {
     constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
@@ -1116,6 +1130,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     constexpr bool GUMBEL = has_opt<GumbelOpts, FO...> || GTREE;
     static_assert(!GUMBEL || (!VL && !SOLVE && !FORCED), "sz_set_gumbel refuses leaf batching, the solver and forced playouts");
     static_assert(!GTREE || !FPU, "sz_set_gumbel_tree consults neither site of sz_set_fpu");
+    constexpr bool PUCT = has_opt<PuctOpts, FO...>;
+    static_assert(!GUMBEL || !PUCT, "sz_set_gumbel and sz_set_cpuct refuse each other");
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -1261,6 +1277,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             int bi = -1;
             EdgeStat ps;                                                // sz_set_fpu: vp comes from the parent's own stored edge (cur; the root is edge 0)
             if constexpr (FPU) ps = bp.es[cur];
+            float c_puct = v.c_puct;                                    // sz_set_cpuct: the rate at this parent's count, once per selection
+            if constexpr (PUCT) c_puct = puct_c(opt_of<PuctOpts>(fo...).o, parentN, d == 0);
             // In order: a forced child of the root (sz_set_forced_playouts), else the Gumbel rule at the root (sz_set_gumbel), else the arg-max.
             // Without FPU the forced root keeps its own composition, wave_select_root_forced, and counts through `forced`: folded into the
             // sequence below, three of the four k_search_step<.., ForcedOpts> instantiations spill 8 to 24 bytes more per lane.
@@ -1287,15 +1305,15 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
                 }
             } else if (FORCED && !FPU && d == 0 && (status & ST_FORCED)) {
                 if constexpr (FORCED)
-                    bi = wave_select_root_forced<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, opt_of<ForcedOpts>(fo...).k, &forced);
+                    bi = wave_select_root_forced<VL, SOLVE>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, c_puct, vb.lam, opt_of<ForcedOpts>(fo...).k, &forced);
             } else if (bi < 0) {
                 if constexpr (FPU) {
                     // sz_set_fpu: the root's mode and value at depth 0, the tree's below
                     const sz_fpu_options& fp = opt_of<FpuOpts>(fo...).o;
-                    bi = wave_select_child<VL, SOLVE, true>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, d == 0 ? fp.root_mode : fp.tree_mode,
+                    bi = wave_select_child<VL, SOLVE, true>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, c_puct, vb.lam, d == 0 ? fp.root_mode : fp.tree_mode,
                                                             d == 0 ? fp.root_value : fp.tree_value, uni(ps.N), uni_f64(ps.W), nullptr);
                 } else
-                    bi = wave_select_child<VL, SOLVE, false>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, v.c_puct, vb.lam, SZ_FPU_REFERENCE, 0.f, 0, 0.0, nullptr);
+                    bi = wave_select_child<VL, SOLVE, false>(bp.es + m.first, bp.em + m.first, vk + m.first, mn, parentN, c_puct, vb.lam, SZ_FPU_REFERENCE, 0.f, 0, 0.0, nullptr);
             }
             n_forced += forced ? 1 : 0;
             cur = m.first + bi;
@@ -1496,12 +1514,15 @@ __device__ void wave_keep_subtree(const View& v, const BoardPtrs& bp, int b, int
 // v_mix and the root's network value are left for sz_fetch_gumbel; the record keeps the counted visits
 // FO holds TempOpts (sz_set_move_temperature): the move is wave_temperature's, from the counts the sampling reads (pruned on a forced board), after
 // the ending decision; the record and the subtree kept are untouched
+// FO holds PuctOpts (sz_set_cpuct, only beside ForcedOpts): wave_prune reads the root triple's c at the root's counted N in c_puct's place
 template <bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO... fo) {
     constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
     constexpr bool ENDING = has_opt<EndOpts, FO...>;
     constexpr bool GUMBEL = has_opt<GumbelOpts, FO...>;
     constexpr bool TEMP = has_opt<TempOpts, FO...>;
+    constexpr bool PUCT = has_opt<PuctOpts, FO...>;
+    static_assert(!PUCT || (FORCED && !GUMBEL), "policy-target pruning is k_play's only use of the exploration rate");
     static_assert(!GUMBEL || (!SOLVE && !FORCED && !ENDING && !TEMP), "sz_set_gumbel refuses the solver, forced playouts, endings and the move temperature");
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
@@ -1551,7 +1572,12 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     }
     if constexpr (FORCED) {
         if (status & ST_FORCED) {                                        // the zero-visit check above stays on the counted visits
-            const int cut = wave_prune(bp.es + first, n, uni(bp.es[0].N), v.c_puct, opt_of<ForcedOpts>(fo...).k, vis_lds, nullptr);
+            int cut;
+            if constexpr (PUCT) {                                        // sz_set_cpuct: the root triple's rate at the root's counted N
+                const int rootN = uni(bp.es[0].N);
+                cut = wave_prune(bp.es + first, n, rootN, puct_c(opt_of<PuctOpts>(fo...).o, rootN, true), opt_of<ForcedOpts>(fo...).k, vis_lds, nullptr);
+            } else
+                cut = wave_prune(bp.es + first, n, uni(bp.es[0].N), v.c_puct, opt_of<ForcedOpts>(fo...).k, vis_lds, nullptr);
             __syncthreads();
             total -= cut;
             if (v.rec_action) for (int c = lane; c < n; c += 64) v.rec_visits[(size_t)b * SZ_MAX_CHILDREN + c] = vis_lds[c];
@@ -1864,10 +1890,16 @@ __global__ __launch_bounds__(64) void k_debug_temperature(const int* offsets, co
     if (lane == 0) { chosen_out[cs] = mv; kind_out[cs] = kind; nelig_out[cs] = ne; pch_out[cs] = p; excl_out[cs] = ex; }
 }
 
+// test hook (sz_debug_cpuct): puct_c, the function the option's k_search_step and k_play call, on caller-supplied cases, one lane per case
+__global__ __launch_bounds__(64) void k_debug_cpuct(const int* n_p, const uint8_t* is_root, const sz_cpuct_options* opts, float* c_out, int n_cases) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n_cases) c_out[i] = puct_c(opts[i], n_p[i], is_root[i] != 0);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
-// what sz_set_forced_playouts, sz_set_fpu and sz_set_gumbel set for the next sz_search_begin, which takes it up whole: a search, its descent-only
+// what sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel and sz_set_cpuct set for the next sz_search_begin, which takes it up whole: a search, its descent-only
 // launch, its steps and its sz_play run with what its sz_search_begin saw, whatever the setters are told in between
 struct Latched {
     float forced_k;                 // the forced constant, 0 = off; > 0 selects the FORCED instantiations
@@ -1875,6 +1907,8 @@ struct Latched {
     int gumbel_on;                  // != 0 selects the GUMBEL instantiations ...
     sz_gumbel_options gumbel; const double* gumbel_g;      // ... which run with these
     int gumbel_tree;                // sz_set_gumbel_tree: != 0 (only beside gumbel_on) selects k_search_step<false, false, GumbelTreeOpts>
+    int cpuct_on;                   // sz_set_cpuct: != 0 (never beside gumbel_on) selects the instantiations that take PuctOpts ...
+    sz_cpuct_options cpuct;         // ... which run with these
 };
 
 struct sz_engine {
@@ -1895,7 +1929,7 @@ struct sz_engine {
     std::vector<void*> vb_allocs;
     int solver;                     // sz_set_solver: the SOLVE instantiations of begin / step / play run
     unsigned long long* d_sstat;    // its counters [n_boards][2], allocated by the first enabling call
-    Latched next, cur;              // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel: what the next sz_search_begin takes up, and what it took up last
+    Latched next, cur;              // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel, sz_set_cpuct: what the next sz_search_begin takes up, and what it took up last
     ForcedOpts fo;                  // sz_set_forced_playouts: fo.boards [n_boards] and fo.stat [n_boards][2], allocated by the first enabling call
     GumbelOpts go;                  // sz_set_gumbel: its arrays, allocated by the first enabling call (go.stat != NULL from then on)
     float* gt_nval;                 // sz_set_gumbel_tree: the node values [n_boards][n_cap] and the counter [n_boards], allocated by the first
@@ -1930,7 +1964,7 @@ template <typename T> static int dalloc(sz_engine* e, T** p, size_t count) {
 // is called with two std::bool_constants, VL = leaf batching on (vb.L > 1; instantiations without it take an empty Batch) and SOLVE = the solver
 // on, and with the option structs in force, in the order the kernels take them: ForcedOpts or else GumbelOpts (the search begun last, e->cur;
 // under Gumbel VL = SOLVE = false, which the setters' refusals see to; GumbelTreeOpts in its place and no FpuOpts under sz_set_gumbel_tree),
-// FpuOpts (e->cur), TempOpts (sz_set_move_temperature; never beside GumbelOpts), EndOpts (sz_set_endings; `proven` cleared while the
+// FpuOpts (e->cur), PuctOpts (e->cur; never beside GumbelOpts), TempOpts (sz_set_move_temperature; never beside GumbelOpts), EndOpts (sz_set_endings; `proven` cleared while the
 // solver is off; never beside GumbelOpts).  Each kernel takes the members of the pack that concern it: pick below.
 template <typename F> static void with_search_options(const sz_engine* e, F&& f) {
     const Latched& c = e->cur;
@@ -1944,8 +1978,13 @@ template <typename F> static void with_search_options(const sz_engine* e, F&& f)
         else if (e->temp_on) endings(vl, solve, o..., e->to);
         else endings(vl, solve, o...);
     };
+    auto puct = [&](auto vl, auto solve, auto... o) {
+        if constexpr (has_opt<GumbelOpts, decltype(o)...>) temperature(vl, solve, o...);
+        else if (c.cpuct_on) temperature(vl, solve, o..., PuctOpts{c.cpuct});
+        else temperature(vl, solve, o...);
+    };
     auto fpu = [&](auto vl, auto solve, auto... o) {
-        if (c.fpu.tree_mode != SZ_FPU_REFERENCE || c.fpu.root_mode != SZ_FPU_REFERENCE) temperature(vl, solve, o..., FpuOpts{c.fpu}); else temperature(vl, solve, o...);
+        if (c.fpu.tree_mode != SZ_FPU_REFERENCE || c.fpu.root_mode != SZ_FPU_REFERENCE) puct(vl, solve, o..., FpuOpts{c.fpu}); else puct(vl, solve, o...);
     };
     auto forced = [&](auto vl, auto solve) {
         if (c.forced_k > 0.0f) { ForcedOpts fo = e->fo; fo.k = c.forced_k; fpu(vl, solve, fo); } else fpu(vl, solve);
@@ -2128,10 +2167,11 @@ struct OptionState {
     bool forced, gumbel;            // sz_set_forced_playouts, sz_set_gumbel: what the next sz_search_begin takes up
     bool endings, noise;            // sz_set_endings; sz_set_root_noise / sz_set_search_root_noise with a gamma
     bool temperature;               // sz_set_move_temperature
+    bool cpuct;                     // sz_set_cpuct: what the next sz_search_begin takes up
 };
 enum OptionSetter { BY_ANY, BY_LEAF_BATCHING, BY_SOLVER, BY_ROOT_NOISE };     // the setters whose own entry point accepts less than the engine runs
 static OptionState option_state(const sz_engine* e) {
-    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0};
+    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0, e->next.cpuct_on != 0};
 }
 static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter by = BY_ANY) {
     const bool reuse = e->v.reuse != 0;
@@ -2144,6 +2184,7 @@ static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter
     if (by == BY_SOLVER && p.solver && (reuse || p.L > 1)) return SZ_ERR_INVALID;
     if (p.gumbel && p.noise) return SZ_ERR_STATE;                           // Gumbel is the root's exploration
     if (p.gumbel && p.temperature) return SZ_ERR_STATE;                     // ... and chooses its own move
+    if (p.gumbel && p.cpuct) return SZ_ERR_STATE;                           // Gumbel's rule is a chain of its own: the combination is a follow-up
     // sz_set_root_noise: a reused root was expanded as an inner node, on un-noised priors, and is never expanded again, so the noise would silently
     // apply to the first ply of a game only; and a reuse engine under sz_set_search_root_noise leaves that mode through that setter, which drops
     // the kept subtrees
@@ -2305,14 +2346,14 @@ static void launch_step(sz_engine* e, const float* policy, const float* value, v
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         std::apply([&](auto... k) {
             hipLaunchKernelGGL((k_search_step<VL, SOLVE, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, k...);
-        }, pick<ForcedOpts, GumbelOpts, GumbelTreeOpts, FpuOpts>(o...));    // the ending rules live in sz_play alone
+        }, pick<ForcedOpts, GumbelOpts, GumbelTreeOpts, FpuOpts, PuctOpts>(o...));      // the ending rules live in sz_play alone
     });
 }
 
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    e->cur = e->next;                                                       // sz_set_forced_playouts, sz_set_fpu and sz_set_gumbel take effect here
+    e->cur = e->next;                                                       // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel and sz_set_cpuct take effect here
     with_search_options(e, [&](auto vl, auto solve, auto... o) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         std::apply([&](auto... k) {
@@ -2475,6 +2516,27 @@ int sz_set_fpu(sz_engine* e, const sz_fpu_options* opt, void* stream) {
     if (o.tree_mode == SZ_FPU_REFERENCE) o.tree_value = 0.0f;
     if (o.root_mode == SZ_FPU_REFERENCE) o.root_value = 0.0f;
     e->next.fpu = o;
+    return SZ_OK;
+}
+
+static bool cpuct_site_ok(float init, float base, float factor) {
+    if (!std::isfinite(init) || !std::isfinite(base) || !std::isfinite(factor)) return false;
+    return init >= 0.0f && init <= 100.0f && factor >= 0.0f && factor <= 100.0f && base >= 1.0f && base <= 1e9f;
+}
+
+int sz_set_cpuct(sz_engine* e, const sz_cpuct_options* opt, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (opt && (!cpuct_site_ok(opt->tree_init, opt->tree_base, opt->tree_factor) || !cpuct_site_ok(opt->root_init, opt->root_base, opt->root_factor))) return SZ_ERR_INVALID;
+    OptionState p = option_state(e);
+    p.cpuct = opt != nullptr;
+    const int refused = option_refusal(e, p);
+    if (refused == SZ_ERR_INVALID) return refused;
+    ENGINE_GUARD(e);
+    int rc = between_searches(e, (hipStream_t)stream);
+    if (rc) return rc;
+    if (!opt) { e->next.cpuct_on = 0; e->next.cpuct = sz_cpuct_options{}; return SZ_OK; }
+    if (refused) return refused;                                            // Gumbel is on: SZ_ERR_STATE, after the question whether the engine searches
+    e->next.cpuct = *opt; e->next.cpuct_on = 1;
     return SZ_OK;
 }
 
@@ -2709,9 +2771,12 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     with_search_options(e, [&](auto, auto solve, auto... o) {
-        std::apply([&](auto... k) {
+        auto launch = [&](auto... k) {
             hipLaunchKernelGGL((k_play<decltype(solve)::value, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, k...);
-        }, pick<ForcedOpts, GumbelOpts, TempOpts, EndOpts>(play_opt(o)...));   // first-play urgency acts in the descent alone
+        };
+        // first-play urgency acts in the descent alone; the exploration rate reaches k_play for pruning alone, so only beside ForcedOpts
+        if constexpr (has_opt<ForcedOpts, decltype(o)...>) std::apply(launch, pick<ForcedOpts, GumbelOpts, PuctOpts, TempOpts, EndOpts>(play_opt(o)...));
+        else std::apply(launch, pick<ForcedOpts, GumbelOpts, TempOpts, EndOpts>(play_opt(o)...));
     });
     HIPCHK(hipGetLastError());
     return SZ_OK;
@@ -2912,6 +2977,13 @@ int sz_debug_gumbel(const double* x_dev, double* slog_out_dev, double* sexp_out_
     hipLaunchKernelGGL(k_debug_gumbel, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(double) + sizeof(float)), (hipStream_t)stream,
                        x_dev, slog_out_dev, sexp_out_dev, tnm_dev, level_out_dev, offsets_dev, vc_dev, value_sum_dev, prior_dev, g_dev, visit_dev, goal_dev,
                        root_value_dev, opts_dev, selected_out_dev, fallback_out_dev, final_out_dev, policy_out_dev, v_mix_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_cpuct(const int32_t* n_p_dev, const uint8_t* is_root_dev, const sz_cpuct_options* opts_dev, float* c_out_dev, int32_t n_cases, void* stream) {
+    if (!n_p_dev || !is_root_dev || !opts_dev || !c_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_cpuct, dim3((n_cases + 63) / 64), dim3(64), 0, (hipStream_t)stream, n_p_dev, is_root_dev, opts_dev, c_out_dev, n_cases);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

@@ -183,6 +183,43 @@ def fpu_options_of(args):
     return tuple(out)
 
 
+CPUCT_KEYS = ("init", "base", "factor", "root_init", "root_base", "root_factor")
+CPUCT_RANGES = {"init": (0.0, 100.0), "base": (1.0, 1e9), "factor": (0.0, 100.0)}
+
+
+def cpuct_options_of(args):
+    """The visit-dependent exploration rate of args, checked: (tree_init, tree_base, tree_factor, root_init, root_base, root_factor) rounded to
+    f32, or None when the key is absent.  NON-REFERENCE, default off.
+
+    args["cpuct"] = {"init": c, "base": 19652, "factor": 1, "root_init": ..., "root_base": ..., "root_factor": ...} replaces the constant C of
+    selection by c(n_p) = init + factor * ln((n_p + base + 1) / base), n_p the parent's visit count (sz_set_cpuct): AlphaZero's schedule is
+    {"init": 1.25}, lc0's CPuct / CPuctBase / CPuctFactor with its ...AtRoot triple map onto the six keys.  init / base / factor hold below
+    the root, the root_ keys where a child of the root is selected and in policy-target pruning; each of the root's defaults to the tree's.
+    init is required and lies in [0, 100], base in [1, 1e9], factor in [0, 100].  factor 0 is the constant init.  Refused with args["gumbel"].
+    Checked in this order: the dict and its keys, init, base, factor, root_init, root_base, root_factor, the combinations.  Its effect on
+    playing strength is unmeasured."""
+    opt = args.get("cpuct")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(CPUCT_KEYS):
+        raise ValueError("args['cpuct'] must be a dict with keys from %s, got %r" % (CPUCT_KEYS, opt))
+    if "init" not in opt:
+        raise ValueError("args['cpuct'] needs 'init'")
+    tree = {"init": opt["init"], "base": opt.get("base", 19652.0), "factor": opt.get("factor", 1.0)}
+    out = []
+    for prefix in ("", "root_"):
+        for key in ("init", "base", "factor"):
+            x = opt.get(prefix + key, tree[key])
+            lo, hi = CPUCT_RANGES[key]
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or \
+                    not (math.isfinite(x) and lo <= float(np.float32(x)) <= float(np.float32(hi))):     # NaN fails the comparison
+                raise ValueError("args['cpuct'][%r] must be a number in [%g, %g], got %r" % (prefix + key, lo, hi, x))
+            out.append(float(np.float32(x)))
+    if args.get("gumbel") is not None:
+        raise ValueError("args['cpuct'] and args['gumbel'] exclude each other: the Gumbel rule is a chain of its own, combining them is a follow-up")
+    return tuple(out)
+
+
 GUMBEL_KEYS = ("m", "c_visit", "c_scale")
 
 
@@ -391,6 +428,8 @@ class SelfPlayEngine:
             raise ValueError("args['forced_playouts'] needs learning=True: it is an exploration option of self-play, like root noise")
         # NON-REFERENCE option (default off): first-play urgency for unvisited children, see fpu_options_of
         self.fpu = fpu_options_of(self.args)
+        # NON-REFERENCE option (default off): AlphaZero's visit-dependent exploration rate in C's place, see cpuct_options_of
+        self.cpuct = cpuct_options_of(self.args)
         # NON-REFERENCE option (default off): Gumbel root search with sequential halving and the completed-Q policy target, see gumbel_options_of
         self.gumbel = gumbel_options_of(self.args)
         self._gumbel_g = None         # the device copy of the Gumbel draws in force (set_gumbel)
@@ -453,6 +492,8 @@ class SelfPlayEngine:
             self.set_forced_playouts(self.forced_k)
         if self.fpu is not None:
             self.set_fpu(self.fpu)
+        if self.cpuct is not None:
+            self.set_cpuct(self.cpuct)
         if self.gumbel is not None:    # g = None (a deterministic search) until set_gumbel hands over draws
             self.set_gumbel(self.gumbel)
         if self.gumbel_tree:
@@ -578,6 +619,14 @@ class SelfPlayEngine:
         o = None if opts is None else N.sz_fpu_options(int(opts[0]), float(opts[1]), int(opts[2]), float(opts[3]))
         N.check(N.lib().sz_set_fpu(self._e, None if o is None else C.byref(o), self._stream()), "sz_set_fpu")
         self.fpu = None if opts is None else tuple(opts)
+
+    def set_cpuct(self, opts):
+        """The visit-dependent exploration rate (sz_set_cpuct, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (tree_init,
+        tree_base, tree_factor, root_init, root_base, root_factor) as cpuct_options_of returns it, or None = off (args["C"] again).  Between
+        searches only; kept subtrees are not dropped; refused while the Gumbel search is on."""
+        o = None if opts is None else N.sz_cpuct_options(*[float(x) for x in opts])
+        N.check(N.lib().sz_set_cpuct(self._e, None if o is None else C.byref(o), self._stream()), "sz_set_cpuct")
+        self.cpuct = None if opts is None else tuple(float(x) for x in opts)
 
     def set_gumbel(self, opts, g=None):
         """Gumbel root search (sz_set_gumbel, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (m, c_visit, c_scale) as

@@ -116,6 +116,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     holdout flags of the games it starts.  The extra per-ply host copy (sz_fetch_endings) happens in this mode only.  Strength effect unmeasured.
     args["fpu"] = {...} (NON-REFERENCE, selfplay.fpu_options_of): first-play urgency, what selection takes an unvisited child to be worth
     (sz_set_fpu), one setting for the root and one below it, on fast and full plies alike; the engine applies it.  Strength effect unmeasured.
+    args["cpuct"] = {...} (NON-REFERENCE, selfplay.cpuct_options_of): AlphaZero's visit-dependent exploration rate in the place of the constant
+    C (sz_set_cpuct), one triple for the root and one below it, on fast and full plies alike; the engine applies it.  Strength effect unmeasured.
     args["gumbel"] = {"m": m, "c_visit": x, "c_scale": y} (NON-REFERENCE, selfplay.gumbel_options_of): the Gumbel root search (sz_set_gumbel), on fast
     and full plies alike.  The move is the search's own choice (`uniforms` is still drawn as always and not read by the engine) and a sample's
     'actions' dict holds the completed-Q improved policy as Python floats instead of visit fractions.  With `learning` the Gumbel(0,1) draws

@@ -462,7 +462,7 @@ def write_step_log(path, epoch, hist, lr_scheduler, append=True):
 
 def selfplay_args_of(a):
     """the self-play `args` dict of main()'s parsed flags `a`; nothing is checked here: the engine's option readers (selfplay.search_options_of,
-    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, temperature_options_of, sim.playout_cap_of) refuse what does not go together"""
+    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, temperature_options_of, cpuct_options_of, sim.playout_cap_of) refuse what does not go together"""
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
@@ -496,6 +496,10 @@ def selfplay_args_of(a):
                                       ("fast", a.temperature_fast), ("visit_offset", a.temp_visit_offset), ("value_cutoff", a.temp_value_cutoff)) if val is not None}
     if temp:
         args["temperature"] = temp
+    cpuct = {key: val for key, val in (("init", a.cpuct_init), ("base", a.cpuct_base), ("factor", a.cpuct_factor), ("root_init", a.cpuct_root_init),
+                                       ("root_base", a.cpuct_root_base), ("root_factor", a.cpuct_root_factor)) if val is not None}
+    if cpuct:
+        args["cpuct"] = cpuct
     return args
 
 
@@ -581,6 +585,15 @@ def flag_parser():
                     help="added to every visit count before the power; a move it leaves at or below 0 is not sampled (lc0 TempVisitOffset)")
     ap.add_argument("--temp-value-cutoff", type=float, default=None, metavar="D",
                     help="a move whose value lies more than D below the most visited move's is not sampled (lc0 TempValueCutoff)")
+    ap.add_argument("--cpuct-init", type=float, default=None, metavar="C",
+                    help="NON-REFERENCE: selection's exploration rate grows with the parent's visit count, c = C + F * ln((n_p + B + 1) / B), in the "
+                         "place of the constant 2 (args['cpuct'], sz_set_cpuct; AlphaZero: 1.25 with the defaults B = 19652, F = 1); any of the six "
+                         "cpuct flags switches the option on and needs this one; not combined with --gumbel; strength effect unmeasured")
+    ap.add_argument("--cpuct-base", type=float, default=None, metavar="B", help="the base of --cpuct-init's logarithm, in [1, 1e9] (default 19652)")
+    ap.add_argument("--cpuct-factor", type=float, default=None, metavar="F", help="the factor of --cpuct-init's logarithm, in [0, 100] (default 1; 0 = the constant C)")
+    ap.add_argument("--cpuct-root-init", type=float, default=None, metavar="C", help="C where a child of the root is selected and in policy-target pruning (default --cpuct-init)")
+    ap.add_argument("--cpuct-root-base", type=float, default=None, metavar="B", help="B at the root (default --cpuct-base)")
+    ap.add_argument("--cpuct-root-factor", type=float, default=None, metavar="F", help="F at the root (default --cpuct-factor)")
     return ap
 
 
@@ -654,6 +667,7 @@ def main(argv=None):
                                         "endings": args.get("endings"), "ending_report": ending_report(games) if args.get("endings") else None,
                                         "temperature": args.get("temperature"), "tempered_plays": sp_stats.get("tempered_plays"),
                                         "greedy_plays": sp_stats.get("greedy_plays"), "excluded_children": sp_stats.get("excluded_children"),
+                                        "cpuct": args.get("cpuct"),
                                         "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"

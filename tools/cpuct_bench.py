@@ -1,0 +1,109 @@
+"""The visit-dependent exploration rate (args["cpuct"], sz_set_cpuct): what a search step costs with the option off and on, on the GPU.
+4096 boards from the start position, bf16 MFMA network with random-init weights, a learning engine; whole searches of --searches simulations
+are timed.  Legs: the option off, on (AlphaZero's schedule, {"init": 1.25, "base": 19652, "factor": 1}: every selection forms its rate with
+one sz_slog) and, with --parent-tree DIR (a checkout of the parent commit with its library built), the default path of that checkout, so
+that "no default kernel changed" is also a measurement.  The legs run alternately (off, on[, parent], off, ...), one fresh process per run
+under its own time limit, all in one session on one GPU; the first run that fails ends the tool.  Reported per search:
+
+  ms per step       wall time of SelfPlayEngine.search (network call + tree step, every step of the search) / its number of steps
+
+and per leg the spread of its repeats, beside the mean leaf depth (sz_stats sum_depth / simulations: how the option changes the shape of the
+search).  Nothing is gated.  With random-init weights the figures say nothing about a trained network's search; the effect of the option on
+playing strength is unmeasured.
+
+    python tools/cpuct_bench.py --searches 64 --out profiles/cpuct_bench_64.txt
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ON = {"init": 1.25, "base": 19652, "factor": 1}
+
+
+def child(leg, root, boards, searches, plies):
+    import torch
+    sys.path.insert(0, root)
+    import sigma_zero_amd as sz
+    from sigma_zero_amd.fastnet import FastPolicyNet
+    from sigma_zero_amd.selfplay import SelfPlayEngine
+    assert torch.cuda.is_available(), "needs an MI355X"
+    torch.manual_seed(0)
+    net = FastPolicyNet(sz.policyNN({}).cuda().eval(), operands="bf16")
+    args = {"C": 2, "num_searches": searches}
+    if leg == "on":
+        args["cpuct"] = ON
+    eng = SelfPlayEngine(net, args, boards, learning=True, planes_dtype="bits128")
+    warm = SelfPlayEngine(net, dict(args, num_searches=8), boards, learning=True, planes_dtype="bits128")
+    warm.new_games([-1] * boards)
+    warm.search()                                            # warm-up on a throw-away engine: code objects, buffers, the network's first calls
+    warm.check_errors()
+    warm.close()
+    eng.new_games([-1] * boards)
+    ms, depth = [], []
+    for ply in range(plies):
+        st0 = eng.stats()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.search()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        st = eng.check_errors()
+        assert st["boards_pending"] == 0 and eng.last_steps > 0
+        ms.append(1000.0 * dt / eng.last_steps)
+        depth.append(float(st["sum_depth"] - st0["sum_depth"]) / max(int(st["simulations"] - st0["simulations"]), 1))
+        eng.play([-1.0] * boards)
+    eng.close()
+    print("RESULT " + json.dumps(dict(leg=leg, boards=boards, searches=searches, ms=ms, depth=depth, device=torch.cuda.get_device_name(0))), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--boards", type=int, default=4096)
+    ap.add_argument("--searches", type=int, default=64)
+    ap.add_argument("--plies", type=int, default=2, help="timed searches per process")
+    ap.add_argument("--rounds", type=int, default=3, help="rounds of the legs, run alternately")
+    ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its library built: adds the `parent` leg")
+    ap.add_argument("--timeout", type=int, default=150, help="seconds per child")
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--root", default=ROOT)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.root, a.boards, a.searches, a.plies)
+    legs = ["off", "on"] + (["parent"] if a.parent_tree else [])
+    lines, device, per_leg = [], None, {leg: [] for leg in legs}
+    for rnd in range(a.rounds):
+        for leg in legs:
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", "off" if leg == "parent" else leg, "--boards", str(a.boards), "--searches", str(a.searches),
+                   "--plies", str(a.plies), "--root", os.path.abspath(a.parent_tree) if leg == "parent" else ROOT]
+            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=a.timeout)      # the parent never opens the GPU
+            res = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not res:
+                print(p.stdout[-4000:])
+                raise SystemExit("leg %s of round %d failed (exit status %d): stopping here" % (leg, rnd, p.returncode))
+            r = json.loads(res[-1][len("RESULT "):])
+            device = r["device"]
+            per_leg[leg] += r["ms"]
+            lines.append("round %d  %-6s  ms per step: %s   mean leaf depth: %s" % (rnd, leg, "  ".join("%.4f" % x for x in r["ms"]), "  ".join("%.3f" % x for x in r["depth"])))
+            print(lines[-1], flush=True)
+    for leg in legs:
+        v = sorted(per_leg[leg])
+        lines.append("%-6s  median %.4f ms per step over %d searches, mean %.4f, min %.4f, max %.4f (spread %.1f %% of the median)"
+                     % (leg, v[len(v) // 2], len(v), sum(v) / len(v), v[0], v[-1], 100.0 * (v[-1] - v[0]) / v[len(v) // 2]))
+        print(lines[-1], flush=True)
+    head = ("tools/cpuct_bench.py on %s: %d boards from the start position, bf16 network, random-init weights, learning engine, searches of %d\n"
+            "simulations; `on` = args[\"cpuct\"] = %s%s; legs run alternately in one session, one process per run, after a warm-up search on a\n"
+            "throw-away engine.  Nothing is gated.\n"
+            % (device, a.boards, a.searches, json.dumps(ON), "; `parent` = the default path of a checkout of the parent commit" if a.parent_tree else ""))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(head + "\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
