@@ -9,11 +9,16 @@
  * device memory; tensors handed in by pointer stay owned by the caller; all device work is enqueued
  * on the caller's stream (pass torch.cuda.current_stream().cuda_stream), which must belong to the
  * engine's device (sz_config.device); every call makes that device current for its duration and
- * restores the caller's current device; not thread-safe.  One engine per GPU per process is the usual
- * arrangement (self-play fills the card with one), a usage note and not a constraint: the library keeps no
- * process-global state, and several engines may live side by side on one device (arena.play_options_match
+ * restores the caller's current device; not thread-safe.  "All device work" means launches, copies,
+ * fills and the waits in front of host reads alike.  tests/test_gpu_stream_contract.py holds every
+ * entry point to that on a non-default stream, bit for bit.  One engine per GPU per process is the usual
+ * arrangement (self-play fills the card with one), a usage note and not a constraint: engines share
+ * nothing, and several may live side by side on one device (arena.play_options_match
  * holds two).  Give each an explicit edges_per_board then: the default sizes the first one to half of the
- * free HBM.
+ * free HBM.  The network launches (sz_nn_*) do keep state per device and process: the persistent tower's
+ * pacing counters, the function-attribute flags and the stamp pointers of the diagnostic builds.  It is
+ * safe in program order on one stream at a time; two streams with network launches in flight at once are
+ * not supported.
  */
 #ifndef SIGMAZERO_H
 #define SIGMAZERO_H

@@ -1343,7 +1343,10 @@ static int tower_launch(const void* planes, const void* const* w_packed, const f
         if (pace_on < 0) { const char* ev = getenv("SZ_NN_PACE"); pace_on = (ev && ev[0] == '0') ? 0 : 1; }
         if (pace_on && grid.x % 8 == 0 && n_tiles % (int)grid.x == 0) {
             const int slot = current_device_slot();
-            if (!pace_buf[slot]) { HIPCHK(hipMalloc(&pace_buf[slot], 8 * sizeof(unsigned long long))); HIPCHK(hipMemset(pace_buf[slot], 0, 8 * sizeof(unsigned long long))); }
+            if (!pace_buf[slot]) {      // zeroed on the launch's own stream: a fill on the null stream is not ordered before a launch on a non-blocking stream
+                HIPCHK(hipMalloc(&pace_buf[slot], 8 * sizeof(unsigned long long)));
+                HIPCHK(hipMemsetAsync(pace_buf[slot], 0, 8 * sizeof(unsigned long long), (hipStream_t)stream));
+            }
             prm.pace = pace_buf[slot]; prm.pace_base = pace_total[slot];
             pace_add = (unsigned long long)(n_tiles / (int)grid.x) * (grid.x / 8); pace_slot = &pace_total[slot];
         }

@@ -32,6 +32,10 @@ step: dominated by ReLU branch flips (an input within rounding of zero takes the
 ranges over 1e-6 .. 5e-3 for ANY fp32 implementation (MIOpen's step included) depending on which inputs flip; with the device's ReLU masks given to both
 steps, MIOpen's is ~1.3e-6 and this one ~2x that (tests/test_gpu_train_fp64.py).  OPERANDS_F16 = False selects hi + lo bf16 operands for forward / backward-data
 (16 bits: 4.5e-6 per convolution, gradient 1.1e-2) with torch's weight gradient; WGRAD_KERNEL = False keeps torch's weight gradient.
+One stream at a time: `_scratch` (the forward weight stream every convolution rewrites, the weight gradient's partial sums) is one set of buffers per device, shared
+by every convolution of every model in the process.  Program order on any ONE stream keeps it correct, the default stream or another — two models stepped alternately
+on a side stream equal their default-stream run bit for bit, tests/test_gpu_stream_contract.py::test_train_kernels_stay_on_the_callers_stream — but two streams with
+train kernels in flight at the same time race on it and are not supported.
 """
 import contextlib
 import ctypes as C
