@@ -766,6 +766,66 @@ int sz_set_cpuct(sz_engine* e, const sz_cpuct_options* opt, void* stream);
  * otherwise.  opts are not checked.  All device pointers. */
 int sz_debug_cpuct(const int32_t* n_p_dev, const uint8_t* is_root_dev, const sz_cpuct_options* opts_dev, float* c_out_dev, int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, default off: KLD-gain early stopping of a board's search (lc0's minimum-kldgain-per-node / kldgain-average-interval;
+ * its training runs used 5e-6 and 100).  Every other option changes where a simulation goes; this one lets a board stop when further
+ * simulations no longer change its answer: the root's visit distribution is compared with its last snapshot at check points the caller chooses,
+ * and the board's goal is lowered to what it has made and has in flight when the Kullback-Leibler gain per new visit is below min_gain.
+ * Never switched on, every kernel that runs today runs unchanged, and with it on too: k_search_begin, k_search_step and k_play have no variant.
+ * The rule lives in small kernels of its own beside them; the search kernels read the board's goal where they read a budget.
+ * Per-board state, reset by sz_search_begin for every board that starts a search, fresh or continued: prev[SZ_MAX_MOVES] (int32, the root
+ * children's N at the last snapshot), prev_total = 0, has_prev = 0, stopped_at = -1, checks = 0, last_gain = NaN.
+ * The check (sz_search_check_stop), one wavefront per board, for a board that searches, is not done, not in error and has stopped_at < 0:
+ *   1. K = the root's child count.  K == 0 (the root is not expanded yet): nothing happens.
+ *   2. now_c = N_c of the root's children in action order: counted visits only, the in-flight counts k of leaf batching are not included.
+ *      new_total = sum of now_c, in integer arithmetic.
+ *   3. new_total < prev_total + interval: nothing happens.
+ *   4. has_prev != 0 and prev_total > 0: the gain is formed, all in f64, every operator one IEEE rounding (-ffp-contract=off); slog is
+ *      sz_set_gumbel's (csrc/sz_gumbel.h), the term is sz_kld_term in csrc/sz_kldgain.h, plain C++ for host and device:
+ *        for every child with prev_c != 0:  o = (double)prev_c / (double)prev_total;  n = (double)now_c / (double)new_total;
+ *                                           term_c = o * slog(o / n)              (0.0 for a child with prev_c == 0)
+ *        gain = the sum of the terms in the fixed order: lane l adds term_l, term_{l+64}, ... ascending from 0.0, then the xor butterfly
+ *               (offsets 32, 16, .., 1: acc = acc + other)
+ *        g = gain / (double)(new_total - prev_total);  last_gain = g;  checks += 1
+ *      Visits never fall within a search, so now_c >= prev_c > 0 and slog's precondition holds.  The board stops iff
+ *      g < min_gain && sims_done >= min_simulations (sims_done: the new simulations this search has made).
+ *   5. a stop: stopped_at = goal[b] = sims_done + pending, pending the board's leaves in flight (n_pend under leaf batching, else 1 while
+ *      the board waits for the network, else 0).  Nothing else on the board changes: the next sz_search_step consumes what is in flight,
+ *      finds its simulations made, starts no descent and sets the board done.  A board with nothing in flight is set done by the check.
+ *   6. otherwise, the first evaluated check included, which only takes the snapshot: prev = now, prev_total = new_total, has_prev = 1.
+ * The goals: while the option is on every kernel reads a board's simulations from one array, which sz_search_begin fills for every board: the
+ * goal sz_set_visit_targets derives, else the board's budget (sz_set_search_budgets), else num_searches.  sz_search_goals reports that value,
+ * sz_fetch_kld_stop where the board stopped.  Budgets and targets work underneath; the option only ever lowers a goal.
+ * The invariant: a board stopped at s ends with the tree, record and counters of the same search run with goal s from the start (as a budget,
+ * or on a reuse_subtree engine as the visit target s + N_kept - 1), bit for bit; under leaf batching the last gather ended at
+ * sims_done + pending == s either way.
+ * Composes with budgets, visit targets, reuse_subtree (a kept root's children carry their visits into the first snapshot), leaf batching,
+ * the solver (a proven root is done before any check), forced playouts, sz_set_fpu, sz_set_cpuct, root noise, endings, the move temperature,
+ * sz_compact and sz_compact_searching.  sz_set_gumbel plans sequential halving on the goal: the two refuse each other, see the setter.
+ * Held bit for bit to the host restatement tests/kldref.py by tests/test_gpu_kld_stop.py.  Its effect on playing strength is unmeasured. */
+typedef struct sz_kld_stop_options {
+    double  min_gain;          /* stop when the gain per new root-child visit is below this; finite, in (0, 1] */
+    int32_t interval;          /* a check is evaluated only when the root's children gained >= interval visits since the last snapshot; 1..num_searches */
+    int32_t min_simulations;   /* never stop a board before its search has made this many new simulations; 0..num_searches */
+} sz_kld_stop_options;                            /* 16 bytes */
+/* opt == NULL switches the option off.  SZ_ERR_INVALID (nothing is changed): min_gain not finite or outside (0, 1], interval outside
+ * 1..num_searches, min_simulations outside 0..num_searches.  SZ_ERR_STATE: a call during a search (the rule of sz_set_search_budgets; nothing
+ * is changed then); switching on while Gumbel is on for the next search, and sz_set_gumbel(opt != NULL) refuses with SZ_ERR_STATE while this
+ * option is on.  The setter never touches a tree: kept subtrees survive a change.  Holds from the next sz_search_begin until changed. */
+int sz_set_kld_stop(sz_engine* e, const sz_kld_stop_options* opt, void* stream);
+/* the check above for every board: one kernel launch on `stream`, no synchronisation.  With the option off a successful no-op, so that a driver
+ * may call it unconditionally.  SZ_ERR_STATE, as the host knows it without asking the device: before the first sz_search_begin, after sz_play /
+ * sz_play_moves, and after a sz_compact_searching that found no board searching. */
+int sz_search_check_stop(sz_engine* e, void* stream);
+/* host arrays [n_boards], each may be NULL: stopped_at (-1: not stopped), checks and last_gain (NaN: none evaluated) of each board's last
+ * search.  Synchronises the stream.  SZ_ERR_STATE when the option was never on. */
+int sz_fetch_kld_stop(sz_engine* e, int32_t* stopped_at, int32_t* checks, double* last_gain, void* stream);
+/* boards stopped early, checks evaluated, simulations not made (goal at begin - stopped_at), all boards, cumulative; zeros when never on */
+int sz_kld_stop_stats(sz_engine* e, uint64_t out[3], void* stream);
+/* test: the DEVICE code of the gain (wave_kld_gain as k_kld_check calls it) on caller-supplied cases, one wavefront per case: prev / now are
+ * [n_cases][SZ_MAX_MOVES] int32, n_child[i] in 0..SZ_MAX_MOVES the children of case i, the totals are the integer sums of the first n_child[i]
+ * entries; gain_out[i] = the summed gain, before the division by the new visits.  All device pointers. */
+int sz_debug_kld_gain(const int32_t* prev_dev, const int32_t* now_dev, const int32_t* n_child_dev, double* gain_out_dev, int32_t n_cases, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

@@ -52,6 +52,10 @@ class sz_cpuct_options(C.Structure):
                 ("root_init", C.c_float), ("root_base", C.c_float), ("root_factor", C.c_float)]
 
 
+class sz_kld_stop_options(C.Structure):
+    _fields_ = [("min_gain", C.c_double), ("interval", C.c_int32), ("min_simulations", C.c_int32)]
+
+
 class sz_stats(C.Structure):
     _fields_ = [("simulations", C.c_uint64), ("expansions", C.c_uint64), ("terminal_hits", C.c_uint64), ("sum_depth", C.c_uint64),
                 ("sum_children", C.c_uint64), ("max_edges_used", C.c_uint64), ("boards_pending", C.c_int32),
@@ -105,6 +109,11 @@ EXPORTS = {
     "sz_debug_temperature": (C.c_int, [C.c_void_p] * 14 + [C.c_int32, C.c_void_p]),
     "sz_set_cpuct": (C.c_int, [C.c_void_p, C.POINTER(sz_cpuct_options), C.c_void_p]),
     "sz_debug_cpuct": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
+    "sz_set_kld_stop": (C.c_int, [C.c_void_p, C.POINTER(sz_kld_stop_options), C.c_void_p]),
+    "sz_search_check_stop": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sz_fetch_kld_stop": (C.c_int, [C.c_void_p] * 5),
+    "sz_kld_stop_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_debug_kld_gain": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_set_visit_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

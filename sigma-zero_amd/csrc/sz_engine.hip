@@ -36,6 +36,7 @@
 #include "sz_chess.h"
 #include "sz_gumbel.h"
 #include "sz_cpuct.h"
+#include "sz_kldgain.h"
 #include "../../include/sigmazero.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1897,6 +1898,109 @@ __global__ __launch_bounds__(64) void k_debug_cpuct(const int* n_p, const uint8_
 }
 
 // ------------------------------------------------------------------------------------------------
+// NON-REFERENCE option (sz_set_kld_stop; include/sigmazero.h is the rule, sz_kldgain.h the term): a board's search stops when the
+// Kullback-Leibler gain per new root-child visit falls below a threshold.  The rule lives in the kernels below, which the host launches beside
+// k_search_begin and at check points; k_search_begin, k_search_step and k_play have no variant: they read the board's goal where they read a
+// budget, and a stop lowers it.
+// ------------------------------------------------------------------------------------------------
+struct KldStop {
+    sz_kld_stop_options o;
+    int* goal;                  // [B] the goals in force: View::budget (and BeginOpts::goal under visit targets) point here while the option is on
+    int* goal0;                 // [B] the goal k_search_begin left, what sz_search_goals reports
+    int* prev;                  // [B][SZ_MAX_MOVES] the root children's N at the last snapshot
+    int* prev_total;            // [B] their sum; 0 at search begin
+    int* has_prev;              // [B] a snapshot was taken in this search
+    int* stopped_at;            // [B] the goal the board was stopped at, -1 = not stopped
+    int* checks;                // [B] checks evaluated in this search (a gain was formed)
+    double* last_gain;          // [B] the last of them, per new visit; NaN before the first
+    unsigned long long* stat;   // [B][3] boards stopped early, checks evaluated, simulations not made
+};
+
+// the goals of a search without visit targets, before k_search_begin reads them: the board's budget (sz_set_search_budgets), else num_searches
+__global__ void k_kld_goals(int* goal, const int* budget, int S, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) goal[b] = budget ? budget[b] : S;
+}
+
+// after k_search_begin: every board that starts a search, fresh or continued, starts with clean stop state, and its goal is kept
+__global__ void k_kld_begin(View v, KldStop ks) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= v.B || !(v.ctl[b].status & ST_SEARCHING)) return;
+    ks.goal0[b] = ks.goal[b];
+    ks.prev_total[b] = 0; ks.has_prev[b] = 0; ks.stopped_at[b] = -1; ks.checks[b] = 0;
+    ks.last_gain[b] = __longlong_as_double(0x7ff8000000000000LL);
+}
+
+// gain = sum over the K children of sz_kld_term in the project's fixed order: lane l adds term_l, term_{l+64}, ... ascending, then the xor
+// butterfly.  now(c): child c's count now.  The same sum in every lane (f64 addition commutes).
+template <typename NowF>
+__device__ __forceinline__ double wave_kld_gain(const int* prev, NowF now, int K, int prev_total, int new_total) {
+    double acc = 0.0;
+    for (int c = lane_id(); c < K; c += 64) acc = acc + sz_kld_term(prev[c], prev_total, now(c), new_total);
+    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off);
+    return uni_f64(acc);
+}
+__device__ __forceinline__ int wave_sum_int(int x) {
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+    return uni(x);
+}
+
+// the check (sz_search_check_stop): one wavefront per board.  vl: leaf batching is on, the board's leaves in flight are n_pend
+__global__ __launch_bounds__(64) void k_kld_check(View v, KldStop ks, int vl) {
+    const int b = blockIdx.x, lane = lane_id();
+    BoardPtrs bp = board_ptrs(v, b);
+    const int status = uni(bp.ctl->status);
+    if (!(status & ST_SEARCHING) || (status & (ST_DONE | ST_ERROR)) || uni(ks.stopped_at[b]) >= 0) return;
+    const EdgeMeta rm = bp.em[0];
+    int K = uni((int)rm.n);
+    const int first = uni(rm.first);
+    if (K <= 0 || first < 0) return;                                  // the root is not expanded yet
+    if (K > SZ_MAX_MOVES) K = SZ_MAX_MOVES;
+    const EdgeStat* ch = bp.es + first;
+    int* prev = ks.prev + (size_t)b * SZ_MAX_MOVES;
+    int part = 0;
+    for (int c = lane; c < K; c += 64) part += ch[c].N;               // counted visits only: no in-flight count
+    const int new_total = wave_sum_int(part), prev_total = uni(ks.prev_total[b]);
+    if (new_total < prev_total + ks.o.interval) return;
+    const int sims = uni(bp.ctl->sims_done);
+    bool stop = false;
+    if (uni(ks.has_prev[b]) && prev_total > 0) {
+        const double gain = wave_kld_gain(prev, [&](int c) { return ch[c].N; }, K, prev_total, new_total);
+        const double g = gain / (double)(new_total - prev_total);
+        stop = g < ks.o.min_gain && sims >= ks.o.min_simulations;
+        if (lane == 0) { ks.last_gain[b] = g; ks.checks[b] += 1; ks.stat[(size_t)b * 3 + 1] += 1; }
+    }
+    if (stop) {
+        // the goal becomes what is made and in flight: the next sz_search_step consumes the leaves in flight, starts no descent and sets ST_DONE
+        if (lane == 0) {
+            const int pending = vl ? bp.ctl->n_pend : ((status & ST_PENDING) ? 1 : 0);
+            const int s = sims + pending;
+            ks.stopped_at[b] = s; ks.goal[b] = s;
+            ks.stat[(size_t)b * 3] += 1; ks.stat[(size_t)b * 3 + 2] += (unsigned long long)(ks.goal0[b] - s);
+            if (!pending) bp.ctl->status = status | ST_DONE;
+        }
+        return;
+    }
+    for (int c = lane; c < K; c += 64) prev[c] = ch[c].N;
+    if (lane == 0) { ks.prev_total[b] = new_total; ks.has_prev[b] = 1; }
+}
+
+// test hook (sz_debug_kld_gain): wave_kld_gain, the function k_kld_check calls, on caller-supplied cases, one wavefront per case
+__global__ __launch_bounds__(64) void k_debug_kld_gain(const int* prev, const int* now, const int* n_child, double* gain_out) {
+    const int cs = blockIdx.x;
+    const int* p = prev + (size_t)cs * SZ_MAX_MOVES;
+    const int* q = now + (size_t)cs * SZ_MAX_MOVES;
+    int K = uni(n_child[cs]);
+    if (K < 0) K = 0;
+    if (K > SZ_MAX_MOVES) K = SZ_MAX_MOVES;
+    int pp = 0, pq = 0;
+    for (int c = lane_id(); c < K; c += 64) { pp += p[c]; pq += q[c]; }
+    const int prev_total = wave_sum_int(pp), new_total = wave_sum_int(pq);
+    const double gain = wave_kld_gain(p, [&](int c) { return q[c]; }, K, prev_total, new_total);
+    if (lane_id() == 0) gain_out[cs] = gain;
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
 // what sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel and sz_set_cpuct set for the next sz_search_begin, which takes it up whole: a search, its descent-only
@@ -1938,6 +2042,10 @@ struct sz_engine {
     EndOpts eo;                     // ... with these; its arrays are allocated by the first enabling call (eo.state != NULL from then on)
     int temp_on;                    // sz_set_move_temperature: sz_play runs the TEMPERATURE instantiations of k_play
     TempOpts to;                    // ... with these; its arrays are allocated by the first enabling call (to.stat != NULL from then on)
+    int budgets_set, targets_set;   // sz_set_search_budgets / sz_set_visit_targets hold an array: what goal_view points View::budget and bo at
+    int kld_on;                     // sz_set_kld_stop: View::budget points at d_goal, sz_search_begin fills it, sz_search_check_stop lowers it
+    KldStop ks;                     // ... with these; its arrays are allocated by the first enabling call (ks.stat != NULL from then on)
+    int search_open;                // a sz_search_begin was made and neither sz_play, sz_play_moves nor a sz_compact_searching that found no board followed
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
@@ -2168,10 +2276,11 @@ struct OptionState {
     bool endings, noise;            // sz_set_endings; sz_set_root_noise / sz_set_search_root_noise with a gamma
     bool temperature;               // sz_set_move_temperature
     bool cpuct;                     // sz_set_cpuct: what the next sz_search_begin takes up
+    bool kld;                       // sz_set_kld_stop
 };
 enum OptionSetter { BY_ANY, BY_LEAF_BATCHING, BY_SOLVER, BY_ROOT_NOISE };     // the setters whose own entry point accepts less than the engine runs
 static OptionState option_state(const sz_engine* e) {
-    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0, e->next.cpuct_on != 0};
+    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0, e->next.cpuct_on != 0, e->kld_on != 0};
 }
 static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter by = BY_ANY) {
     const bool reuse = e->v.reuse != 0;
@@ -2185,11 +2294,21 @@ static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter
     if (p.gumbel && p.noise) return SZ_ERR_STATE;                           // Gumbel is the root's exploration
     if (p.gumbel && p.temperature) return SZ_ERR_STATE;                     // ... and chooses its own move
     if (p.gumbel && p.cpuct) return SZ_ERR_STATE;                           // Gumbel's rule is a chain of its own: the combination is a follow-up
+    if (p.gumbel && p.kld) return SZ_ERR_STATE;                             // sequential halving plans on the goal: it cannot be lowered under it
     // sz_set_root_noise: a reused root was expanded as an inner node, on un-noised priors, and is never expanded again, so the noise would silently
     // apply to the first ply of a game only; and a reuse engine under sz_set_search_root_noise leaves that mode through that setter, which drops
     // the kept subtrees
     if (by == BY_ROOT_NOISE && reuse && (p.noise || e->v.root_gamma)) return SZ_ERR_STATE;
     return SZ_OK;
+}
+
+// Where the kernels read a board's simulations from.  Visit targets: k_search_begin turns d_target into d_goal and everything reads d_goal.
+// Budgets: d_budget.  Neither: num_searches (NULL).  sz_set_kld_stop: d_goal in every case, which sz_search_begin fills from the budgets or
+// num_searches where k_search_begin does not, so that a stop has a goal to lower.
+static void goal_view(sz_engine* e) {
+    e->bo.target = e->targets_set ? e->d_target : nullptr;
+    e->bo.goal = e->targets_set ? e->d_goal : nullptr;
+    e->v.budget = (e->targets_set || e->kld_on) ? e->d_goal : (e->budgets_set ? e->d_budget : nullptr);
 }
 
 int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream) {
@@ -2206,8 +2325,9 @@ int sz_set_search_budgets(sz_engine* e, const int32_t* budgets, void* stream) {
         HIPCHK(hipMemcpyAsync(e->d_budget, budgets, (size_t)e->v.B * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
     }
-    e->v.budget = budgets ? e->d_budget : nullptr;
-    e->bo.target = nullptr; e->bo.goal = nullptr;                             // budgets and visit targets exclude each other: the later setter wins
+    e->budgets_set = budgets != nullptr;
+    e->targets_set = 0;                                                       // budgets and visit targets exclude each other: the later setter wins
+    goal_view(e);
     return SZ_OK;
 }
 
@@ -2225,9 +2345,9 @@ int sz_set_visit_targets(sz_engine* e, const int32_t* targets, void* stream) {
         HIPCHK(hipStreamSynchronize(s));                                    // the caller's array may go out of scope
     }
     // k_search_begin writes each board's goal into d_goal; everything that reads a budget reads it from there
-    e->bo.target = targets ? e->d_target : nullptr;
-    e->bo.goal = targets ? e->d_goal : nullptr;
-    e->v.budget = targets ? e->d_goal : nullptr;
+    e->targets_set = targets != nullptr;
+    e->budgets_set = 0;
+    goal_view(e);
     return SZ_OK;
 }
 
@@ -2238,8 +2358,9 @@ int sz_search_goals(sz_engine* e, int32_t* goals, void* stream) {
     const size_t B = e->v.B;
     std::vector<Ctl> h(B);
     std::vector<int> bud(e->v.budget ? B : 0);                              // the goals (targets set), the budgets, or nothing: num_searches
+    const int* src = e->kld_on ? e->ks.goal0 : e->v.budget;                 // sz_set_kld_stop: the goals at begin, whatever a stop made of them
     HIPCHK(hipMemcpyAsync(h.data(), e->v.ctl, B * sizeof(Ctl), hipMemcpyDeviceToHost, s));
-    if (e->v.budget) HIPCHK(hipMemcpyAsync(bud.data(), e->v.budget, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (src) HIPCHK(hipMemcpyAsync(bud.data(), src, B * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     for (size_t b = 0; b < B; b++)
         goals[b] = (h[b].status & ST_SEARCHING) ? (e->v.budget ? bud[b] : e->v.S) : 0;
@@ -2274,7 +2395,7 @@ int sz_compact_searching(sz_engine* e, void* planes_dev, int32_t* n_live_out, vo
     int n = 0;
     HIPCHK(hipMemcpyAsync(&n, e->d_nlive, sizeof n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (n <= 0) return SZ_ERR_STATE;
+    if (n <= 0) { e->search_open = 0; return SZ_ERR_STATE; }
     int* t = e->d_slot; e->d_slot = e->d_slot_next; e->d_slot_next = t;
     e->v.slot = e->d_slot;
     if (n_live_out) *n_live_out = n;
@@ -2354,6 +2475,8 @@ int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     e->cur = e->next;                                                       // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel and sz_set_cpuct take effect here
+    if (e->kld_on && !e->targets_set)                                       // sz_set_kld_stop: the goals k_search_begin reads as budgets (under targets it writes them itself)
+        hipLaunchKernelGGL(k_kld_goals, dim3((e->v.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d_goal, e->budgets_set ? e->d_budget : nullptr, e->v.S, e->v.B);
     with_search_options(e, [&](auto vl, auto solve, auto... o) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         std::apply([&](auto... k) {
@@ -2361,6 +2484,11 @@ int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
         }, pick<ForcedOpts>(o...));                                         // the one option that acts where a root is made: the board's bit
     });
     HIPCHK(hipGetLastError());
+    if (e->kld_on) {                                                        // sz_set_kld_stop: clean stop state for the boards that search
+        hipLaunchKernelGGL(k_kld_begin, dim3((e->v.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->v, e->ks);
+        HIPCHK(hipGetLastError());
+    }
+    e->search_open = 1;
     if (e->v.reuse && planes_dev) {
         // boards that continue on a kept subtree have no root to evaluate: one descent-only launch selects their first leaf (boards whose fresh
         // root waits for the network sit it out), so that every board enters the first network call with a real position.  Batched
@@ -2539,6 +2667,67 @@ int sz_set_cpuct(sz_engine* e, const sz_cpuct_options* opt, void* stream) {
     e->next.cpuct = *opt; e->next.cpuct_on = 1;
     return SZ_OK;
 }
+
+int sz_set_kld_stop(sz_engine* e, const sz_kld_stop_options* opt, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (opt && (!std::isfinite(opt->min_gain) || !(opt->min_gain > 0.0) || opt->min_gain > 1.0 || opt->interval < 1 || opt->interval > e->v.S ||
+                opt->min_simulations < 0 || opt->min_simulations > e->v.S)) return SZ_ERR_INVALID;
+    OptionState p = option_state(e);
+    p.kld = opt != nullptr;
+    const int refused = option_refusal(e, p);
+    if (refused == SZ_ERR_INVALID) return refused;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = between_searches(e, s);
+    if (rc) return rc;
+    if (!opt) { e->kld_on = 0; goal_view(e); return SZ_OK; }
+    if (refused) return refused;                                            // Gumbel is on: SZ_ERR_STATE, after the question whether the engine searches
+    if (!e->ks.stat) {                                                      // the first enabling call: the per-board state and the counters
+        const size_t B = e->v.B;
+        KldStop k = e->ks;
+        if ((rc = dalloc(e, &k.goal0, B)) || (rc = dalloc(e, &k.prev, B * SZ_MAX_MOVES)) || (rc = dalloc(e, &k.prev_total, B)) || (rc = dalloc(e, &k.has_prev, B)) ||
+            (rc = dalloc(e, &k.stopped_at, B)) || (rc = dalloc(e, &k.checks, B)) || (rc = dalloc(e, &k.last_gain, B)) || (rc = dalloc(e, &k.stat, B * 3))) return rc;
+        HIPCHK(hipMemsetAsync(k.goal0, 0, B * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(k.prev, 0, B * SZ_MAX_MOVES * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(k.prev_total, 0, B * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(k.has_prev, 0, B * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(k.stopped_at, 0xff, B * sizeof(int), s));      // -1: no board was stopped
+        HIPCHK(hipMemsetAsync(k.checks, 0, B * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(k.last_gain, 0xff, B * sizeof(double), s));    // a NaN: no check was evaluated
+        HIPCHK(hipMemsetAsync(k.stat, 0, B * 3 * sizeof(unsigned long long), s));
+        HIPCHK(hipStreamSynchronize(s));
+        k.goal = e->d_goal;
+        e->ks = k;
+    }
+    e->ks.o = *opt; e->kld_on = 1;
+    goal_view(e);
+    return SZ_OK;
+}
+
+int sz_search_check_stop(sz_engine* e, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (!e->kld_on) return SZ_OK;                                           // off: a driver may call it unconditionally
+    if (!e->search_open) return SZ_ERR_STATE;
+    ENGINE_GUARD(e);
+    hipLaunchKernelGGL(k_kld_check, dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, e->ks, e->vb.L > 1 ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_fetch_kld_stop(sz_engine* e, int32_t* stopped_at, int32_t* checks, double* last_gain, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (!e->ks.stat) return SZ_ERR_STATE;                                   // the option was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = e->v.B;
+    if (stopped_at) HIPCHK(hipMemcpyAsync(stopped_at, e->ks.stopped_at, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (checks) HIPCHK(hipMemcpyAsync(checks, e->ks.checks, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (last_gain) HIPCHK(hipMemcpyAsync(last_gain, e->ks.last_gain, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SZ_OK;
+}
+
+int sz_kld_stop_stats(sz_engine* e, uint64_t out[3], void* stream) { return sum_board_counters(e, e ? e->ks.stat : nullptr, 3, out, stream); }
 
 int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
@@ -2770,6 +2959,7 @@ int sz_root_children(sz_engine* e, int32_t* action_dev, int32_t* visits_dev, int
 int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
+    e->search_open = 0;
     with_search_options(e, [&](auto, auto solve, auto... o) {
         auto launch = [&](auto... k) {
             hipLaunchKernelGGL((k_play<decltype(solve)::value, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, k...);
@@ -2785,6 +2975,7 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
 int sz_play_moves(sz_engine* e, const int32_t* actions_dev, void* stream) {
     if (!e || !actions_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
+    e->search_open = 0;
     hipLaunchKernelGGL(k_play_moves, dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, actions_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
@@ -2984,6 +3175,13 @@ int sz_debug_gumbel(const double* x_dev, double* slog_out_dev, double* sexp_out_
 int sz_debug_cpuct(const int32_t* n_p_dev, const uint8_t* is_root_dev, const sz_cpuct_options* opts_dev, float* c_out_dev, int32_t n_cases, void* stream) {
     if (!n_p_dev || !is_root_dev || !opts_dev || !c_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
     hipLaunchKernelGGL(k_debug_cpuct, dim3((n_cases + 63) / 64), dim3(64), 0, (hipStream_t)stream, n_p_dev, is_root_dev, opts_dev, c_out_dev, n_cases);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_kld_gain(const int32_t* prev_dev, const int32_t* now_dev, const int32_t* n_child_dev, double* gain_out_dev, int32_t n_cases, void* stream) {
+    if (!prev_dev || !now_dev || !n_child_dev || !gain_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_kld_gain, dim3(n_cases), dim3(64), 0, (hipStream_t)stream, prev_dev, now_dev, n_child_dev, gain_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

@@ -220,6 +220,41 @@ def cpuct_options_of(args):
     return tuple(out)
 
 
+KLD_STOP_KEYS = ("min_gain", "interval", "min_simulations")
+
+
+def kld_stop_options_of(args):
+    """The KLD-gain early stopping options of args, checked: (min_gain, interval, min_simulations), or None when the key is absent.
+    NON-REFERENCE, default off.
+
+    args["kld_stop"] = {"min_gain": 5e-6, "interval": 100, "min_simulations": 0} (lc0's minimum-kldgain-per-node and kldgain-average-interval;
+    the values are those of its training runs and the defaults here) lets a board's search stop before its goal (sz_set_kld_stop): whenever
+    the root's children gained `interval` visits since the last snapshot, the Kullback-Leibler divergence of the snapshot's visit distribution
+    from the one now, per new visit, is compared with min_gain, and below it the board makes no further simulation, provided it has made
+    min_simulations.  Obvious recaptures and forced replies then cost a fraction of num_searches, sharp positions all of it.  min_gain lies in
+    (0, 1], interval in 1..num_searches, min_simulations in 0..num_searches.  Budgets, visit targets and every other option work underneath;
+    refused with args["gumbel"], whose sequential halving plans on the goal.  Checked in this order: the dict and its keys, min_gain, interval,
+    min_simulations, the combinations.  Its effect on playing strength is unmeasured."""
+    opt = args.get("kld_stop")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(KLD_STOP_KEYS):
+        raise ValueError("args['kld_stop'] must be a dict with keys from %s, got %r" % (KLD_STOP_KEYS, opt))
+    g = opt.get("min_gain", 5e-6)
+    if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, float, np.integer, np.floating)) or not (math.isfinite(g) and 0.0 < g <= 1.0):   # NaN fails the comparison
+        raise ValueError("args['kld_stop']['min_gain'] must be a number in (0, 1], got %r" % (g,))
+    S = int(args["num_searches"])
+    out = [float(g)]
+    for key, default, lo in (("interval", min(100, max(S, 1)), 1), ("min_simulations", 0, 0)):
+        x = opt.get(key, default)
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not lo <= x <= S:
+            raise ValueError("args['kld_stop'][%r] must be an integer in %d..num_searches = %d, got %r" % (key, lo, S, x))
+        out.append(int(x))
+    if args.get("gumbel") is not None:
+        raise ValueError("args['kld_stop'] and args['gumbel'] exclude each other: sequential halving plans on the goal the stop would lower")
+    return tuple(out)
+
+
 GUMBEL_KEYS = ("m", "c_visit", "c_scale")
 
 
@@ -430,6 +465,8 @@ class SelfPlayEngine:
         self.fpu = fpu_options_of(self.args)
         # NON-REFERENCE option (default off): AlphaZero's visit-dependent exploration rate in C's place, see cpuct_options_of
         self.cpuct = cpuct_options_of(self.args)
+        # NON-REFERENCE option (default off): KLD-gain early stopping of a board's search, see kld_stop_options_of
+        self.kld_stop = kld_stop_options_of(self.args)
         # NON-REFERENCE option (default off): Gumbel root search with sequential halving and the completed-Q policy target, see gumbel_options_of
         self.gumbel = gumbel_options_of(self.args)
         self._gumbel_g = None         # the device copy of the Gumbel draws in force (set_gumbel)
@@ -494,6 +531,8 @@ class SelfPlayEngine:
             self.set_fpu(self.fpu)
         if self.cpuct is not None:
             self.set_cpuct(self.cpuct)
+        if self.kld_stop is not None:
+            self.set_kld_stop(self.kld_stop)
         if self.gumbel is not None:    # g = None (a deterministic search) until set_gumbel hands over draws
             self.set_gumbel(self.gumbel)
         if self.gumbel_tree:
@@ -627,6 +666,33 @@ class SelfPlayEngine:
         o = None if opts is None else N.sz_cpuct_options(*[float(x) for x in opts])
         N.check(N.lib().sz_set_cpuct(self._e, None if o is None else C.byref(o), self._stream()), "sz_set_cpuct")
         self.cpuct = None if opts is None else tuple(float(x) for x in opts)
+
+    def set_kld_stop(self, opts):
+        """KLD-gain early stopping (sz_set_kld_stop, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (min_gain, interval,
+        min_simulations) as kld_stop_options_of returns it, or None = off.  Between searches only; kept subtrees are not touched; refused
+        while the Gumbel search is on."""
+        o = None if opts is None else N.sz_kld_stop_options(float(opts[0]), int(opts[1]), int(opts[2]))
+        N.check(N.lib().sz_set_kld_stop(self._e, None if o is None else C.byref(o), self._stream()), "sz_set_kld_stop")
+        self.kld_stop = None if opts is None else (float(opts[0]), int(opts[1]), int(opts[2]))
+
+    def check_stop(self):
+        """One check of every searching board against the stopping rule (sz_search_check_stop: one launch, no synchronisation); a no-op
+        while the option is off.  A stopped board takes the leaves it has in flight through one more step() and is done."""
+        N.check(N.lib().sz_search_check_stop(self._e, self._stream()), "sz_search_check_stop")
+
+    def fetch_kld_stop(self):
+        """sz_fetch_kld_stop: dict of [B] arrays of each board's last search: stopped_at (the simulations it was stopped at, -1: not stopped),
+        checks (checks that formed a gain) and last_gain (the last of them, per new visit; NaN: none)"""
+        out = dict(stopped_at=np.zeros(self.B, np.int32), checks=np.zeros(self.B, np.int32), last_gain=np.zeros(self.B, np.float64))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        N.check(N.lib().sz_fetch_kld_stop(self._e, p(out["stopped_at"]), p(out["checks"]), p(out["last_gain"]), self._stream()), "sz_fetch_kld_stop")
+        return out
+
+    def kld_stop_stats(self):
+        """(boards stopped early, checks evaluated, simulations not made), all boards, cumulative (sz_kld_stop_stats)"""
+        out = (C.c_uint64 * 3)()
+        N.check(N.lib().sz_kld_stop_stats(self._e, out, self._stream()), "sz_kld_stop_stats")
+        return tuple(int(x) for x in out)
 
     def set_gumbel(self, opts, g=None):
         """Gumbel root search (sz_set_gumbel, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (m, c_visit, c_scale) as
@@ -827,7 +893,10 @@ class SelfPlayEngine:
         the batch shrinks to the boards that still search; with max_shrinks > 0 it is also shrunk once right after the roots were made:
         boards with budget 0 and terminal roots never take a row.  Without budgets there is one segment and no shrink.
         args["visit_targets"]: the segments are planned from search_goals(), read after begin(); a board whose kept root already holds its
-        target is done at begin and never takes a row."""
+        target is done at begin and never takes a row.
+        args["kld_stop"]: the steps run in chunks of ceil(interval / leaves_per_step); after a chunk comes check_stop(), then the first step
+        of the next chunk, which takes in what the stopped boards had in flight, then the batch shrinks to the boards that still search (one
+        stream synchronisation per check) and the search ends when there is none.  Segment ends shrink where they did."""
         ev = evaluator or self.evaluate
         self.begin()
         self.last_steps = self.last_rows = 0
@@ -841,8 +910,30 @@ class SelfPlayEngine:
         segs = search_segments(budgets, self.L, self.max_shrinks, self.S)
         if budgets is not None and self.max_shrinks > 0 and self._compact_searching() == 0:
             return                                          # nothing to search: every board was done at begin
+        if self.kld_stop is not None:
+            return self._search_checked(ev, segs)
         for i, n in enumerate(segs):
             self._run_steps(ev, n)
+            if i + 1 < len(segs) and self._compact_searching() == 0:
+                return
+        self._run_pending(ev)
+
+    def _search_checked(self, ev, segs):
+        """search()'s segments under args["kld_stop"]"""
+        chunk = -(-self.kld_stop[1] // self.L)
+        since, drain = 0, False                             # steps since the last check; a check was issued and its boards' leaves are still in flight
+        for i, n in enumerate(segs):
+            while n > 0:
+                k = 1 if drain else min(n, chunk - since)
+                self._run_steps(ev, k)
+                n, since = n - k, since + k
+                if drain:
+                    drain = False
+                    if self._compact_searching() == 0:
+                        return
+                if since == chunk:
+                    self.check_stop()
+                    since, drain = 0, True
             if i + 1 < len(segs) and self._compact_searching() == 0:
                 return
         self._run_pending(ev)

@@ -118,6 +118,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     (sz_set_fpu), one setting for the root and one below it, on fast and full plies alike; the engine applies it.  Strength effect unmeasured.
     args["cpuct"] = {...} (NON-REFERENCE, selfplay.cpuct_options_of): AlphaZero's visit-dependent exploration rate in the place of the constant
     C (sz_set_cpuct), one triple for the root and one below it, on fast and full plies alike; the engine applies it.  Strength effect unmeasured.
+    args["kld_stop"] = {...} (NON-REFERENCE, selfplay.kld_stop_options_of): KLD-gain early stopping (sz_set_kld_stop), on fast and full plies
+    alike: SelfPlayEngine.search checks every board's root every `interval` visits and a board whose visit distribution has stopped moving makes
+    no further simulation; stats['sims'] stay the goals the searches began with (kld_stop_stats() has what was not made).  Strength effect unmeasured.
     args["gumbel"] = {"m": m, "c_visit": x, "c_scale": y} (NON-REFERENCE, selfplay.gumbel_options_of): the Gumbel root search (sz_set_gumbel), on fast
     and full plies alike.  The move is the search's own choice (`uniforms` is still drawn as always and not read by the engine) and a sample's
     'actions' dict holds the completed-Q improved policy as Python floats instead of visit fractions.  With `learning` the Gumbel(0,1) draws

@@ -462,7 +462,7 @@ def write_step_log(path, epoch, hist, lr_scheduler, append=True):
 
 def selfplay_args_of(a):
     """the self-play `args` dict of main()'s parsed flags `a`; nothing is checked here: the engine's option readers (selfplay.search_options_of,
-    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, temperature_options_of, cpuct_options_of, sim.playout_cap_of) refuse what does not go together"""
+    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, temperature_options_of, cpuct_options_of, kld_stop_options_of, sim.playout_cap_of) refuse what does not go together"""
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
@@ -500,6 +500,9 @@ def selfplay_args_of(a):
                                        ("root_base", a.cpuct_root_base), ("root_factor", a.cpuct_root_factor)) if val is not None}
     if cpuct:
         args["cpuct"] = cpuct
+    kld = {key: val for key, val in (("min_gain", a.kld_min_gain), ("interval", a.kld_interval), ("min_simulations", a.kld_min_simulations)) if val is not None}
+    if kld:
+        args["kld_stop"] = kld
     return args
 
 
@@ -594,6 +597,12 @@ def flag_parser():
     ap.add_argument("--cpuct-root-init", type=float, default=None, metavar="C", help="C where a child of the root is selected and in policy-target pruning (default --cpuct-init)")
     ap.add_argument("--cpuct-root-base", type=float, default=None, metavar="B", help="B at the root (default --cpuct-base)")
     ap.add_argument("--cpuct-root-factor", type=float, default=None, metavar="F", help="F at the root (default --cpuct-factor)")
+    ap.add_argument("--kld-min-gain", type=float, default=None, metavar="G",
+                    help="KLD-gain early stopping: a board's search stops when the Kullback-Leibler gain of its root's visit distribution per new visit falls below G "
+                         "(args['kld_stop'], sz_set_kld_stop; lc0's minimum-kldgain-per-node, 5e-6 in its training runs, the default); any of the three kld flags "
+                         "switches the option on; not combined with --gumbel; strength effect unmeasured")
+    ap.add_argument("--kld-interval", type=int, default=None, metavar="N", help="visits between two checks of --kld-min-gain, in 1..--searches (lc0's kldgain-average-interval; default 100)")
+    ap.add_argument("--kld-min-simulations", type=int, default=None, metavar="N", help="no board stops before its search has made N simulations (default 0)")
     return ap
 
 
@@ -667,7 +676,7 @@ def main(argv=None):
                                         "endings": args.get("endings"), "ending_report": ending_report(games) if args.get("endings") else None,
                                         "temperature": args.get("temperature"), "tempered_plays": sp_stats.get("tempered_plays"),
                                         "greedy_plays": sp_stats.get("greedy_plays"), "excluded_children": sp_stats.get("excluded_children"),
-                                        "cpuct": args.get("cpuct"),
+                                        "cpuct": args.get("cpuct"), "kld_stop": args.get("kld_stop"),
                                         "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"
