@@ -826,6 +826,56 @@ int sz_kld_stop_stats(sz_engine* e, uint64_t out[3], void* stream);
  * entries; gain_out[i] = the summed gain, before the division by the new visits.  All device pointers. */
 int sz_debug_kld_gain(const int32_t* prev_dev, const int32_t* now_dev, const int32_t* n_child_dev, double* gain_out_dev, int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, default off: the search summary.  Every other option changes where a simulation goes, when a search stops or which move
+ * is played; this one changes nothing and records what a finished search hands to a trainer beside the visit counts: the search's own value of
+ * the root (lc0 trains its value head on (1 - q_ratio) * z + q_ratio * q) and how far the policy target lies from the prior the search started
+ * from (KataGo's policy surprise weighting).  While it is on sz_play launches two more kernels on the caller's stream, k_summary_pre before
+ * k_play (the tree is intact: k_play compacts it in place under reuse_subtree) and k_summary_post after it (the ply's record exists: the pruned
+ * counts of a forced-playouts board exist nowhere else).  k_play, k_search_begin, k_search_step and k_play_moves run unchanged, on or off.
+ * One wavefront per board.  All arithmetic is f64, every operator one IEEE rounding (-ffp-contract=off); slog is sz_set_gumbel's
+ * (csrc/sz_gumbel.h), the term o * slog(o / n) is csrc/sz_kldgain.h's sz_kld_term, the scalar functions are csrc/sz_summary.h's, plain C++ for
+ * host and device.
+ *   wsum(term): sz_set_gumbel_tree's fixed-order sum: lane l adds the terms c = l, l + 64, l + 128, l + 192 ascending from 0.0, then the xor
+ *               butterfly with offsets 32, 16, .., 1 (acc = acc + other); the result is read through readfirstlane.
+ * Before k_play, for a board that plays in this sz_play (it searches, is done, has no error, its game is not over: k_play's early return,
+ * restated) and passes k_play's zero-visit check (K > 0 and total > 0; otherwise k_play sets SZ_ERR_ZERO_VISITS):
+ *   K = the root's child count; for the children in the tree's order N_c (counted visits, no in-flight count), W_c (f64, stored from the
+ *   child's side to move), P_c (f32, the stored prior the search used: the noised one where root noise is on)
+ *   total  = the sum of N_c, in integer arithmetic
+ *   root_q = -(wsum(N_c >= 1 ? W_c : 0.0) / (double)total)      the mover's expected outcome over the whole search, in [-1, 1]
+ *   best_q = -(W_c* / (double)N_c*), c* the first maximum of N_c: the m of sz_set_endings, bit for bit
+ *   valid = 1, surprise = NaN, and the K priors are kept for the second kernel
+ * Any other board: valid = 0, root_q = best_q = surprise = NaN.
+ * After k_play, for a board with valid = 1, on the record k_play just wrote (sz_fetch_ply's; its child order is the tree root's, see
+ * csrc/sz_summary.h; an ending that fires still writes it):
+ *   n_c = visits[c] for c < n_child: the pruned counts on a forced-playouts board, the policy target as trained on
+ *   rtotal = the sum of n_c, in integer arithmetic;  rtotal == 0: surprise = NaN
+ *   t_c = (double)n_c / (double)rtotal;  term_c = n_c > 0 ? t_c * slog(t_c / (double)P_c) : 0.0;  surprise = wsum(term_c)
+ *   a P_c that is not a normal positive finite f32 (expansion stores none): term_c = 0.0 and the term is counted, see the stats
+ * The priors are read as the tree stores them.  Where they sum to 1 (learning off, or Dirichlet root noise: sz_set_root_noise /
+ * sz_set_search_root_noise) surprise is KL(target || prior) up to rounding: >= 0 but for a few ulp of the largest term, and exactly 0.0 at
+ * K = 1 with P_0 = 1.  Under the reference's learning noise every stored prior is 0.75 p + 0.25 * noise_value with noise_value near 1: they
+ * sum to more than 1 and the same sum can be negative; it is reported as it is.
+ * Composes with budgets, visit targets, reuse_subtree, leaf batching, the solver, forced playouts, sz_set_fpu, sz_set_cpuct, root noise, the move
+ * temperature, sz_set_kld_stop, sz_set_endings, sz_compact and sz_compact_searching.  sz_play_moves makes no summary and leaves the last one as
+ * it is.  sz_set_gumbel's record is pi' and it exports v_mix itself: the two refuse each other, see the setter.
+ * Held bit for bit to the host restatement tests/summaryref.py by tests/test_gpu_search_summary.py.  Its effect on training is unmeasured. */
+/* enable != 0 switches the option on, 0 off; takes effect at the next sz_play.  SZ_ERR_STATE: a call during a search (the rule of
+ * sz_set_search_budgets; nothing is changed then); switching on while Gumbel is on for the next search, and sz_set_gumbel(opt != NULL) refuses
+ * with SZ_ERR_STATE while this option is on.  The setter never touches a tree.  The first enabling call allocates the per-board arrays. */
+int sz_set_search_summary(sz_engine* e, int32_t enable, void* stream);
+/* host arrays [n_boards], each may be NULL: the summary of each board's last sz_play made with the option on (valid = 0 and NaNs: the board
+ * did not play then, or no sz_play was made yet).  Synchronises the stream.  SZ_ERR_STATE when the option was never on. */
+int sz_fetch_search_summary(sz_engine* e, double* root_q, double* best_q, double* surprise, uint8_t* valid, void* stream);
+/* out[0] = summaries made, out[1] = surprise terms dropped by the rule on P_c above, all boards, cumulative; zeros when never on */
+int sz_search_summary_stats(sz_engine* e, uint64_t out[2], void* stream);
+/* test: the DEVICE functions the two kernels call (wave_summary_values, wave_summary_surprise) on caller-supplied cases, one wavefront per case:
+ * tree_vc / record_vc are [n_cases][SZ_MAX_MOVES] int32, value_sum [n_cases][SZ_MAX_MOVES] f64, prior [n_cases][SZ_MAX_MOVES] f32, n_child[i] in
+ * 0..SZ_MAX_MOVES the children of case i.  out3[i] = root_q, best_q (NaN both when n_child[i] == 0 or the tree counts sum to 0), surprise (NaN
+ * when the record counts sum to 0).  All device pointers. */
+int sz_debug_search_summary(const int32_t* n_child_dev, const int32_t* tree_vc_dev, const double* value_sum_dev, const float* prior_dev, const int32_t* record_vc_dev,
+                            double* out3_dev, int32_t n_cases, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

@@ -114,6 +114,10 @@ EXPORTS = {
     "sz_fetch_kld_stop": (C.c_int, [C.c_void_p] * 5),
     "sz_kld_stop_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "sz_debug_kld_gain": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
+    "sz_set_search_summary": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "sz_fetch_search_summary": (C.c_int, [C.c_void_p] * 6),
+    "sz_search_summary_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_debug_search_summary": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_set_visit_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

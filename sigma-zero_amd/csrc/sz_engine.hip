@@ -37,6 +37,7 @@
 #include "sz_gumbel.h"
 #include "sz_cpuct.h"
 #include "sz_kldgain.h"
+#include "sz_summary.h"
 #include "../../include/sigmazero.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -2001,6 +2002,118 @@ __global__ __launch_bounds__(64) void k_debug_kld_gain(const int* prev, const in
 }
 
 // ------------------------------------------------------------------------------------------------
+// NON-REFERENCE option (sz_set_search_summary; include/sigmazero.h is the rule, sz_summary.h the scalar arithmetic, the child order and the
+// logarithm's precondition): what a finished search hands to the trainer beside the visit counts.  Two kernels of their own around k_play, one
+// wavefront per board; k_play, k_search_begin, k_search_step and k_play_moves have no variant and no new argument.
+// ------------------------------------------------------------------------------------------------
+struct SummaryOpts {
+    double* root_q;             // [B] the mover's expected outcome over the whole search; NaN on a board that did not play
+    double* best_q;             // [B] ... over the most visited child's visits: sz_set_endings' m
+    double* surprise;           // [B] KL(record's visit fractions || stored priors); NaN on a board that did not play or whose record holds no visit
+    uint8_t* valid;             // [B] the board played in the last sz_play and the three values above are its summary
+    float* prior;               // [B][SZ_MAX_MOVES] the root children's stored priors, copied by k_summary_pre for k_summary_post
+    unsigned long long* stat;   // [B][2] summaries made, terms dropped by the precondition rule
+};
+
+// root_q and best_q of the K children with counts N(c) and value sums W(c), lanes = children.  false (nothing written): no child or no visit,
+// k_play's SZ_ERR_ZERO_VISITS.  Every lane returns the same.
+template <typename NF, typename WF>
+__device__ __forceinline__ bool wave_summary_values(NF N, WF W, int K, double* root_q, double* best_q) {
+    const int lane = lane_id();
+    int part = 0, bn = -1, bi = 0x7fffffff;
+    double acc = 0.0;
+    for (int c = lane; c < K; c += 64) {
+        const int nc = N(c);
+        part += nc;
+        if (nc > bn) { bn = nc; bi = c; }
+        acc = acc + sz_summary_value_term(nc, W(c));
+    }
+    for (int off = 32; off >= 1; off >>= 1) {                              // the first maximum of N_c, wave_ending's butterfly
+        const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
+        if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+    }
+    const int total = wave_sum_int(part);
+    if (K <= 0 || total == 0) return false;
+    *root_q = sz_summary_root_q(wave_sum_f64(acc), total);
+    bi = uni(bi);
+    *best_q = sz_summary_best_q(uni_f64(W(bi)), uni(N(bi)));
+    return true;
+}
+
+// the surprise of the K children with record counts n(c) against the priors P(c); NaN when the record holds no visit.  *dropped: the terms
+// the precondition rule left out.  Every lane returns the same.
+template <typename RF, typename PF>
+__device__ __forceinline__ double wave_summary_surprise(RF n, PF P, int K, int* dropped) {
+    const int lane = lane_id();
+    int part = 0;
+    for (int c = lane; c < K; c += 64) part += n(c);
+    const int rtotal = wave_sum_int(part);
+    *dropped = 0;
+    if (rtotal == 0) return sz_summary_nan();
+    double acc = 0.0;
+    int drop = 0;
+    for (int c = lane; c < K; c += 64) acc = acc + sz_summary_term(n(c), rtotal, P(c), &drop);
+    *dropped = wave_sum_int(drop);
+    return wave_sum_f64(acc);
+}
+
+// before k_play, while the tree is intact: the two values and the priors of every board that will play.  The conditions are k_play's early
+// return and its zero-visit check, restated.
+__global__ __launch_bounds__(64) void k_summary_pre(View v, SummaryOpts so) {
+    const int b = blockIdx.x, lane = lane_id();
+    BoardPtrs bp = board_ptrs(v, b);
+    const int status = uni(bp.ctl->status);
+    double rq = sz_summary_nan(), bq = sz_summary_nan();
+    bool ok = (status & ST_SEARCHING) && (status & ST_DONE) && !(status & (ST_ERROR | ST_GAMEOVER));
+    if (ok) {
+        const EdgeMeta rm = bp.em[0];
+        int K = uni((int)rm.n);
+        const int first = uni(rm.first);
+        if (K > SZ_MAX_MOVES) K = SZ_MAX_MOVES;
+        ok = K > 0 && first >= 0;
+        if (ok) {
+            const EdgeStat* ch = bp.es + first;
+            ok = wave_summary_values([&](int c) { return ch[c].N; }, [&](int c) { return ch[c].W; }, K, &rq, &bq);
+            if (ok) for (int c = lane; c < K; c += 64) so.prior[(size_t)b * SZ_MAX_MOVES + c] = ch[c].P;
+        }
+    }
+    if (lane == 0) { so.valid[b] = ok ? 1 : 0; so.root_q[b] = rq; so.best_q[b] = bq; so.surprise[b] = sz_summary_nan(); }
+}
+
+// after k_play: the surprise of every board k_summary_pre marked, on the record k_play just wrote (the pruned counts on a forced board)
+__global__ __launch_bounds__(64) void k_summary_post(View v, SummaryOpts so) {
+    const int b = blockIdx.x;
+    if (!uni((int)so.valid[b])) return;
+    int K = uni(v.rec_nchild[b]);
+    if (K < 0) K = 0;
+    if (K > SZ_MAX_MOVES) K = SZ_MAX_MOVES;
+    const int* rv = v.rec_visits + (size_t)b * SZ_MAX_CHILDREN;
+    const float* pr = so.prior + (size_t)b * SZ_MAX_MOVES;
+    int dropped;
+    const double s = wave_summary_surprise([&](int c) { return rv[c]; }, [&](int c) { return pr[c]; }, K, &dropped);
+    if (lane_id() == 0) { so.surprise[b] = s; so.stat[(size_t)b * 2] += 1; so.stat[(size_t)b * 2 + 1] += (unsigned long long)dropped; }
+}
+
+// test hook (sz_debug_search_summary): wave_summary_values and wave_summary_surprise, the functions the two kernels call, on caller-supplied
+// cases, one wavefront per case.  out3[cs] = root_q, best_q (NaN both without a child or a visit), surprise.
+__global__ __launch_bounds__(64) void k_debug_search_summary(const int* n_child, const int* tree_vc, const double* value_sum, const float* prior, const int* record_vc,
+                                                             double* out3) {
+    const int cs = blockIdx.x;
+    const int* tn = tree_vc + (size_t)cs * SZ_MAX_MOVES;
+    const double* tw = value_sum + (size_t)cs * SZ_MAX_MOVES;
+    const float* pr = prior + (size_t)cs * SZ_MAX_MOVES;
+    const int* rv = record_vc + (size_t)cs * SZ_MAX_MOVES;
+    int K = uni(n_child[cs]);
+    if (K < 0) K = 0;
+    if (K > SZ_MAX_MOVES) K = SZ_MAX_MOVES;
+    double rq = sz_summary_nan(), bq = sz_summary_nan();
+    wave_summary_values([&](int c) { return tn[c]; }, [&](int c) { return tw[c]; }, K, &rq, &bq);
+    int dropped;
+    const double s = wave_summary_surprise([&](int c) { return rv[c]; }, [&](int c) { return pr[c]; }, K, &dropped);
+    if (lane_id() == 0) { out3[(size_t)cs * 3] = rq; out3[(size_t)cs * 3 + 1] = bq; out3[(size_t)cs * 3 + 2] = s; }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
 // what sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel and sz_set_cpuct set for the next sz_search_begin, which takes it up whole: a search, its descent-only
@@ -2046,6 +2159,8 @@ struct sz_engine {
     int kld_on;                     // sz_set_kld_stop: View::budget points at d_goal, sz_search_begin fills it, sz_search_check_stop lowers it
     KldStop ks;                     // ... with these; its arrays are allocated by the first enabling call (ks.stat != NULL from then on)
     int search_open;                // a sz_search_begin was made and neither sz_play, sz_play_moves nor a sz_compact_searching that found no board followed
+    int sum_on;                     // sz_set_search_summary: sz_play launches k_summary_pre before k_play and k_summary_post after it
+    SummaryOpts so;                 // ... with these; its arrays are allocated by the first enabling call (so.stat != NULL from then on)
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
@@ -2277,10 +2392,11 @@ struct OptionState {
     bool temperature;               // sz_set_move_temperature
     bool cpuct;                     // sz_set_cpuct: what the next sz_search_begin takes up
     bool kld;                       // sz_set_kld_stop
+    bool summary;                   // sz_set_search_summary
 };
 enum OptionSetter { BY_ANY, BY_LEAF_BATCHING, BY_SOLVER, BY_ROOT_NOISE };     // the setters whose own entry point accepts less than the engine runs
 static OptionState option_state(const sz_engine* e) {
-    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0, e->next.cpuct_on != 0, e->kld_on != 0};
+    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0, e->next.cpuct_on != 0, e->kld_on != 0, e->sum_on != 0};
 }
 static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter by = BY_ANY) {
     const bool reuse = e->v.reuse != 0;
@@ -2295,6 +2411,7 @@ static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter
     if (p.gumbel && p.temperature) return SZ_ERR_STATE;                     // ... and chooses its own move
     if (p.gumbel && p.cpuct) return SZ_ERR_STATE;                           // Gumbel's rule is a chain of its own: the combination is a follow-up
     if (p.gumbel && p.kld) return SZ_ERR_STATE;                             // sequential halving plans on the goal: it cannot be lowered under it
+    if (p.gumbel && p.summary) return SZ_ERR_STATE;                         // Gumbel's record is pi' and it exports v_mix itself: the combination is a follow-up
     // sz_set_root_noise: a reused root was expanded as an inner node, on un-noised priors, and is never expanded again, so the noise would silently
     // apply to the first ply of a game only; and a reuse engine under sz_set_search_root_noise leaves that mode through that setter, which drops
     // the kept subtrees
@@ -2729,6 +2846,52 @@ int sz_fetch_kld_stop(sz_engine* e, int32_t* stopped_at, int32_t* checks, double
 
 int sz_kld_stop_stats(sz_engine* e, uint64_t out[3], void* stream) { return sum_board_counters(e, e ? e->ks.stat : nullptr, 3, out, stream); }
 
+int sz_set_search_summary(sz_engine* e, int32_t enable, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    OptionState p = option_state(e);
+    p.summary = enable != 0;
+    const int refused = option_refusal(e, p);
+    if (refused == SZ_ERR_INVALID) return refused;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = between_searches(e, s);
+    if (rc) return rc;
+    if (!enable) { e->sum_on = 0; return SZ_OK; }
+    if (refused) return refused;                                            // Gumbel is on: SZ_ERR_STATE, after the question whether the engine searches
+    if (!e->so.stat) {                                                      // the first enabling call: the per-board outputs, the prior copy and the counters
+        const size_t B = e->v.B;
+        SummaryOpts o = e->so;
+        if ((rc = dalloc(e, &o.root_q, B)) || (rc = dalloc(e, &o.best_q, B)) || (rc = dalloc(e, &o.surprise, B)) || (rc = dalloc(e, &o.valid, B)) ||
+            (rc = dalloc(e, &o.prior, B * SZ_MAX_MOVES)) || (rc = dalloc(e, &o.stat, B * 2))) return rc;
+        HIPCHK(hipMemsetAsync(o.root_q, 0xff, B * sizeof(double), s));       // NaNs: no summary was made
+        HIPCHK(hipMemsetAsync(o.best_q, 0xff, B * sizeof(double), s));
+        HIPCHK(hipMemsetAsync(o.surprise, 0xff, B * sizeof(double), s));
+        HIPCHK(hipMemsetAsync(o.valid, 0, B, s));
+        HIPCHK(hipMemsetAsync(o.prior, 0, B * SZ_MAX_MOVES * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(o.stat, 0, B * 2 * sizeof(unsigned long long), s));
+        HIPCHK(hipStreamSynchronize(s));
+        e->so = o;
+    }
+    e->sum_on = 1;
+    return SZ_OK;
+}
+
+int sz_fetch_search_summary(sz_engine* e, double* root_q, double* best_q, double* surprise, uint8_t* valid, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (!e->so.stat) return SZ_ERR_STATE;                                   // the option was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = e->v.B;
+    if (root_q) HIPCHK(hipMemcpyAsync(root_q, e->so.root_q, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (best_q) HIPCHK(hipMemcpyAsync(best_q, e->so.best_q, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (surprise) HIPCHK(hipMemcpyAsync(surprise, e->so.surprise, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (valid) HIPCHK(hipMemcpyAsync(valid, e->so.valid, B, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SZ_OK;
+}
+
+int sz_search_summary_stats(sz_engine* e, uint64_t out[2], void* stream) { return sum_board_counters(e, e ? e->so.stat : nullptr, 2, out, stream); }
+
 int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     if (opt) {
@@ -2960,6 +3123,8 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
     if (!e || !uniforms_dev) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
     e->search_open = 0;
+    if (e->sum_on)                                                          // sz_set_search_summary: while the tree is intact
+        hipLaunchKernelGGL(k_summary_pre, dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, e->so);
     with_search_options(e, [&](auto, auto solve, auto... o) {
         auto launch = [&](auto... k) {
             hipLaunchKernelGGL((k_play<decltype(solve)::value, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, k...);
@@ -2968,6 +3133,8 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
         if constexpr (has_opt<ForcedOpts, decltype(o)...>) std::apply(launch, pick<ForcedOpts, GumbelOpts, PuctOpts, TempOpts, EndOpts>(play_opt(o)...));
         else std::apply(launch, pick<ForcedOpts, GumbelOpts, TempOpts, EndOpts>(play_opt(o)...));
     });
+    if (e->sum_on)                                                          // ... and when the ply's record exists
+        hipLaunchKernelGGL(k_summary_post, dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, e->so);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }
@@ -3182,6 +3349,14 @@ int sz_debug_cpuct(const int32_t* n_p_dev, const uint8_t* is_root_dev, const sz_
 int sz_debug_kld_gain(const int32_t* prev_dev, const int32_t* now_dev, const int32_t* n_child_dev, double* gain_out_dev, int32_t n_cases, void* stream) {
     if (!prev_dev || !now_dev || !n_child_dev || !gain_out_dev || n_cases <= 0) return SZ_ERR_INVALID;
     hipLaunchKernelGGL(k_debug_kld_gain, dim3(n_cases), dim3(64), 0, (hipStream_t)stream, prev_dev, now_dev, n_child_dev, gain_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_search_summary(const int32_t* n_child_dev, const int32_t* tree_vc_dev, const double* value_sum_dev, const float* prior_dev, const int32_t* record_vc_dev,
+                            double* out3_dev, int32_t n_cases, void* stream) {
+    if (!n_child_dev || !tree_vc_dev || !value_sum_dev || !prior_dev || !record_vc_dev || !out3_dev || n_cases <= 0) return SZ_ERR_INVALID;
+    hipLaunchKernelGGL(k_debug_search_summary, dim3(n_cases), dim3(64), 0, (hipStream_t)stream, n_child_dev, tree_vc_dev, value_sum_dev, prior_dev, record_vc_dev, out3_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

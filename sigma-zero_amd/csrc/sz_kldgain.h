@@ -14,3 +14,7 @@ SZG_FN double sz_kld_term(int prev_c, int prev_total, int now_c, int new_total) 
     const double n = (double)now_c / (double)new_total;
     return o * sz_slog(o / n);
 }
+
+// the same term on two probabilities formed by the caller (the search summary's policy surprise, sz_summary.h): o * ln(o / n).  o / n must be
+// a positive normal f64; the caller sees to it.
+SZG_FN double sz_kld_term(double o, double n) { return o * sz_slog(o / n); }

@@ -255,6 +255,46 @@ def kld_stop_options_of(args):
     return tuple(out)
 
 
+SEARCH_TARGET_KEYS = ("q_ratio", "q_source", "surprise_fraction")
+Q_SOURCES = ("root", "best")
+
+
+def search_targets_of(args):
+    """The training-target options of args, checked: (q_ratio, q_source, surprise_fraction), or None when the key is absent.  NON-REFERENCE,
+    default off.
+
+    args["search_targets"] = {"q_ratio": r, "q_source": "root" | "best", "surprise_fraction": f} switches the engine's search summary on
+    (sz_set_search_summary) and tells play_games and train_rl what to do with it.  q_ratio in [0, 1] (default 0): a sample's value target
+    becomes (1 - r) * z + r * q, z the game's result and q the search's own value of the position from the mover's side (lc0's q_ratio);
+    q_source "root" (default) takes the mover's expected outcome over all of the root's visits, "best" over the most visited child's (the m of
+    args["endings"]).  surprise_fraction in [0, 1] (default 0): the share of training effort handed out in proportion to each sample's policy
+    surprise KL(target || prior) (KataGo's policy surprise weighting; train_rl.surprise_weights / resample_by_weight).  The key alone, with
+    both at 0, records search_values and surprises and changes no target.  The surprise reads the priors the search used: a divergence >= 0
+    where those sum to 1 (learning off, or args["root_dirichlet_alpha"]); under the reference's learning noise (0.75 p + 0.25 * a constant near 1
+    on every child) they do not, the figure can be negative and surprise_weights counts it as 0: set root_dirichlet_alpha beside it.
+    The search itself is untouched.  Refused with args["gumbel"], whose record is the improved policy and which exports v_mix itself.  Checked in this order: the dict and its keys, q_ratio, q_source,
+    surprise_fraction, the combination.  Its effect on training is unmeasured."""
+    opt = args.get("search_targets")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(SEARCH_TARGET_KEYS):
+        raise ValueError("args['search_targets'] must be a dict with keys from %s, got %r" % (SEARCH_TARGET_KEYS, opt))
+    def unit(key):
+        x = opt.get(key, 0.0)
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not 0.0 <= x <= 1.0:       # NaN fails the comparison
+            raise ValueError("args['search_targets'][%r] must be a number in [0, 1], got %r" % (key, x))
+        return float(x)
+
+    q_ratio = unit("q_ratio")
+    src = opt.get("q_source", "root")
+    if not isinstance(src, str) or src not in Q_SOURCES:
+        raise ValueError("args['search_targets']['q_source'] must be one of %s, got %r" % (Q_SOURCES, src))
+    fraction = unit("surprise_fraction")
+    if args.get("gumbel") is not None:
+        raise ValueError("args['search_targets'] and args['gumbel'] exclude each other: Gumbel's record is its improved policy and it exports v_mix itself")
+    return q_ratio, src, fraction
+
+
 GUMBEL_KEYS = ("m", "c_visit", "c_scale")
 
 
@@ -467,6 +507,9 @@ class SelfPlayEngine:
         self.cpuct = cpuct_options_of(self.args)
         # NON-REFERENCE option (default off): KLD-gain early stopping of a board's search, see kld_stop_options_of
         self.kld_stop = kld_stop_options_of(self.args)
+        # NON-REFERENCE option (default off): the search summary and what training does with it, see search_targets_of
+        self.search_targets = search_targets_of(self.args)
+        self.search_summary = False   # sz_set_search_summary is on (set_search_summary)
         # NON-REFERENCE option (default off): Gumbel root search with sequential halving and the completed-Q policy target, see gumbel_options_of
         self.gumbel = gumbel_options_of(self.args)
         self._gumbel_g = None         # the device copy of the Gumbel draws in force (set_gumbel)
@@ -533,6 +576,8 @@ class SelfPlayEngine:
             self.set_cpuct(self.cpuct)
         if self.kld_stop is not None:
             self.set_kld_stop(self.kld_stop)
+        if self.search_targets is not None:
+            self.set_search_summary(True)
         if self.gumbel is not None:    # g = None (a deterministic search) until set_gumbel hands over draws
             self.set_gumbel(self.gumbel)
         if self.gumbel_tree:
@@ -693,6 +738,31 @@ class SelfPlayEngine:
         out = (C.c_uint64 * 3)()
         N.check(N.lib().sz_kld_stop_stats(self._e, out, self._stream()), "sz_kld_stop_stats")
         return tuple(int(x) for x in out)
+
+    def set_search_summary(self, on):
+        """The search summary (sz_set_search_summary, a NON-REFERENCE option) from the next play() on, until changed: every play() also records
+        each playing board's root_q, best_q and policy surprise.  Between searches only; no tree is touched; refused while the Gumbel search
+        is on."""
+        N.check(N.lib().sz_set_search_summary(self._e, int(bool(on)), self._stream()), "sz_set_search_summary")
+        self.search_summary = bool(on)
+
+    def fetch_search_summary(self):
+        """sz_fetch_search_summary: dict of [B] arrays of the last play() made with the summary on: root_q (the mover's expected outcome over
+        all of the root's visits), best_q (over the most visited child's), surprise (KL(record's visit fractions || the priors the search
+        used)) and valid (0: the board did not play, the three are NaN)"""
+        B = self.B
+        out = dict(root_q=np.zeros(B, np.float64), best_q=np.zeros(B, np.float64), surprise=np.zeros(B, np.float64), valid=np.zeros(B, np.uint8))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        N.check(N.lib().sz_fetch_search_summary(self._e, p(out["root_q"]), p(out["best_q"]), p(out["surprise"]), p(out["valid"]), self._stream()),
+                "sz_fetch_search_summary")
+        return out
+
+    def search_summary_stats(self):
+        """(summaries made, surprise terms dropped because the stored prior was no normal positive f32), all boards, cumulative
+        (sz_search_summary_stats)"""
+        out = (C.c_uint64 * 2)()
+        N.check(N.lib().sz_search_summary_stats(self._e, out, self._stream()), "sz_search_summary_stats")
+        return int(out[0]), int(out[1])
 
     def set_gumbel(self, opts, g=None):
         """Gumbel root search (sz_set_gumbel, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (m, c_visit, c_scale) as

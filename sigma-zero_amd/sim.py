@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, gumbel_tree_of, temperature_options_of, temperature_at, ENDING_KINDS
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, gumbel_tree_of, temperature_options_of, temperature_at, search_targets_of, ENDING_KINDS
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -121,6 +121,11 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     args["kld_stop"] = {...} (NON-REFERENCE, selfplay.kld_stop_options_of): KLD-gain early stopping (sz_set_kld_stop), on fast and full plies
     alike: SelfPlayEngine.search checks every board's root every `interval` visits and a board whose visit distribution has stopped moving makes
     no further simulation; stats['sims'] stay the goals the searches began with (kld_stop_stats() has what was not made).  Strength effect unmeasured.
+    args["search_targets"] = {...} (NON-REFERENCE, selfplay.search_targets_of): the search summary (sz_set_search_summary) is fetched after every
+    play(); a game gets 'search_values' (the search's own value of each sampled position from the mover's side, root_q or best_q by q_source),
+    'surprises' (its policy surprise KL(target || prior)) and 'value_targets' ((1 - q_ratio) * reward + q_ratio * search value, Python floats),
+    all aligned with 'states'.  'rewards', 'actions' and the moves played are what they are without
+    the key; train_rl takes the blended targets and the surprise weights from there.  Effect on training unmeasured.
     args["gumbel"] = {"m": m, "c_visit": x, "c_scale": y} (NON-REFERENCE, selfplay.gumbel_options_of): the Gumbel root search (sz_set_gumbel), on fast
     and full plies alike.  The move is the search's own choice (`uniforms` is still drawn as always and not read by the engine) and a sample's
     'actions' dict holds the completed-Q improved policy as Python floats instead of visit fractions.  With `learning` the Gumbel(0,1) draws
@@ -153,6 +158,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     gumbel_tree_of(args)
     if gumbel_noise is not None and gum is None:
         raise ValueError("gumbel_noise needs args['gumbel']")
+    targets = search_targets_of(args)
     temp_opts = temperature_options_of(args)
     if temperature is not None and temp_opts is None:
         raise ValueError("temperature needs args['temperature']")
@@ -182,6 +188,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     S = int(args["num_searches"])
     eng = SelfPlayEngine(model, args, B, chess960=c960, learning=learning, planes_dtype=planes_dtype, device=dev)
     games = [dict(states=[], actions=[], rewards=[], colours=[], result=None, packed_states=[], sample_plies=[], chosen_actions=[], termination=None, holdout=False, would_end=None) for _ in range(n_games)]   # packed_states: the (119,8) uint8 form (train_RL.py:42)
+    if targets is not None:
+        for g_ in games:
+            g_.update(search_values=[], surprises=[], value_targets=[])
     cap_rng = np.random.default_rng() if pcap is not None and full_search is None else None
     holdout_rng = np.random.default_rng() if end_opts is not None and holdout is None else None
     gumbel_rng = np.random.default_rng() if gum is not None and gumbel_noise is None and learning else None
@@ -214,7 +223,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
                 eng.set_endings(end_opts, slot_holdout)    # the new games' holdout flags; streaks and marks of the games that go on stay
         eng.set_active((slot_game >= 0).astype(np.uint8))
 
-    def absorb(rec, game_of_slot, sampled, ply_of_slot, improved=None):
+    def absorb(rec, game_of_slot, sampled, ply_of_slot, improved=None, summary=None):
         """host-side bookkeeping of one ply's records (sim.py:71-73); runs while the GPU searches the next ply"""
         slots = np.nonzero((game_of_slot >= 0) & rec["active"].astype(bool))[0]
         for s_ in slots.tolist():                          # the move played, sample or not: chosen_actions has one action index per ply of the game
@@ -241,6 +250,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
                 games[g]["actions"].append(dict(zip(moves, (vis / int(vis.sum())).tolist())))      # int / int in float64: the reference's v / sum_values
             games[g]["colours"].append(white)
             games[g]["sample_plies"].append(int(ply_of_slot[s_]))
+            if summary is not None:                        # args["search_targets"]: the search's own value and the policy surprise of this sample
+                games[g]["search_values"].append(float(summary["best_q" if targets[1] == "best" else "root_q"][s_]))
+                games[g]["surprises"].append(float(summary["surprise"][s_]))
             if rec["game_over"][s_]:
                 games[g]["result"] = {1: "1-0", -1: "0-1", 0: "1/2-1/2"}[int(rec["result"][s_])]
 
@@ -303,11 +315,12 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         rec = eng.fetch_ply()
         ends = eng.fetch_endings() if end_opts is not None else None
         improved = eng.fetch_gumbel()["policy"] if gum is not None else None
+        summary = eng.fetch_search_summary() if targets is not None else None
         if eng.stats()["boards_error"]:
             eng.check_errors()
         t0 = lap("play_fetch", t0)
         ply_of_slot = np.where(slot_game >= 0, plies[np.maximum(slot_game, 0)], -1)
-        pending = (rec, slot_game.copy(), sampled, ply_of_slot, improved)
+        pending = (rec, slot_game.copy(), sampled, ply_of_slot, improved, summary)
         n_full = int(sampled[running].sum())
         if vt:                                             # the goals actually made: a kept root's visits count towards its target
             work["sims"] += int(eng.last_goals[running].sum()) if eng.last_goals is not None else 0
@@ -333,6 +346,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     for g in range(n_games):
         reward = {"1-0": 1, "0-1": -1}.get(games[g]["result"], 0)
         games[g]["rewards"] = [reward if ply % 2 == 0 else -reward for ply in games[g]["sample_plies"]]   # sim.py:94-97: the sign alternates with the ply the sample was taken at
+        if targets is not None:                            # lc0's q_ratio blend in Python float64; every sampled ply played, so it has a value
+            r_ = targets[0]
+            games[g]["value_targets"] = [(1.0 - r_) * z + r_ * q for z, q in zip(games[g]["rewards"], games[g]["search_values"])]
     if forced_k is not None:
         work["forced_selections"], work["pruned_visits"] = eng.forced_stats()
     if end_opts is not None:

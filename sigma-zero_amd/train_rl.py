@@ -84,18 +84,70 @@ class DeviceBatches:
             yield {"states": states, "actions": target, "rewards": self.rewards[sel]}
 
 
-def records_from_games(games):
-    """sim.play_games() output -> arrays for SelfPlayDataset (states re-packed to the (119,8) uint8 format)."""
+def records_from_games(games, value_key="rewards"):
+    """sim.play_games() output -> arrays for SelfPlayDataset (states re-packed to the (119,8) uint8 format).  value_key: the per-sample list
+    the value targets come from: "rewards" (the game's result, the reference's) or "value_targets" (args["search_targets"]: the result blended
+    with the search's own value)."""
     from .chess_tensor import action_index
     packed, aidx, aprob, rew = [], [], [], []
     w = (1 << np.arange(8)).astype(np.uint8)
     for g in games:
         pre = g.get("packed_states")                       # play_games() keeps the engine's own bit-packed record next to the bool tensor
-        for i, (st, act, r, col) in enumerate(zip(g["states"], g["actions"], g["rewards"], g["colours"])):
+        for i, (st, act, r, col) in enumerate(zip(g["states"], g["actions"], g[value_key], g["colours"])):
             packed.append(pre[i] if pre else (st.numpy().astype(np.uint8) * w).sum(-1).astype(np.uint8))
             aidx.append(np.array([action_index(m, col) for m in act], dtype=np.int64))
             aprob.append(np.array(list(act.values()), dtype=np.float64))
             rew.append(r)
+    return packed, aidx, aprob, rew
+
+
+def surprise_weights(surprises, fraction):
+    """KataGo's policy surprise weighting: w_i = (1 - f) + f * N * s_i / sum(s), f = fraction in [0, 1], s_i the samples' policy surprises
+    KL(target || prior) (play_games' 'surprises').  A share f of the N units of training effort goes out in proportion to the surprise, the
+    rest evenly; the weights sum to N.  A NaN surprise counts as 0, and so does one a rounding left below 0; all ones when sum(s) == 0."""
+    import math
+    f = float(fraction)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError("surprise_weights: fraction must lie in [0, 1], got %r" % (fraction,))
+    s = [0.0 if (x != x or x < 0.0) else float(x) for x in surprises]
+    total = math.fsum(s)
+    if total == 0.0:
+        return [1.0] * len(s)
+    n = float(len(s))
+    return [(1.0 - f) + f * n * x / total for x in s]
+
+
+def resample_by_weight(n, weights, generator):
+    """KataGo's frequency weighting: the indices of records 0..n-1 with record i repeated floor(w_i) times plus once more with probability
+    frac(w_i).  One generator.random() per record, in record order, whatever its weight, so the same generator state gives the same list;
+    with weights that sum to n the expected length is n.  generator: a numpy Generator (or anything with random() -> [0, 1))."""
+    import math
+    if len(weights) != n:
+        raise ValueError("resample_by_weight: %d weights for %d records" % (len(weights), n))
+    out = []
+    for i in range(n):
+        w = float(weights[i])
+        if not (w >= 0.0 and math.isfinite(w)):
+            raise ValueError("resample_by_weight: weight %d is %r" % (i, weights[i]))
+        k = int(math.floor(w))
+        k += bool(generator.random() < w - k)
+        out.extend([i] * k)
+    return out
+
+
+def training_records(games, targets=None, generator=None):
+    """What run_cycle trains on: records_from_games(games), under targets = selfplay.search_targets_of(args) (None: the reference's records).
+    q_ratio > 0 takes play_games' blended 'value_targets' as the value targets; surprise_fraction > 0 resamples the records by
+    surprise_weights over the games' 'surprises', which play_games keeps in the order records_from_games walks (game by game, sample by
+    sample), through resample_by_weight with `generator` (a numpy Generator; default a fresh one).  -> (packed, aidx, aprob, rew)"""
+    q_ratio, _, fraction = targets if targets is not None else (0.0, "root", 0.0)
+    packed, aidx, aprob, rew = records_from_games(games, value_key="value_targets" if q_ratio > 0.0 else "rewards")
+    if fraction > 0.0:
+        surprises = [s for g in games for s in g["surprises"]]
+        if len(surprises) != len(rew):
+            raise ValueError("training_records: %d surprises for %d records" % (len(surprises), len(rew)))
+        keep = resample_by_weight(len(rew), surprise_weights(surprises, fraction), generator if generator is not None else np.random.default_rng())
+        packed, aidx, aprob, rew = ([x[i] for i in keep] for x in (packed, aidx, aprob, rew))
     return packed, aidx, aprob, rew
 
 
@@ -370,7 +422,7 @@ def load_cycle(model, optimiser, cycle, out_dir="saves", device=None):
 
 
 def run_cycle(model, optimiser, lr_scheduler, args, n_games, chess960=True, sync=None, batch_size=128, total_steps=6, fast_inference=True, train_convs="split", train_graph=False,
-              selfplay_stats=None):
+              selfplay_stats=None, resample_generator=None):
     """One epoch of train_RL.main (:205-264) on this rank: self-play n_games on this GPU, then 7 passes of training.
     fast_inference — the self-play network, fastest first (measured on MI355X at 4096 boards x 800 searches; fidelity = the same 64 positions
     searched with the fp32 module, tests/test_gpu_train_and_precision.py):
@@ -380,8 +432,13 @@ def run_cycle(model, optimiser, lr_scheduler, args, n_games, chess960=True, sync
                       clock): 0.95x, 64 of 64 boards with the fp32 network's exact visit counts at 100 and at 800 searches;
       "split"         SplitPolicyNet (hi + lo bf16 operands, 3 MFMAs per product): the reference's precision class by construction (logits
                       within 6e-6 of fp64, fp32 itself is at 4e-7), 0.40x; reproduces the reference's own CPU game ply for ply;
-      False / "fp32"  the torch module itself (MIOpen), 0.04x."""
+      False / "fp32"  the torch module itself (MIOpen), 0.04x.
+    args["search_targets"] (selfplay.search_targets_of): with q_ratio > 0 the value targets are play_games' blended 'value_targets'; with
+    surprise_fraction > 0 the records are resampled by surprise_weights through resample_by_weight, drawing from resample_generator (a numpy
+    Generator; default a fresh one)."""
     from .sim import play_games
+    from .selfplay import search_targets_of
+    targets = search_targets_of(args)
     from .fastnet import FastPolicyNet, SplitPolicyNet
     device = next(model.parameters()).device
     model.eval()
@@ -396,7 +453,7 @@ def run_cycle(model, optimiser, lr_scheduler, args, n_games, chess960=True, sync
     else:
         raise ValueError("fast_inference: %r" % (fast_inference,))
     games = play_games(player, args, n_games, c960=chess960, max_plies=args.get("max_plies", 100000), stats=selfplay_stats)
-    packed, aidx, aprob, rew = records_from_games(games)
+    packed, aidx, aprob, rew = training_records(games, targets, resample_generator)
     dl = DeviceBatches(packed, aidx, aprob, rew, batch_size=batch_size, device=device, shuffle=True)       # same batches as DataLoader + collate
     return train(model, dl, optimiser, total_steps=total_steps, lr_scheduler=lr_scheduler, sync=sync, device=device,
                  split_convs=None if train_convs == "split" else False, graph=train_graph), games
@@ -462,7 +519,7 @@ def write_step_log(path, epoch, hist, lr_scheduler, append=True):
 
 def selfplay_args_of(a):
     """the self-play `args` dict of main()'s parsed flags `a`; nothing is checked here: the engine's option readers (selfplay.search_options_of,
-    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, temperature_options_of, cpuct_options_of, kld_stop_options_of, sim.playout_cap_of) refuse what does not go together"""
+    visit_target_options_of, forced_playout_options_of, gumbel_options_of, gumbel_tree_of, ending_options_of, temperature_options_of, cpuct_options_of, kld_stop_options_of, search_targets_of, sim.playout_cap_of) refuse what does not go together"""
     args = {"C": 2, "num_searches": a.searches, "max_plies": a.max_plies}
     if a.leaves_per_step != 1:
         args.update(leaves_per_step=a.leaves_per_step, virtual_loss=a.virtual_loss)
@@ -503,6 +560,9 @@ def selfplay_args_of(a):
     kld = {key: val for key, val in (("min_gain", a.kld_min_gain), ("interval", a.kld_interval), ("min_simulations", a.kld_min_simulations)) if val is not None}
     if kld:
         args["kld_stop"] = kld
+    st = {key: val for key, val in (("q_ratio", a.q_ratio), ("q_source", a.q_source), ("surprise_fraction", a.surprise_fraction)) if val is not None}
+    if st:
+        args["search_targets"] = st
     return args
 
 
@@ -603,6 +663,13 @@ def flag_parser():
                          "switches the option on; not combined with --gumbel; strength effect unmeasured")
     ap.add_argument("--kld-interval", type=int, default=None, metavar="N", help="visits between two checks of --kld-min-gain, in 1..--searches (lc0's kldgain-average-interval; default 100)")
     ap.add_argument("--kld-min-simulations", type=int, default=None, metavar="N", help="no board stops before its search has made N simulations (default 0)")
+    ap.add_argument("--q-ratio", type=float, default=None, metavar="R",
+                    help="value target = (1 - R) * game result + R * the search's own value of the position, R in [0, 1] (args['search_targets'], "
+                         "sz_set_search_summary; lc0's q_ratio); any of the three flags switches the search summary on; not combined with --gumbel; "
+                         "effect on training unmeasured")
+    ap.add_argument("--q-source", choices=("root", "best"), default=None, help="the search value --q-ratio blends in: the mover's expected outcome over all root visits (root, the default) or over the most visited child's (best)")
+    ap.add_argument("--surprise-fraction", type=float, default=None, metavar="F",
+                    help="KataGo's policy surprise weighting: the share F in [0, 1] of training samples handed out in proportion to KL(policy target || prior)")
     return ap
 
 
@@ -676,7 +743,7 @@ def main(argv=None):
                                         "endings": args.get("endings"), "ending_report": ending_report(games) if args.get("endings") else None,
                                         "temperature": args.get("temperature"), "tempered_plays": sp_stats.get("tempered_plays"),
                                         "greedy_plays": sp_stats.get("greedy_plays"), "excluded_children": sp_stats.get("excluded_children"),
-                                        "cpuct": args.get("cpuct"), "kld_stop": args.get("kld_stop"),
+                                        "cpuct": args.get("cpuct"), "kld_stop": args.get("kld_stop"), "search_targets": args.get("search_targets"),
                                         "searches_without_network": sp_stats.get("searches_without_network")}) + "\n")
             last = hist[-1] if hist else (float("nan"), float("nan"))
             print("epoch %d: %d ranks x %d games, %d samples on rank 0, %d optimiser steps, last mse %.4f ce %.4f"
