@@ -876,6 +876,73 @@ int sz_search_summary_stats(sz_engine* e, uint64_t out[2], void* stream);
 int sz_debug_search_summary(const int32_t* n_child_dev, const int32_t* tree_vc_dev, const double* value_sum_dev, const float* prior_dev, const int32_t* record_vc_dev,
                             double* out3_dev, int32_t n_cases, void* stream);
 
+/* NON-REFERENCE option, default off: the spread of the values backed up through every edge, and lower-confidence-bound (LCB) move selection on
+ * it (KataGo's useLcbForSelection, lcbStdevs = 5.0, minVisitPropForLCB = 0.15).  Every other option leaves what the tree knows about an edge at
+ * W, N, P; with this one on the tree also keeps Q, the sum of the squares of the values W sums, and where sz_play would play "the most visited
+ * move" it plays, among the well-visited root moves, the one whose mean value is best after z standard errors are taken off.
+ * All arithmetic is f64, every operator one IEEE rounding (-ffp-contract=off); ssqrt and the scalar functions are csrc/sz_lcb.h's, plain C++
+ * for host and device (ssqrt: a square root from + - * / and bit operations; ssqrt(0.0) = 0.0; an argument that is neither 0.0 nor a positive
+ * normal number counts as 0.0 and is counted, see the stats).
+ * The second moment.  Q is one f64 per edge, [n_boards][edges], allocated by the first enabling call (8 bytes per edge beside the tree's 32).
+ * It is written by the searches begun with the option on, at these sites and nowhere else, in the order W is written:
+ *   Q[e] = 0.0            where an edge is created: the root edge of a fresh root (sz_search_begin), the children at expansion (sz_search_step)
+ *   Q[e] = Q[e] + sv * sv wherever sv is added to W[e] in a backup, sv = +v or -v by the level's parity, v the (double) of the network's f32
+ *                         value or a terminal / proven -1, 0, +1: the evaluated leaf (under leaf batching every pending leaf, in leaf order), a
+ *                         visited terminal, a new terminal, the solver's proven stop (a proven root counts the rest of its budget out this
+ *                         way, one simulation at a time).  The product is exact, the sum one rounding.
+ *   Q[0] = (tv * tv) * (double)S   the terminal root, whose budget S is counted out at once beside W[0] = tv * (double)S
+ * The move choice, in sz_play, for a board that passes its early return and zero-visit check, after the ending decision (an ending that fires
+ * makes no choice) and after policy-target pruning.  The root's children c = 0..K-1 in action order; n_c the counts the move choice reads
+ * (pruned on a forced-playouts board); N_c, W_c, Q_c the tree's, never pruned; c* the first maximum of n_c; z = (double)stdevs,
+ * p = (double)min_visit_prop.  For a child with N_c >= 2:
+ *   m_c   = -(W_c / (double)N_c)                                       the mover's value, sz_set_endings' convention
+ *   s_c   = Q_c / (double)N_c - m_c * m_c;  if (!(s_c > 0.0)) s_c = 0.0
+ *   r_c   = z * ssqrt(s_c / (double)(N_c - 1))                          z standard errors of the mean, with the unbiased variance
+ *   lcb_c = m_c - r_c
+ * and lcb_c = NaN for a child with N_c < 2.  Child c is a candidate iff N_c >= 2 && n_c >= 1 && (double)n_c >= p * (double)n_c*.  The rule's
+ * move is the first maximum of lcb_c over the candidates (lanes = children; each lane keeps its first strict maximum over c, c + 64, ..; the
+ * wave64 xor butterfly keeps the larger value and the lower index on a tie, as in selection); without a candidate it is c*.
+ * Where it applies: exactly where sz_play would play the most visited move: a negative uniform without sz_set_move_temperature, the greedy kind
+ * of that option with it (u < 0, T not above 0, or no count above minus the offset).  A sampled play is chosen as without the option, and on
+ * a root proven WIN the proving move is played as without it.  With select == 0 the option observes: the move is always the one without the
+ * option, while Q, the outputs and the counters are produced all the same.
+ * Not combined with reuse_subtree (the kept subtree's Q would have to be compacted with it) nor with sz_set_gumbel: follow-ups, see the setter.
+ * Composes with budgets, leaf batching, the solver, forced playouts, sz_set_fpu, sz_set_cpuct,
+ * root noise, the move temperature, sz_set_kld_stop, sz_set_endings, the search summary, sz_compact and sz_compact_searching.
+ * Held bit for bit to the host restatement tests/lcbref.py by tests/test_gpu_lcb.py.  Its effect on playing strength is unmeasured. */
+typedef struct sz_lcb_options {
+    float stdevs;                 /* z >= 0, finite; KataGo: 5.0 */
+    float min_visit_prop;         /* p in [0, 1]; KataGo: 0.15 */
+    int32_t select;               /* != 0: the rule's move is played where it applies; 0: observe only */
+} sz_lcb_options;                 /* 12 bytes */
+/* opt == NULL switches the option off.  Takes effect at the next sz_search_begin, whole: a search, its steps and its sz_play run with what its
+ * sz_search_begin saw, and a sz_play after a search that was begun without the option plays as without it.  SZ_ERR_INVALID: stdevs not finite
+ * or negative, min_visit_prop outside [0, 1] or NaN.  SZ_ERR_STATE: a call during a search (nothing is changed then); switching on on a
+ * reuse_subtree engine; switching on while Gumbel is on for the next search, and sz_set_gumbel(opt != NULL) refuses with SZ_ERR_STATE while this
+ * option is on for the next search.  The setter never touches a tree.  The first enabling call allocates Q and the per-board arrays. */
+int sz_set_lcb(sz_engine* e, const sz_lcb_options* opt, void* stream);
+/* host arrays [n_boards], each may be NULL: what the rule found at each board's last sz_play made under the option.  move: the rule's move as a
+ * child index; cstar: c*; lcb_move / lcb_cstar: their bounds (NaN where the child has N < 2); n_candidates; decided: 1 when the rule decided
+ * the move played (it applied and select != 0).  A board that made no choice then (it did not play, an ending fired, zero visits), or before
+ * any such sz_play: -1, -1, NaN, NaN, 0, 0.  Synchronises the stream.  SZ_ERR_STATE when the option was never on. */
+int sz_fetch_lcb(sz_engine* e, int32_t* move, int32_t* cstar, double* lcb_move, double* lcb_cstar, int32_t* n_candidates, uint8_t* decided, void* stream);
+/* out[0] = plays the rule decided, out[1] = plays at which the rule's move differs from c* (decided or not: sampled plays and select == 0
+ * count), out[2] = ssqrt arguments treated as 0.0 (expect 0), all boards, cumulative; zeros when never on */
+int sz_lcb_stats(sz_engine* e, uint64_t out[3], void* stream);
+/* the root children's Q_c of every board, device f64 [n_boards][SZ_MAX_MOVES] in sz_root_children's order, 0.0 beyond the children; on the
+ * caller's stream, not synchronised.  SZ_ERR_STATE unless the search begun last ran with the option. */
+int sz_root_value_spread(sz_engine* e, double* sq_sum_dev, void* stream);
+/* test: every edge's Q of one board in sz_debug_tree's order (host array, may be NULL for the count alone).  SZ_ERR_STATE as above. */
+int sz_debug_tree_spread(sz_engine* e, int32_t board, int32_t max_nodes, double* sq_sum, int32_t* n_out, void* stream);
+/* test: the DEVICE functions of the option on caller-supplied data.  Two parts, each skipped when its first array is NULL.  ssqrt_out[i] =
+ * ssqrt(x[i]) for i < n_x, x_bad_out[i] (optional) = 1 where the argument was treated as 0.0.  wave_lcb, the function k_play calls, one
+ * wavefront per case: case i has the children offsets[i] .. offsets[i + 1] - 1 (1..SZ_MAX_MOVES of them) of the flat arrays vc (n_c), tree_vc
+ * (N_c), value_sum (W_c), sq_sum (Q_c) and the options opts[i]; move_out / cstar_out / n_candidates_out / bad_out [n_cases], lcb_out flat like
+ * the inputs: every child's lcb_c.  All device pointers. */
+int sz_debug_lcb(const double* x_dev, double* ssqrt_out_dev, int32_t* x_bad_out_dev, int32_t n_x, const int32_t* offsets_dev, const int32_t* vc_dev,
+                 const int32_t* tree_vc_dev, const double* value_sum_dev, const double* sq_sum_dev, const sz_lcb_options* opts_dev, int32_t* move_out_dev,
+                 int32_t* cstar_out_dev, int32_t* n_candidates_out_dev, int32_t* bad_out_dev, double* lcb_out_dev, int32_t n_cases, void* stream);
+
 /* diagnostic only: with a device buffer of n_boards*8 uint64, sz_search_step records s_memtime at its phase boundaries per board
  * (0 start, 1 after expand+backprop, 2 after select, 3 after move/movegen/repetition/terminal, 4 after encode); NULL = off (default) */
 int sz_debug_step_stamps(sz_engine* e, void* dev_buffer);

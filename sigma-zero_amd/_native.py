@@ -56,6 +56,10 @@ class sz_kld_stop_options(C.Structure):
     _fields_ = [("min_gain", C.c_double), ("interval", C.c_int32), ("min_simulations", C.c_int32)]
 
 
+class sz_lcb_options(C.Structure):
+    _fields_ = [("stdevs", C.c_float), ("min_visit_prop", C.c_float), ("select", C.c_int32)]
+
+
 class sz_stats(C.Structure):
     _fields_ = [("simulations", C.c_uint64), ("expansions", C.c_uint64), ("terminal_hits", C.c_uint64), ("sum_depth", C.c_uint64),
                 ("sum_children", C.c_uint64), ("max_edges_used", C.c_uint64), ("boards_pending", C.c_int32),
@@ -118,6 +122,12 @@ EXPORTS = {
     "sz_fetch_search_summary": (C.c_int, [C.c_void_p] * 6),
     "sz_search_summary_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "sz_debug_search_summary": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
+    "sz_set_lcb": (C.c_int, [C.c_void_p, C.POINTER(sz_lcb_options), C.c_void_p]),
+    "sz_fetch_lcb": (C.c_int, [C.c_void_p] * 8),
+    "sz_lcb_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "sz_root_value_spread": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sz_debug_tree_spread": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "sz_debug_lcb": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 11 + [C.c_int32, C.c_void_p]),
     "sz_set_search_budgets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_compact_searching": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "sz_set_visit_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

@@ -108,6 +108,8 @@ def play_options_match(model, args_a, args_b, n_pairs, chess960=True, scharnagl=
     A side whose args have "temperature" (selfplay.temperature_options_of) samples every move with uniforms of default_rng(seed) at the
     temperature its schedule gives for the GAME's ply (opening included; a final temperature of 0 plays the most visited move); sample_plies
     must be 0 then (ValueError otherwise): the two are the same control.
+    A side whose args have "lcb" (selfplay.lcb_options_of) plays its greedy moves by the lower-confidence bound, through its engine: no rule
+    of the arena's own.
 
     One ply: each engine has exactly the boards active where its side is to move (set_active + compact), searches them, plays, and hands
     the chosen moves to the other engine by play_moves (sz_play_moves), which re-roots that engine's kept subtree on a reuse_subtree

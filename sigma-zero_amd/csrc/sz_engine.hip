@@ -38,6 +38,7 @@
 #include "sz_cpuct.h"
 #include "sz_kldgain.h"
 #include "sz_summary.h"
+#include "sz_lcb.h"
 #include "../../include/sigmazero.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -255,6 +256,30 @@ struct TempOpts {
     unsigned long long* stat;   // [B][3] plays sampled by the rule, greedy plays under the option, visited children excluded
 };
 enum { TEMP_SAMPLED = 0, TEMP_GREEDY = 1, TEMP_PROVEN = 2 };                                  // how wave_temperature came to its move
+
+// NON-REFERENCE option (sz_set_lcb; include/sigmazero.h is the rule, sz_lcb.h the scalar arithmetic): the second moment of every edge and
+// lower-confidence-bound move selection.  Two structs, each the last member of its pack.  SpreadOpts is what the instantiations of
+// k_search_begin and k_search_step that keep the second moment take on top of everything else: k_search_begin<VL, SOLVE, [ForcedOpts,] SpreadOpts>,
+// k_search_step<VL, SOLVE, [ForcedOpts,] [FpuOpts,] [PuctOpts,] SpreadOpts>.  Q is written at these sites and nowhere else:
+//   zeroed    the root edge of a fresh root (k_search_begin); the children at expansion (k_search_step, beside s.W = 0.0; s.N = 0)
+//   Q += sv^2 wave_backprop, every caller: the network leaf (every pending leaf under leaf batching, in leaf order), the solver's proven stop (a
+//             proven root counts its budget out through it, one simulation at a time), the visited terminal, the new terminal
+//   counted   the terminal root in k_search_begin: Q = (tv * tv) * (double)S beside W = tv * (double)S
+// LcbOpts is what k_play's instantiations take after every other option: k_play<SOLVE, [ForcedOpts,] [PuctOpts,] [TempOpts,] [EndOpts,] LcbOpts>.
+// Never beside GumbelOpts / GumbelTreeOpts, never on a reuse_subtree engine (wave_keep_subtree does not compact Q).
+struct SpreadOpts {
+    double* Q;                  // [B][e_cap] the sum of the squares of the values backed up through each edge, edge-indexed like Batch::vk
+};
+struct LcbOpts {
+    sz_lcb_options o;
+    const double* Q;            // SpreadOpts::Q
+    int* move;                  // [B] the rule's move (child index) of the last sz_play, -1 for a board that made no choice ...
+    int* cstar;                 // [B] ... the first maximum of the counts the move choice reads (-1 likewise) ...
+    double* lcb2;               // [B][2] ... their two bounds (NaN likewise, and where the child has N < 2) ...
+    int* ncand;                 // [B] ... the number of candidates (0 likewise) ...
+    uint8_t* decided;           // [B] ... and whether the rule decided the move played (0 likewise)
+    unsigned long long* stat;   // [B][3] plays the rule decided, plays where its move differs from c*, ssqrt arguments treated as 0.0
+};
 
 // forced playouts at a root (sz_set_forced_playouts): child c with n_c = N_c + k_c >= 1 visits is forced while n_c < sqrt((k * P_c) * T) in f64,
 // T = parentVC - 1.  Returns the forced child with the lowest index, -1 when none is forced: the arg-max decides as everywhere.  Lanes = children
@@ -637,6 +662,48 @@ __device__ __forceinline__ int wave_temperature(const EdgeStat* ch, const int* v
     return uni(chosen);
 }
 
+// the move of sz_set_lcb on a finished search (include/sigmazero.h is the rule, sz_lcb.h the arithmetic): ch[0..n) the root's children with the
+// tree's N and W, Q[0..n) their square sums, vis[0..n) the counts the move choice reads.  Lanes = children: c* is the first maximum of vis
+// (wave_ending's butterfly), every child's bound is formed once (lcb_out, optional, receives them), and the first maximum of the bounds over the
+// candidates is found with wave_select_child's butterfly and lowest-index tie-break.  Without a candidate the move is c*.  *lcb_move / *lcb_star:
+// the bounds of the move and of c* (NaN with N < 2); *ncand: the candidates; *bad: ssqrt arguments treated as 0.0.  Every lane returns the same.
+__device__ __forceinline__ int wave_lcb(const EdgeStat* ch, const double* Q, const int* vis, int n, const sz_lcb_options& o, double* lcb_out, int* cstar,
+                                        double* lcb_move, double* lcb_star, int* ncand, int* bad) {
+    const int lane = lane_id();
+    int bn = -1, ci = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) { const int nc = vis[c]; if (nc > bn) { bn = nc; ci = c; } }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int on = __shfl_xor(bn, off), oi = __shfl_xor(ci, off);
+        if (on > bn || (on == bn && oi < ci)) { bn = on; ci = oi; }
+    }
+    const int cs = uni(ci), nstar = uni(bn);
+    const double z = (double)o.stdevs, p = (double)o.min_visit_prop;
+    double best = 0.0, vstar = sz_lcb_nan(); int bi = 0x7fffffff;
+    int cand = 0, nbad = 0;
+    for (int c = lane; c < n; c += 64) {
+        const EdgeStat s = ch[c];
+        const double val = sz_lcb_value(s.N, s.W, Q[c], z, &nbad);
+        if (lcb_out) lcb_out[c] = val;
+        if (c == cs) vstar = val;
+        if (!sz_lcb_candidate(s.N, vis[c], nstar, p)) continue;
+        cand++;
+        if (bi == 0x7fffffff || val > best) { best = val; bi = c; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(best, off); const int oi = __shfl_xor(bi, off);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+        cand += __shfl_xor(cand, off); nbad += __shfl_xor(nbad, off);
+    }
+    bi = uni(bi);
+    // c*'s bound lives in the lane that owns c* (cs & 63): hand it to every lane
+    vstar = __shfl(vstar, cs & 63);
+    *cstar = cs; *ncand = uni(cand); *bad = uni(nbad);
+    *lcb_star = uni_f64(vstar);
+    if (bi == 0x7fffffff) { *lcb_move = *lcb_star; return cs; }
+    *lcb_move = uni_f64(best);
+    return bi;
+}
+
 // solver update after a backup whose last node path[d] has just become proven: walk towards the root; the parent of a newly proven node is
 // recomputed from its children alone (lanes = children): WIN if any child is LOSS, else, when it is complete and every child is proven,
 // DRAW if any child is DRAW, else LOSS.  The walk ends at the first node that stays UNKNOWN.  Returns the number of nodes proven.
@@ -882,6 +949,18 @@ __device__ __forceinline__ void wave_backprop(EdgeStat* es, const int* path, int
     }
     __threadfence_block();
 }
+// ... and under sz_set_lcb (SpreadOpts): the square of the same sv beside it, in the same order.  sv * sv is exact, the sum one rounding.
+__device__ __forceinline__ void wave_backprop(EdgeStat* es, double* Q, const int* path, int d, double v) {
+    for (int j = lane_id(); j <= d; j += 64) {
+        const int ei = path[j];
+        EdgeStat* e = es + ei;
+        double sv = ((d - j) & 1) ? -v : v;
+        e->W = e->W + sv;
+        e->N = e->N + 1;
+        Q[ei] = Q[ei] + sv * sv;
+    }
+    __threadfence_block();
+}
 
 // make a new position from `parent` by action index and finish it (movegen, key, repetition, terminal).
 // D = tree depth of the new position; path[0..D-1] are the edges above it.
@@ -1006,6 +1085,7 @@ __global__ void k_reset_endings(EndState* st, const uint8_t* active, int B, int 
 template <bool VL, bool SOLVE, typename... FO>
 __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch vb, BeginOpts o, FO... fo) {
     constexpr bool FORCED = has_opt<ForcedOpts, FO...>;
+    constexpr bool SPREAD = has_opt<SpreadOpts, FO...>;
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -1063,6 +1143,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
         if constexpr (SOLVE) { if (szm_term(X.meta)) m.pad = szm_loss(X.meta) ? PR_LOSS : PR_DRAW; }
         bp.em[0] = m;
         bp.gpath[0] = 0;
+        if constexpr (SPREAD) opt_of<SpreadOpts>(fo...).Q[(size_t)b * v.e_cap] = 0.0;      // sz_set_lcb: the root edge is created
     }
     int st = (status & ST_ACTIVE) | ST_SEARCHING | qbit | fbit;
     const int budget = o.target ? uni(o.target[b]) : board_budget(v, b);     // a fresh root: the visit target is a budget
@@ -1073,6 +1154,7 @@ __global__ __launch_bounds__(64) void k_search_begin(View v, void* planes, Batch
             int S = budget > 0 ? budget : 0;
             double tv = szm_loss(X.meta) ? -1.0 : 0.0;
             bp.es[0].W = tv * (double)S; bp.es[0].N = 1 + S;
+            if constexpr (SPREAD) opt_of<SpreadOpts>(fo...).Q[(size_t)b * v.e_cap] = (tv * tv) * (double)S;      // sz_set_lcb: the budget counted out at once
             Ctl* c = bp.ctl; c->status = st | ST_DONE; c->n_nodes = 1; c->n_edges = 1; c->sims_done = S;
             c->n_term += (unsigned long long)S; c->pend_node = -1; c->pend_depth = 0;
             if constexpr (VL) c->n_pend = 0;
@@ -1134,6 +1216,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
     static_assert(!GTREE || !FPU, "sz_set_gumbel_tree consults neither site of sz_set_fpu");
     constexpr bool PUCT = has_opt<PuctOpts, FO...>;
     static_assert(!GUMBEL || !PUCT, "sz_set_gumbel and sz_set_cpuct refuse each other");
+    constexpr bool SPREAD = has_opt<SpreadOpts, FO...>;
+    static_assert(!GUMBEL || !SPREAD, "sz_set_gumbel and sz_set_lcb refuse each other");
     extern __shared__ u64 lds64[];
     u64* hist = lds64; u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     const int b = blockIdx.x, lane = lane_id();
@@ -1224,6 +1308,7 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
                         EdgeStat s; s.W = 0.0; s.N = 0; s.P = p;
                         bp.es[slot] = s;
                         if constexpr (VL) vb.vk[(size_t)b * v.e_cap + slot] = 0;
+                        if constexpr (SPREAD) opt_of<SpreadOpts>(fo...).Q[(size_t)b * v.e_cap + slot] = 0.0;
                         EdgeMeta m; m.first = -1; m.node = -1; m.n = 0; m.action = sact[c]; m.term = 0; m.tval = 0; m.pad = 0;
                         bp.em[slot] = m;
                     }
@@ -1253,7 +1338,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         if constexpr (VL) {                                             // its descent is no longer in flight
             for (int j = lane; j <= d; j += 64) vb.vk[(size_t)b * v.e_cap + path[j]] -= 1;
         }
-        wave_backprop(bp.es, path, d, val);
+        if constexpr (SPREAD) wave_backprop(bp.es, opt_of<SpreadOpts>(fo...).Q + (size_t)b * v.e_cap, path, d, val);
+        else wave_backprop(bp.es, path, d, val);
         sims++; n_expand++; sum_depth += d; sum_k += kept;
         if constexpr (!VL) break;
         __syncthreads();                                                // path, mask and stash in LDS are reused by the next leaf
@@ -1331,7 +1417,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         STEP_STAMP(2);
         if constexpr (SOLVE) {
             if (proven) {                                               // the simulation ends here with the proven value (terminal leaves included)
-                wave_backprop(bp.es, path, d, proven == PR_WIN ? 1.0 : (proven == PR_DRAW ? 0.0 : -1.0));
+                if constexpr (SPREAD) wave_backprop(bp.es, opt_of<SpreadOpts>(fo...).Q + (size_t)b * v.e_cap, path, d, proven == PR_WIN ? 1.0 : (proven == PR_DRAW ? 0.0 : -1.0));
+                else wave_backprop(bp.es, path, d, proven == PR_WIN ? 1.0 : (proven == PR_DRAW ? 0.0 : -1.0));
                 sims++; n_term++; sum_depth += d;
                 if (!uni((int)m.term)) n_stop++;
                 continue;
@@ -1342,7 +1429,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
             if (VL && !uni((int)m.term) && m.first < 0) break;          // batched: a collision with a leaf pending in this step ends the gather
             // visited leaf without children: a terminal position (mcts.py:104-109)
             double tv = (double)(int)m.tval;
-            wave_backprop(bp.es, path, d, tv);
+            if constexpr (SPREAD) wave_backprop(bp.es, opt_of<SpreadOpts>(fo...).Q + (size_t)b * v.e_cap, path, d, tv);
+            else wave_backprop(bp.es, path, d, tv);
             sims++; n_term++; sum_depth += d;
             continue;
         }
@@ -1363,7 +1451,8 @@ __global__ __launch_bounds__(64, 4) void k_search_step(View v, const float* __re
         __threadfence_block();
         if (is_term) {                                                  // get_value_and_terminated -> (0|-1, True)
             double tv = szm_loss(X.meta) ? -1.0 : 0.0;
-            wave_backprop(bp.es, path, d, tv);
+            if constexpr (SPREAD) wave_backprop(bp.es, opt_of<SpreadOpts>(fo...).Q + (size_t)b * v.e_cap, path, d, tv);
+            else wave_backprop(bp.es, path, d, tv);
             sims++; n_term++; sum_depth += d;
             if constexpr (SOLVE) n_proved += wave_solver_update(bp.em, path, d);
             continue;
@@ -1526,6 +1615,8 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     constexpr bool PUCT = has_opt<PuctOpts, FO...>;
     static_assert(!PUCT || (FORCED && !GUMBEL), "policy-target pruning is k_play's only use of the exploration rate");
     static_assert(!GUMBEL || (!SOLVE && !FORCED && !ENDING && !TEMP), "sz_set_gumbel refuses the solver, forced playouts, endings and the move temperature");
+    constexpr bool LCB = has_opt<LcbOpts, FO...>;
+    static_assert(!GUMBEL || !LCB, "sz_set_gumbel and sz_set_lcb refuse each other");
     extern __shared__ u64 lds64[];
     u64* mask = lds64 + LDS_HIST_WORDS; int* path = (int*)(lds64 + LDS_HIST_WORDS + LDS_MASK_WORDS);
     int* vis_lds = path + 8;
@@ -1537,6 +1628,12 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     }
     if constexpr (TEMP) {                                                // likewise: no eligible child, p NaN
         if (lane == 0) { opt_of<TempOpts>(fo...).nelig[b] = 0; opt_of<TempOpts>(fo...).pch[b] = __longlong_as_double(0x7ff8000000000000LL); }
+    }
+    if constexpr (LCB) {                                                 // likewise: no move, no c*, no bound, no candidate, not decided
+        if (lane == 0) {
+            const LcbOpts& lo = opt_of<LcbOpts>(fo...);
+            lo.move[b] = -1; lo.cstar[b] = -1; lo.lcb2[(size_t)b * 2] = sz_lcb_nan(); lo.lcb2[(size_t)b * 2 + 1] = sz_lcb_nan(); lo.ncand[b] = 0; lo.decided[b] = 0;
+        }
     }
     if (!(status & ST_SEARCHING) || !(status & ST_DONE) || (status & (ST_ERROR | ST_GAMEOVER))) return;
     EdgeMeta rm = bp.em[0];
@@ -1599,6 +1696,7 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
     }
     // np.random.choice: cdf = cumsum(p); cdf /= cdf[-1]; idx = searchsorted(cdf, u, 'right')   (sequential f64, like numpy)
     int chosen = 0;
+    int temp_kind = TEMP_SAMPLED;                                        // sz_set_lcb reads how wave_temperature came to its move
     if constexpr (GUMBEL) {
         const GumbelOpts& go = opt_of<GumbelOpts>(fo...);
         chosen = wave_gumbel_play(bp.es + first, go.g ? go.g + (size_t)b * SZ_MAX_MOVES : nullptr, n, go.o, go.vhat[b], go.work + (size_t)b * SZ_MAX_MOVES,
@@ -1618,6 +1716,7 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
         int kind, ne, ex; double p;
         chosen = wave_temperature(bp.es + first, vis_lds, n, to.o, uni_f64(to.temps[b]), uni_f64(uniforms[b]), pmove, to.work + (size_t)b * SZ_MAX_MOVES,
                                   &kind, &ne, &p, &ex);
+        temp_kind = kind;
         if (lane == 0) {
             to.nelig[b] = ne; to.pch[b] = p;
             to.stat[(size_t)b * 3 + (kind == TEMP_SAMPLED ? 0 : 1)] += 1;
@@ -1644,6 +1743,27 @@ __global__ __launch_bounds__(64) void k_play(View v, const double* uniforms, FO.
         chosen = idx;
     }
     chosen = uni(chosen);
+    if constexpr (LCB) {
+        // sz_set_lcb: where the move above is "the most visited one" (the negative uniform without the temperature option, wave_temperature's
+        // greedy kind with it; never the proving move of a root proven WIN) the rule's move takes its place, unless the option only observes
+        const LcbOpts& lo = opt_of<LcbOpts>(fo...);
+        int cs, ncand, nbad; double lcb_move, lcb_star;
+        const int mv = wave_lcb(bp.es + first, lo.Q + (size_t)b * v.e_cap + first, vis_lds, n, lo.o, nullptr, &cs, &lcb_move, &lcb_star, &ncand, &nbad);
+        bool greedy;
+        if constexpr (TEMP) greedy = temp_kind == TEMP_GREEDY;
+        else {
+            greedy = uni_f64(uniforms[b]) < 0.0;
+            if constexpr (SOLVE) { if (uni((int)rm.pad & PR_MASK) == PR_WIN) greedy = false; }
+        }
+        const bool decided = greedy && lo.o.select != 0;
+        if (decided) chosen = mv;
+        if (lane == 0) {
+            lo.move[b] = mv; lo.cstar[b] = cs; lo.lcb2[(size_t)b * 2] = lcb_move; lo.lcb2[(size_t)b * 2 + 1] = lcb_star; lo.ncand[b] = ncand; lo.decided[b] = decided ? 1 : 0;
+            lo.stat[(size_t)b * 3] += decided ? 1 : 0;
+            lo.stat[(size_t)b * 3 + 1] += mv != cs ? 1 : 0;
+            lo.stat[(size_t)b * 3 + 2] += (unsigned long long)nbad;
+        }
+    }
     const int action = uni((int)bp.em[first + chosen].action);
     SzPos R = load_pos(bp.npos);
     path[0] = 0;
@@ -2114,6 +2234,42 @@ __global__ __launch_bounds__(64) void k_debug_search_summary(const int* n_child,
 }
 
 // ------------------------------------------------------------------------------------------------
+// NON-REFERENCE option (sz_set_lcb): readout and test hooks.  The rule itself is wave_lcb, called by k_play<.., LcbOpts>.
+// ------------------------------------------------------------------------------------------------
+// the root children's square sums in sz_root_children's order (sz_root_value_spread); 0.0 beyond the children and on a board without a search
+__global__ __launch_bounds__(64) void k_root_spread(View v, const double* Q, double* out) {
+    const int b = blockIdx.x, lane = lane_id();
+    BoardPtrs bp = board_ptrs(v, b);
+    int n = 0, first = 0;
+    if (bp.ctl->status & ST_SEARCHING) { EdgeMeta m = bp.em[0]; n = m.n; first = m.first; }
+    for (int c = lane; c < SZ_MAX_CHILDREN; c += 64) out[(size_t)b * SZ_MAX_CHILDREN + c] = c < n ? Q[(size_t)b * v.e_cap + first + c] : 0.0;
+}
+
+// test hook (sz_debug_lcb): wave_lcb, the function k_play<.., LcbOpts> calls, on caller-supplied cases, one wave per case: the counts the move
+// choice reads, the tree's N, W and Q, the options.  lcb_out receives every child's bound.
+__global__ __launch_bounds__(64) void k_debug_lcb(const int* offsets, const int* vc, const int* tree_vc, const double* wsum, const double* qsum, const sz_lcb_options* opts,
+                                                  int* move_out, int* cstar_out, int* ncand_out, int* bad_out, double* lcb_out) {
+    extern __shared__ u64 lds64[];
+    EdgeStat* ch = (EdgeStat*)lds64;
+    int* vis = (int*)(ch + SZ_MAX_CHILDREN);
+    const int cs = blockIdx.x, lo = offsets[cs], n = offsets[cs + 1] - lo, lane = lane_id();
+    if (n <= 0 || n > SZ_MAX_CHILDREN) { if (lane == 0) { move_out[cs] = -1; cstar_out[cs] = -1; ncand_out[cs] = 0; bad_out[cs] = 0; } return; }
+    for (int c = lane; c < n; c += 64) { EdgeStat s; s.W = wsum[lo + c]; s.N = tree_vc[lo + c]; s.P = 0.0f; ch[c] = s; vis[c] = vc[lo + c]; }
+    __syncthreads();
+    int cstar, ncand, bad; double lm, ls;
+    const int mv = wave_lcb(ch, qsum + lo, vis, n, opts[cs], lcb_out + lo, &cstar, &lm, &ls, &ncand, &bad);
+    if (lane == 0) { move_out[cs] = mv; cstar_out[cs] = cstar; ncand_out[cs] = ncand; bad_out[cs] = bad; }
+}
+// ... and sz_ssqrt on an array of arguments, one lane per argument
+__global__ __launch_bounds__(64) void k_debug_ssqrt(const double* x, double* out, int* bad_out, int n) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    int bad = 0;
+    out[i] = sz_ssqrt(x[i], &bad);
+    if (bad_out) bad_out[i] = bad;
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------------
 // what sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel and sz_set_cpuct set for the next sz_search_begin, which takes it up whole: a search, its descent-only
@@ -2126,6 +2282,8 @@ struct Latched {
     int gumbel_tree;                // sz_set_gumbel_tree: != 0 (only beside gumbel_on) selects k_search_step<false, false, GumbelTreeOpts>
     int cpuct_on;                   // sz_set_cpuct: != 0 (never beside gumbel_on) selects the instantiations that take PuctOpts ...
     sz_cpuct_options cpuct;         // ... which run with these
+    int lcb_on;                     // sz_set_lcb: != 0 (never beside gumbel_on) selects the instantiations that take SpreadOpts / LcbOpts ...
+    sz_lcb_options lcb;             // ... and k_play's run with these
 };
 
 struct sz_engine {
@@ -2161,6 +2319,8 @@ struct sz_engine {
     int search_open;                // a sz_search_begin was made and neither sz_play, sz_play_moves nor a sz_compact_searching that found no board followed
     int sum_on;                     // sz_set_search_summary: sz_play launches k_summary_pre before k_play and k_summary_post after it
     SummaryOpts so;                 // ... with these; its arrays are allocated by the first enabling call (so.stat != NULL from then on)
+    LcbOpts lo;                     // sz_set_lcb: Q, the last play's outputs and the counters, allocated by the first enabling call (lo.stat != NULL from then on)
+    double* lcb_q;                  // ... lo.Q without the const: SpreadOpts::Q
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[sigmazero] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return SZ_ERR_HIP; } } while (0)
@@ -2188,13 +2348,17 @@ template <typename T> static int dalloc(sz_engine* e, T** p, size_t count) {
 // on, and with the option structs in force, in the order the kernels take them: ForcedOpts or else GumbelOpts (the search begun last, e->cur;
 // under Gumbel VL = SOLVE = false, which the setters' refusals see to; GumbelTreeOpts in its place and no FpuOpts under sz_set_gumbel_tree),
 // FpuOpts (e->cur), PuctOpts (e->cur; never beside GumbelOpts), TempOpts (sz_set_move_temperature; never beside GumbelOpts), EndOpts (sz_set_endings; `proven` cleared while the
-// solver is off; never beside GumbelOpts).  Each kernel takes the members of the pack that concern it: pick below.
+// solver is off; never beside GumbelOpts), SpreadOpts and LcbOpts (sz_set_lcb, e->cur; never beside GumbelOpts).  Each kernel takes the members of the pack that concern it: pick below.
 template <typename F> static void with_search_options(const sz_engine* e, F&& f) {
     const Latched& c = e->cur;
+    auto spread = [&](auto vl, auto solve, auto... o) {                     // sz_set_lcb, latched: the last two members, never beside GumbelOpts
+        if (c.lcb_on) { LcbOpts lo = e->lo; lo.o = c.lcb; f(vl, solve, o..., SpreadOpts{e->lcb_q}, lo); }
+        else f(vl, solve, o...);
+    };
     auto endings = [&](auto vl, auto solve, auto... o) {
         if constexpr (has_opt<GumbelOpts, decltype(o)...> || has_opt<GumbelTreeOpts, decltype(o)...>) f(vl, solve, o...);
-        else if (e->end_on) { EndOpts eo = e->eo; if (!decltype(solve)::value) eo.o.proven = 0; f(vl, solve, o..., eo); }
-        else f(vl, solve, o...);
+        else if (e->end_on) { EndOpts eo = e->eo; if (!decltype(solve)::value) eo.o.proven = 0; spread(vl, solve, o..., eo); }
+        else spread(vl, solve, o...);
     };
     auto temperature = [&](auto vl, auto solve, auto... o) {
         if constexpr (has_opt<GumbelOpts, decltype(o)...>) endings(vl, solve, o...);
@@ -2393,10 +2557,11 @@ struct OptionState {
     bool cpuct;                     // sz_set_cpuct: what the next sz_search_begin takes up
     bool kld;                       // sz_set_kld_stop
     bool summary;                   // sz_set_search_summary
+    bool lcb;                       // sz_set_lcb: what the next sz_search_begin takes up
 };
 enum OptionSetter { BY_ANY, BY_LEAF_BATCHING, BY_SOLVER, BY_ROOT_NOISE };     // the setters whose own entry point accepts less than the engine runs
 static OptionState option_state(const sz_engine* e) {
-    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0, e->next.cpuct_on != 0, e->kld_on != 0, e->sum_on != 0};
+    return {e->vb.L, e->solver, e->next.forced_k > 0.0f, e->next.gumbel_on != 0, e->end_on != 0, e->v.root_gamma != nullptr, e->temp_on != 0, e->next.cpuct_on != 0, e->kld_on != 0, e->sum_on != 0, e->next.lcb_on != 0};
 }
 static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter by = BY_ANY) {
     const bool reuse = e->v.reuse != 0;
@@ -2412,6 +2577,8 @@ static int option_refusal(const sz_engine* e, const OptionState& p, OptionSetter
     if (p.gumbel && p.cpuct) return SZ_ERR_STATE;                           // Gumbel's rule is a chain of its own: the combination is a follow-up
     if (p.gumbel && p.kld) return SZ_ERR_STATE;                             // sequential halving plans on the goal: it cannot be lowered under it
     if (p.gumbel && p.summary) return SZ_ERR_STATE;                         // Gumbel's record is pi' and it exports v_mix itself: the combination is a follow-up
+    if (p.gumbel && p.lcb) return SZ_ERR_STATE;                             // Gumbel chooses its own move and backs up through its own rule: a follow-up
+    if (p.lcb && reuse) return SZ_ERR_STATE;                                // wave_keep_subtree and k_play_moves would have to compact Q too: a follow-up
     // sz_set_root_noise: a reused root was expanded as an inner node, on un-noised priors, and is never expanded again, so the noise would silently
     // apply to the first ply of a game only; and a reuse engine under sz_set_search_root_noise leaves that mode through that setter, which drops
     // the kept subtrees
@@ -2584,21 +2751,21 @@ static void launch_step(sz_engine* e, const float* policy, const float* value, v
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         std::apply([&](auto... k) {
             hipLaunchKernelGGL((k_search_step<VL, SOLVE, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, s, e->v, policy, value, planes, VL ? e->vb : Batch{}, k...);
-        }, pick<ForcedOpts, GumbelOpts, GumbelTreeOpts, FpuOpts, PuctOpts>(o...));      // the ending rules live in sz_play alone
+        }, pick<ForcedOpts, GumbelOpts, GumbelTreeOpts, FpuOpts, PuctOpts, SpreadOpts>(o...));      // the ending rules live in sz_play alone
     });
 }
 
 int sz_search_begin(sz_engine* e, void* planes_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     ENGINE_GUARD(e);
-    e->cur = e->next;                                                       // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel and sz_set_cpuct take effect here
+    e->cur = e->next;                                                       // sz_set_forced_playouts, sz_set_fpu, sz_set_gumbel, sz_set_cpuct and sz_set_lcb take effect here
     if (e->kld_on && !e->targets_set)                                       // sz_set_kld_stop: the goals k_search_begin reads as budgets (under targets it writes them itself)
         hipLaunchKernelGGL(k_kld_goals, dim3((e->v.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d_goal, e->budgets_set ? e->d_budget : nullptr, e->v.S, e->v.B);
     with_search_options(e, [&](auto vl, auto solve, auto... o) {
         constexpr bool VL = decltype(vl)::value, SOLVE = decltype(solve)::value;
         std::apply([&](auto... k) {
             hipLaunchKernelGGL((k_search_begin<VL, SOLVE, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, planes_dev, VL ? e->vb : Batch{}, e->bo, k...);
-        }, pick<ForcedOpts>(o...));                                         // the one option that acts where a root is made: the board's bit
+        }, pick<ForcedOpts, SpreadOpts>(o...));                             // the options that act where a root is made: the board's bit, the root edge's Q
     });
     HIPCHK(hipGetLastError());
     if (e->kld_on) {                                                        // sz_set_kld_stop: clean stop state for the boards that search
@@ -2892,6 +3059,103 @@ int sz_fetch_search_summary(sz_engine* e, double* root_q, double* best_q, double
 
 int sz_search_summary_stats(sz_engine* e, uint64_t out[2], void* stream) { return sum_board_counters(e, e ? e->so.stat : nullptr, 2, out, stream); }
 
+int sz_set_lcb(sz_engine* e, const sz_lcb_options* opt, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (opt) {
+        if (!std::isfinite(opt->stdevs) || opt->stdevs < 0.0f) return SZ_ERR_INVALID;
+        if (!(opt->min_visit_prop >= 0.0f && opt->min_visit_prop <= 1.0f)) return SZ_ERR_INVALID;      // a NaN fails the comparison
+    }
+    OptionState p = option_state(e);
+    p.lcb = opt != nullptr;
+    const int refused = option_refusal(e, p);
+    if (refused == SZ_ERR_INVALID) return refused;
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = between_searches(e, s);
+    if (rc) return rc;
+    if (!opt) { e->next.lcb_on = 0; return SZ_OK; }
+    if (refused) return refused;                                            // a reuse_subtree engine, or Gumbel is on: SZ_ERR_STATE, after the question whether the engine searches
+    const size_t B = e->v.B;
+    if (!e->lo.stat) {                                                      // the first enabling call: Q, the last play's outputs and the counters
+        LcbOpts o = e->lo;
+        double* q = nullptr;
+        if ((rc = dalloc(e, &q, B * (size_t)e->v.e_cap)) || (rc = dalloc(e, &o.move, B)) || (rc = dalloc(e, &o.cstar, B)) || (rc = dalloc(e, &o.lcb2, B * 2)) ||
+            (rc = dalloc(e, &o.ncand, B)) || (rc = dalloc(e, &o.decided, B)) || (rc = dalloc(e, &o.stat, B * 3))) return rc;
+        HIPCHK(hipMemsetAsync(q, 0, B * (size_t)e->v.e_cap * sizeof(double), s));
+        HIPCHK(hipMemsetAsync(o.stat, 0, B * 3 * sizeof(unsigned long long), s));
+        o.Q = q;
+        e->lo = o; e->lcb_q = q;
+    }
+    if (!e->next.lcb_on) {                                                  // off -> on: no sz_play of the option to describe yet
+        HIPCHK(hipMemsetAsync(e->lo.move, 0xff, B * sizeof(int), s));       // -1
+        HIPCHK(hipMemsetAsync(e->lo.cstar, 0xff, B * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(e->lo.lcb2, 0xff, B * 2 * sizeof(double), s));    // all ones: a NaN
+        HIPCHK(hipMemsetAsync(e->lo.ncand, 0, B * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(e->lo.decided, 0, B, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    e->next.lcb = *opt;
+    e->next.lcb.select = opt->select ? 1 : 0;
+    e->next.lcb_on = 1;
+    return SZ_OK;
+}
+
+int sz_fetch_lcb(sz_engine* e, int32_t* move, int32_t* cstar, double* lcb_move, double* lcb_cstar, int32_t* n_candidates, uint8_t* decided, void* stream) {
+    if (!e) return SZ_ERR_INVALID;
+    if (!e->lo.stat) return SZ_ERR_STATE;                                   // the option was never on
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = e->v.B;
+    std::vector<double> two(B * 2);
+    if (move) HIPCHK(hipMemcpyAsync(move, e->lo.move, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (cstar) HIPCHK(hipMemcpyAsync(cstar, e->lo.cstar, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(two.data(), e->lo.lcb2, B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (n_candidates) HIPCHK(hipMemcpyAsync(n_candidates, e->lo.ncand, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (decided) HIPCHK(hipMemcpyAsync(decided, e->lo.decided, B, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t b = 0; b < B; b++) { if (lcb_move) lcb_move[b] = two[b * 2]; if (lcb_cstar) lcb_cstar[b] = two[b * 2 + 1]; }
+    return SZ_OK;
+}
+
+int sz_lcb_stats(sz_engine* e, uint64_t out[3], void* stream) { return sum_board_counters(e, e ? e->lo.stat : nullptr, 3, out, stream); }
+
+int sz_root_value_spread(sz_engine* e, double* sq_sum_dev, void* stream) {
+    if (!e || !sq_sum_dev) return SZ_ERR_INVALID;
+    if (!e->lo.stat || !e->cur.lcb_on) return SZ_ERR_STATE;                 // the search begun last kept no second moment
+    ENGINE_GUARD(e);
+    hipLaunchKernelGGL(k_root_spread, dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, e->lo.Q, sq_sum_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_tree_spread(sz_engine* e, int32_t board, int32_t max_nodes, double* sq_sum, int32_t* n_out, void* stream) {
+    if (!e || board < 0 || board >= e->v.B || !n_out) return SZ_ERR_INVALID;
+    if (!e->lo.stat || !e->cur.lcb_on) return SZ_ERR_STATE;                 // the search begun last kept no second moment
+    ENGINE_GUARD(e);
+    hipStream_t s = (hipStream_t)stream;
+    Ctl c;
+    HIPCHK(hipMemcpyAsync(&c, e->v.ctl + board, sizeof c, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n_out = 0;
+    if (!(c.status & ST_SEARCHING) || c.n_edges <= 0) return SZ_OK;
+    std::vector<EdgeMeta> em(c.n_edges);
+    std::vector<double> q(c.n_edges);
+    HIPCHK(hipMemcpyAsync(em.data(), e->v.em + (size_t)board * e->v.e_cap, em.size() * sizeof(EdgeMeta), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(q.data(), e->lo.Q + (size_t)board * e->v.e_cap, q.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<int> stack;                                 // the walk of sz_debug_tree
+    int n = 0;
+    stack.push_back(0);
+    while (!stack.empty()) {
+        const int ed = stack.back(); stack.pop_back();
+        if (n < max_nodes && sq_sum) sq_sum[n] = q[ed];
+        n++;
+        if (em[ed].first >= 0) for (int k = (int)em[ed].n - 1; k >= 0; k--) stack.push_back(em[ed].first + k);
+    }
+    *n_out = n;
+    return SZ_OK;
+}
+
 int sz_set_gumbel(sz_engine* e, const sz_gumbel_options* opt, const double* g_dev, void* stream) {
     if (!e) return SZ_ERR_INVALID;
     if (opt) {
@@ -3130,8 +3394,8 @@ int sz_play(sz_engine* e, const double* uniforms_dev, void* stream) {
             hipLaunchKernelGGL((k_play<decltype(solve)::value, decltype(k)...>), dim3(e->v.B), dim3(64), e->lds_bytes, (hipStream_t)stream, e->v, uniforms_dev, k...);
         };
         // first-play urgency acts in the descent alone; the exploration rate reaches k_play for pruning alone, so only beside ForcedOpts
-        if constexpr (has_opt<ForcedOpts, decltype(o)...>) std::apply(launch, pick<ForcedOpts, GumbelOpts, PuctOpts, TempOpts, EndOpts>(play_opt(o)...));
-        else std::apply(launch, pick<ForcedOpts, GumbelOpts, TempOpts, EndOpts>(play_opt(o)...));
+        if constexpr (has_opt<ForcedOpts, decltype(o)...>) std::apply(launch, pick<ForcedOpts, GumbelOpts, PuctOpts, TempOpts, EndOpts, LcbOpts>(play_opt(o)...));
+        else std::apply(launch, pick<ForcedOpts, GumbelOpts, TempOpts, EndOpts, LcbOpts>(play_opt(o)...));
     });
     if (e->sum_on)                                                          // ... and when the ply's record exists
         hipLaunchKernelGGL(k_summary_post, dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, e->so);
@@ -3335,6 +3599,21 @@ int sz_debug_gumbel(const double* x_dev, double* slog_out_dev, double* sexp_out_
     hipLaunchKernelGGL(k_debug_gumbel, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(double) + sizeof(float)), (hipStream_t)stream,
                        x_dev, slog_out_dev, sexp_out_dev, tnm_dev, level_out_dev, offsets_dev, vc_dev, value_sum_dev, prior_dev, g_dev, visit_dev, goal_dev,
                        root_value_dev, opts_dev, selected_out_dev, fallback_out_dev, final_out_dev, policy_out_dev, v_mix_out_dev);
+    HIPCHK(hipGetLastError());
+    return SZ_OK;
+}
+
+int sz_debug_lcb(const double* x_dev, double* ssqrt_out_dev, int32_t* x_bad_out_dev, int32_t n_x, const int32_t* offsets_dev, const int32_t* vc_dev,
+                 const int32_t* tree_vc_dev, const double* value_sum_dev, const double* sq_sum_dev, const sz_lcb_options* opts_dev, int32_t* move_out_dev,
+                 int32_t* cstar_out_dev, int32_t* n_candidates_out_dev, int32_t* bad_out_dev, double* lcb_out_dev, int32_t n_cases, void* stream) {
+    if (!x_dev && !offsets_dev) return SZ_ERR_INVALID;
+    if (x_dev && (!ssqrt_out_dev || n_x <= 0)) return SZ_ERR_INVALID;
+    if (offsets_dev && (n_cases <= 0 || !vc_dev || !tree_vc_dev || !value_sum_dev || !sq_sum_dev || !opts_dev || !move_out_dev || !cstar_out_dev ||
+                        !n_candidates_out_dev || !bad_out_dev || !lcb_out_dev)) return SZ_ERR_INVALID;
+    if (x_dev) hipLaunchKernelGGL(k_debug_ssqrt, dim3((n_x + 63) / 64), dim3(64), 0, (hipStream_t)stream, x_dev, ssqrt_out_dev, x_bad_out_dev, n_x);
+    if (offsets_dev)
+        hipLaunchKernelGGL(k_debug_lcb, dim3(n_cases), dim3(64), SZ_MAX_CHILDREN * (sizeof(EdgeStat) + sizeof(int)), (hipStream_t)stream, offsets_dev, vc_dev, tree_vc_dev,
+                           value_sum_dev, sq_sum_dev, opts_dev, move_out_dev, cstar_out_dev, n_candidates_out_dev, bad_out_dev, lcb_out_dev);
     HIPCHK(hipGetLastError());
     return SZ_OK;
 }

@@ -295,6 +295,43 @@ def search_targets_of(args):
     return q_ratio, src, fraction
 
 
+LCB_KEYS = ("stdevs", "min_visit_prop", "select")
+
+
+def lcb_options_of(args):
+    """The lower-confidence-bound move selection of args, checked: (stdevs, min_visit_prop, select) with the two numbers as the f32 the engine
+    holds, or None when the key is absent.  NON-REFERENCE, default off.
+
+    args["lcb"] = {"stdevs": 5.0, "min_visit_prop": 0.15, "select": True} (the defaults, KataGo's lcbStdevs and minVisitPropForLCB) makes the
+    tree keep the sum of the squares of the values backed up through every edge (sz_set_lcb) and, where play() would play the most visited
+    move (a negative uniform, or T = 0 under args["temperature"]), play the move whose mean value is best after `stdevs` standard errors are
+    taken off, among the root moves with at least two visits and at least `min_visit_prop` of the most visited move's.  A sampled play is
+    chosen as without the key.  select False only observes: the moves are those without the key, fetch_lcb() / lcb_stats() still report
+    what the rule would have played.  Refused with args["gumbel"], which chooses its own move, and with args["reuse_subtree"], whose kept
+    subtree would have to carry the square sums along.  Checked in this order: the dict and its keys, stdevs, min_visit_prop, select, the
+    combinations.  Its effect on playing strength is unmeasured."""
+    opt = args.get("lcb")
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or not set(opt) <= set(LCB_KEYS):
+        raise ValueError("args['lcb'] must be a dict with keys from %s, got %r" % (LCB_KEYS, opt))
+    number = lambda x: not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating))
+    z = opt.get("stdevs", 5.0)
+    if not number(z) or not (math.isfinite(z) and 0 <= z <= float(np.finfo(np.float32).max)):       # NaN fails the comparison; the struct holds an f32
+        raise ValueError("args['lcb']['stdevs'] must be a finite number >= 0, got %r" % (z,))
+    p = opt.get("min_visit_prop", 0.15)
+    if not number(p) or not 0.0 <= p <= 1.0:
+        raise ValueError("args['lcb']['min_visit_prop'] must be a number in [0, 1], got %r" % (p,))
+    sel = opt.get("select", True)
+    if not isinstance(sel, (bool, np.bool_)):
+        raise ValueError("args['lcb']['select'] must be True or False, got %r" % (sel,))
+    if args.get("gumbel") is not None:
+        raise ValueError("args['lcb'] and args['gumbel'] exclude each other: the Gumbel search chooses its own move")
+    if args.get("reuse_subtree", False):
+        raise ValueError("args['lcb'] and args['reuse_subtree'] exclude each other: the kept subtree does not carry the square sums")
+    return float(np.float32(z)), float(np.float32(p)), bool(sel)
+
+
 GUMBEL_KEYS = ("m", "c_visit", "c_scale")
 
 
@@ -510,6 +547,8 @@ class SelfPlayEngine:
         # NON-REFERENCE option (default off): the search summary and what training does with it, see search_targets_of
         self.search_targets = search_targets_of(self.args)
         self.search_summary = False   # sz_set_search_summary is on (set_search_summary)
+        # NON-REFERENCE option (default off): per-edge value spread and lower-confidence-bound move selection, see lcb_options_of
+        self.lcb = lcb_options_of(self.args)
         # NON-REFERENCE option (default off): Gumbel root search with sequential halving and the completed-Q policy target, see gumbel_options_of
         self.gumbel = gumbel_options_of(self.args)
         self._gumbel_g = None         # the device copy of the Gumbel draws in force (set_gumbel)
@@ -578,6 +617,8 @@ class SelfPlayEngine:
             self.set_kld_stop(self.kld_stop)
         if self.search_targets is not None:
             self.set_search_summary(True)
+        if self.lcb is not None:
+            self.set_lcb(self.lcb)
         if self.gumbel is not None:    # g = None (a deterministic search) until set_gumbel hands over draws
             self.set_gumbel(self.gumbel)
         if self.gumbel_tree:
@@ -763,6 +804,55 @@ class SelfPlayEngine:
         out = (C.c_uint64 * 2)()
         N.check(N.lib().sz_search_summary_stats(self._e, out, self._stream()), "sz_search_summary_stats")
         return int(out[0]), int(out[1])
+
+    def set_lcb(self, opts):
+        """Per-edge value spread and LCB move selection (sz_set_lcb, a NON-REFERENCE option) from the next begin() on, until changed.  opts:
+        (stdevs, min_visit_prop, select) as lcb_options_of returns it, or None = off.  Between searches only; refused on a reuse_subtree
+        engine and while the Gumbel search is on."""
+        if opts is None:
+            N.check(N.lib().sz_set_lcb(self._e, None, self._stream()), "sz_set_lcb")
+            self.lcb = None
+            return
+        z, p, sel = opts
+        o = N.sz_lcb_options(float(z), float(p), int(bool(sel)))
+        N.check(N.lib().sz_set_lcb(self._e, C.byref(o), self._stream()), "sz_set_lcb")
+        self.lcb = (float(np.float32(z)), float(np.float32(p)), bool(sel))
+
+    def fetch_lcb(self):
+        """sz_fetch_lcb after play(): dict of [B] arrays: move (the rule's move as a root-child index), cstar (the most visited child),
+        lcb_move / lcb_cstar (their bounds, NaN where the child has fewer than two visits), n_candidates, decided (1: the rule decided the
+        move played).  -1, -1, NaN, NaN, 0, 0 for a board that made no choice."""
+        B = self.B
+        out = dict(move=np.zeros(B, np.int32), cstar=np.zeros(B, np.int32), lcb_move=np.zeros(B, np.float64), lcb_cstar=np.zeros(B, np.float64),
+                   n_candidates=np.zeros(B, np.int32), decided=np.zeros(B, np.uint8))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        N.check(N.lib().sz_fetch_lcb(self._e, p(out["move"]), p(out["cstar"]), p(out["lcb_move"]), p(out["lcb_cstar"]), p(out["n_candidates"]),
+                                     p(out["decided"]), self._stream()), "sz_fetch_lcb")
+        return out
+
+    def lcb_stats(self):
+        """(plays the rule decided, plays at which its move differs from the most visited one, ssqrt arguments treated as 0), all boards,
+        cumulative (sz_lcb_stats)"""
+        out = (C.c_uint64 * 3)()
+        N.check(N.lib().sz_lcb_stats(self._e, out, self._stream()), "sz_lcb_stats")
+        return tuple(int(x) for x in out)
+
+    def root_value_spread(self):
+        """The root children's sums of squared backed-up values [B, SZ_MAX_MOVES] f64 in root_children()'s order (sz_root_value_spread); the
+        search begun last must have run under set_lcb"""
+        q = torch.zeros(self.B, N.SZ_MAX_MOVES, dtype=torch.float64, device=self.device)
+        N.check(N.lib().sz_root_value_spread(self._e, _ptr(q), self._stream()), "sz_root_value_spread")
+        torch.cuda.synchronize(self.device)
+        return q.cpu().numpy()
+
+    def debug_tree_spread(self, board):
+        """the sum of squared backed-up values of every edge of one board's tree (f64), rows in debug_tree()'s order (sz_debug_tree_spread; a
+        search under set_lcb only)"""
+        n = C.c_int32()
+        N.check(N.lib().sz_debug_tree_spread(self._e, int(board), 0, None, C.byref(n), self._stream()), "sz_debug_tree_spread")
+        q = np.zeros(n.value, np.float64)
+        N.check(N.lib().sz_debug_tree_spread(self._e, int(board), n.value, q.ctypes.data_as(C.c_void_p), C.byref(n), self._stream()), "sz_debug_tree_spread")
+        return q
 
     def set_gumbel(self, opts, g=None):
         """Gumbel root search (sz_set_gumbel, a NON-REFERENCE option) from the next begin() on, until changed.  opts: (m, c_visit, c_scale) as

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .chess_tensor import Move, index_to_move, QUEEN
-from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, gumbel_tree_of, temperature_options_of, temperature_at, search_targets_of, ENDING_KINDS
+from .selfplay import SelfPlayEngine, unpack_planes, model_device, visit_target_options_of, forced_playout_options_of, ending_options_of, gumbel_options_of, gumbel_tree_of, temperature_options_of, temperature_at, search_targets_of, lcb_options_of, ENDING_KINDS
 
 device = "cuda" if torch.cuda.is_available() else "cpu"      # module global of the reference (sim.py:12); the engine itself follows the model's device
 
@@ -126,6 +126,9 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     'surprises' (its policy surprise KL(target || prior)) and 'value_targets' ((1 - q_ratio) * reward + q_ratio * search value, Python floats),
     all aligned with 'states'.  'rewards', 'actions' and the moves played are what they are without
     the key; train_rl takes the blended targets and the surprise weights from there.  Effect on training unmeasured.
+    args["lcb"] = {...} (NON-REFERENCE, selfplay.lcb_options_of): the engine keeps every edge's value spread and plays the lower-confidence-bound
+    move where a play is greedy (a negative uniform; T = 0 under args["temperature"]); sampled plays and every sample's fields are what they are
+    without the key.  stats gains 'lcb_decided' / 'lcb_differs' (sz_lcb_stats).  Strength effect unmeasured.
     args["gumbel"] = {"m": m, "c_visit": x, "c_scale": y} (NON-REFERENCE, selfplay.gumbel_options_of): the Gumbel root search (sz_set_gumbel), on fast
     and full plies alike.  The move is the search's own choice (`uniforms` is still drawn as always and not read by the engine) and a sample's
     'actions' dict holds the completed-Q improved policy as Python floats instead of visit fractions.  With `learning` the Gumbel(0,1) draws
@@ -159,6 +162,7 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
     if gumbel_noise is not None and gum is None:
         raise ValueError("gumbel_noise needs args['gumbel']")
     targets = search_targets_of(args)
+    lcb_opts = lcb_options_of(args)
     temp_opts = temperature_options_of(args)
     if temperature is not None and temp_opts is None:
         raise ValueError("temperature needs args['temperature']")
@@ -357,6 +361,8 @@ def play_games(model, args, n_games, c960=False, scharnagl=None, uniforms=None, 
         work["gumbel_fallbacks"] = eng.gumbel_stats()[1]
     if temp_opts is not None:
         work["tempered_plays"], work["greedy_plays"], work["excluded_children"] = eng.temperature_stats()
+    if lcb_opts is not None:
+        work["lcb_decided"], work["lcb_differs"] = eng.lcb_stats()[:2]
     eng.close()
     if stats is not None:
         stats.update(work)

@@ -6,7 +6,8 @@ process on one GPU play colour-swapped pairs of Chess960 games against each othe
 
 --a / --b take key=value engine args on top of the shared ones (C = 2, num_searches = --searches); values are read as JSON where they
 parse (true, 4, 0.5, {"resign_value": -0.9}) and as strings otherwise.  Prints one JSON line.  The defaults (32 pairs, 64 searches, games
-cut at 160 plies) finish in a few minutes.
+cut at 160 plies) finish in a few minutes.  A side that plays greedy moves takes lower-confidence-bound move selection through its engine:
+--a 'lcb={"stdevs": 5.0, "min_visit_prop": 0.15}' (selfplay.lcb_options_of).
 
 With the random-init weights this tool makes, the only ones the project has, the number says NOTHING about the strength of a trained
 configuration: a random network's values carry no information about who wins, so the match measures how two searches differ when both are
